@@ -9,12 +9,20 @@ One "step" = one full training iteration of the reference's loop (run_img2txt_di
 COCO-shape batch that is already resident in HBM: forward (region projections, embeddings, 12 BertLayers, LM head,
 masked-LM loss) + backward + loss-scaled fused Adam (+ RCCL gradient buckets when N > 1), dropout 0.1 as in training.
 Workload = BASELINE.json configs[1]: BERT-base 12L, 100 regions, seq_len 64 (L = 64+100+3 = 167), batch 64 per GPU, fp16.
-Rank 0 prints ONE JSON line: whole-job samples/s, plus
+Rank 0 prints ONE JSON line: whole-job samples/s and ms_per_step of the K timed steps.  A plain run does nothing else: set-up,
+W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR), the line.  With --full the line also carries
+  parity       -- full-size logits of the bench model vs the oracle on the device, before anything is timed;
+  config.varlen -- the same batches through the padding-free (packed) step, timed the same way;
   roofline     -- the dominant kernel (vlp_gemm_nt: every forward / dgrad GEMM): algorithmic FLOPs per launch / average launch
                   duration, measured live with HIP events on the launch stream in a second pass over the same K steps (so the
                   brackets do not perturb the timed steps);
   cpu_baseline -- the oracle (CPU restatement of the reference, fp32 fwd+bwd+BertAdam) timed on this box's host cores
                   on a bounded sample (rank 0, N = 1 only).
+The --no-* switches below drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0), float32, under 64 MB in all: the loss tuple
+(mlm_loss, vis_pretext_loss, vqa_loss), the head logits of its forward, and a fixed seeded sample of the updated parameters.  The inputs
+(weights, batch pool, dropout seeds) are a function of the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -255,6 +263,28 @@ def parity_block(p32, model, batch, tasks, dev):
     return out
 
 
+DUMP_MAX_ELEMS = 5 << 20            # per array: 20 MB of float32; three arrays can be that large (logits, two parameter groups): < 64 MB
+
+
+def dump_outputs(d, lt, model, eng, tasks):
+    """--dump-outputs DIR: the loss tuple train_step returned in the last timed step, the head logits of that step's forward and the
+    parameters it left, as DIR/<name>.npy (float32).  An array larger than DUMP_MAX_ELEMS is replaced by a fixed sample: the elements at
+    indices drawn from a generator seeded by the array's size alone, so the same run arguments always pick the same elements."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    m = model.module if hasattr(model, "module") else model
+    arrays = dict(zip(("mlm_loss", "vis_pretext_loss", "vqa_loss"), lt))
+    arrays["vqa_logits" if tasks == "vqa2" else "mlm_logits"] = m.last_vqa_logits if tasks == "vqa2" else m.last_mlm_logits
+    arrays["params_decay"], arrays["params_nodecay"] = eng.flat["decay"], eng.flat["nodecay"]
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     if len(sys.argv) >= 2 and sys.argv[1] == "--cpu-baseline-only":
         print(json.dumps(cpu_baseline_worker(float(sys.argv[2]), int(sys.argv[3]))))
@@ -276,7 +306,15 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the parity object (full-size logits vs the oracle on the device, before timing)")
     ap.add_argument("--pool", type=int, default=8, help="device-resident synthetic batches cycled by the timed steps (config.batch_pool)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL + the DDP wrapper even for one rank (path check)")
+    ap.add_argument("--full", action="store_true", help="also the parity object, the padding-free leg, the roofline sampling pass and the "
+                                                        "CPU baseline (each can be dropped with its --no-* switch); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be >= 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_events = args.no_varlen = True
+    want_parity = args.full and not args.no_parity
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -313,7 +351,8 @@ def main():
     p32, parity_err = None, None
     if not args.no_parity:
         # random-init weights of the architecture, drawn by the oracle's initialiser (init_bert_weights, N(0, 0.02): modeling.py:539-551) so that the
-        # parity block below can evaluate the SAME network in fp32 / reference-fp16; every rank loads the same values
+        # parity block below can evaluate the SAME network in fp32 / reference-fp16; every rank loads the same values (a plain run too:
+        # its timed steps train the network a --full run times)
         try:
             from oracle import vlp_oracle as O
             p32 = O.init_params(vocab_size=28996, layers=args.layers, tasks=args.tasks, seed=0)
@@ -345,7 +384,7 @@ def main():
                                     s2s_prob=args.s2s_prob, tasks=args.tasks, seed=1234 + 100 * rank + i), dev, half=True) for i in range(max(1, args.pool))]
     t_total = 100000
     parity = None
-    if not args.no_parity and rank == 0 and world == 1:
+    if want_parity and rank == 0 and world == 1:
         if p32 is None:
             parity = {"error": parity_err}
         else:
@@ -374,6 +413,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        if use_dist:
+            eng.wait_params()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, lt, model, eng, args.tasks)
     # roofline sampling: the SAME K steps once more, now with HIP events around every PROF_EVERY-th launch of the dominant kernel (on
     # the launch stream).  It is a separate, un-timed pass so that the event brackets (and the side-stream joins they need) do not
     # perturb the headline steps above.

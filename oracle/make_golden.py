@@ -264,9 +264,74 @@ def run_reference_loader_case(mode, n_tokens, seed, max_len_b=20, Nv=100, always
     return out, bbox, cls, feat, min(n_tokens, max_len_b)
 
 
+CONTRACT_PATH = os.path.join(GOLDEN_DIR, "reference_contract.npz")
+# (mode, n_tokens, seed, always_truncate_tail, max_pred, mask_prob): tests/test_oracle_vs_reference.py::test_text_preprocessor_reproduces_reference_sample_stream
+TEXT_CASES = [("s2s", 9, 1, True, 3, 0.15), ("bi", 14, 2, True, 3, 0.15), ("s2s", 31, 3, False, 5, 0.5), ("s2s", 40, 4, False, 8, 0.7)]
+# (mode, n_tokens, seed): ...::test_reference_loader_leaves_masked_region_columns_attendable
+MASKED_REGION_CASES = [("s2s", 9, 1), ("bi", 14, 2)]
+ADAM_RUNS = ((0.01, 3), (0.0, 2))
+SCHEDULE_X = (0.0, 0.001, 0.05, 0.5, 0.99, 1.2)
+
+
+def text_case_key(mode, n_tokens, seed, tail, max_pred, mask_prob):
+    return "text_%s_%d_%d_%d_%d_%g" % (mode, n_tokens, seed, tail, max_pred, mask_prob)
+
+
+def reference_contract():
+    """Small outputs of the reference's own code that the contract tests compare against where the reference tree is absent:
+    checkpoint key names, the entry script's flags, BertAdam's parameters after a few steps and its schedules, and the sample
+    stream of the reference's text preprocessor / loader on synthetic inputs."""
+    import re
+    import warnings
+    ref = ref_loader.load_reference()
+    out = {}
+    for tasks in ("img2txt", "vqa2"):
+        model = ref_loader.build_reference_model(dict(vocab_size=512, num_hidden_layers=1), tasks=tasks)
+        out["state_dict_keys_" + tasks] = np.asarray(sorted(model.state_dict().keys()))
+    src = open(os.path.join(ref_loader.REFERENCE_ROOT, "vlp", "run_img2txt_dist.py")).read()
+    live = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
+    out["entry_flags"] = np.asarray(sorted(set(re.findall(r"add_argument\(\s*['\"]--([a-z_0-9]+)['\"]", live))))
+    torch.manual_seed(0)
+    w0, g0 = torch.randn(300, 70), torch.randn(300, 70) * 3
+    out["adam_w0"], out["adam_g0"] = w0.numpy(), g0.numpy()
+    for wd, nsteps in ADAM_RUNS:
+        q = torch.nn.Parameter(w0.clone())
+        opt = ref.optimization.BertAdam([{"params": [q], "weight_decay": wd}], lr=1e-3, warmup=0.1, t_total=20)
+        for s in range(nsteps):
+            q.grad = g0.clone() * (s + 1)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                opt.step()
+        out["adam_w_%g_%d" % (wd, nsteps)] = q.detach().numpy().copy()
+    for name in ("warmup_linear", "warmup_constant"):
+        out["schedule_" + name] = np.asarray([getattr(ref.optimization, name)(x, 0.1) for x in SCHEDULE_X], dtype=np.float64)
+    for case in TEXT_CASES:
+        mode, n_tokens, seed, tail, max_pred, mask_prob = case
+        r = run_reference_loader_case(mode, n_tokens, seed, always_truncate_tail=tail, max_pred=max_pred, mask_prob=mask_prob)
+        o, nb = r[0], r[4]
+        k = text_case_key(*case)
+        for i, f in enumerate(("input_ids", "segment_ids", "input_mask", "masked_ids", "masked_pos", "masked_weights", "is_next", "task_idx")):
+            v = o[i].numpy() if torch.is_tensor(o[i]) else np.asarray(o[i])
+            out[k + "_" + f] = v.astype(np.uint8) if f == "input_mask" else v.astype(np.int64)
+        out[k + "_len_b"] = np.asarray(nb)
+    for mode, n_tokens, seed in MASKED_REGION_CASES:
+        o = run_reference_loader_case(mode, n_tokens, seed, mask_image_regions=True, vis_mask_prob=0.25)[0]
+        out["masked_region_%s_%d_%d_input_mask" % (mode, n_tokens, seed)] = o[2].numpy().astype(np.uint8)
+        out["masked_region_%s_%d_%d_vis_masked_pos" % (mode, n_tokens, seed)] = np.asarray([int(p) for p in o[9]], dtype=np.int64)
+    return out
+
+
+def load_contract():
+    return dict(np.load(CONTRACT_PATH, allow_pickle=False))
+
+
 def main():
     torch.set_num_threads(8)
     os.makedirs(GOLDEN_DIR, exist_ok=True)
+    np.savez_compressed(CONTRACT_PATH, **reference_contract())          # small, cheap: written by every run
+    print("reference contract -> %s (%.0f KB)" % (CONTRACT_PATH, os.path.getsize(CONTRACT_PATH) / 1024))
+    if "--contract-only" in sys.argv:
+        return
     only = [a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--only=")]
     if only:            # python -m oracle.make_golden --only=name[,name]: (re)generate the named forward / backward cases only
         for name in only[0]:

@@ -405,7 +405,7 @@ def test_bench_through_torchrun_and_rccl_world1(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", {"allreduce": "29517", "rs_ag": "29523", "sharded": "29525"}[mode], os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--layers", "2", "--batch", "8", "--force-dist", "--no-cpu-baseline"]
+           "--layers", "2", "--batch", "8", "--force-dist", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=dict(os.environ, VLP_DDP_MODE=mode))
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -447,7 +447,7 @@ def test_bench_world2_on_one_gpu_real_engine_ddp_hooks(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", {"allreduce": "29519", "rs_ag": "29521", "sharded": "29527"}[mode], os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--layers", "3",
-           "--batch", "16", "--no-cpu-baseline"]
+           "--batch", "16", "--no-cpu-baseline", "--full"]
     env = dict(os.environ, VLP_BENCH_SHARE_GPU="1", VLP_DIST_BACKEND="gloo", VLP_BENCH_CHECK_RANKS="1", VLP_DDP_MODE=mode)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

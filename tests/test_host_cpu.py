@@ -147,11 +147,9 @@ def test_engine_layout_and_buckets():
 def test_entry_script_arguments_match_reference():
     from vlp_amd import run_img2txt_dist as R
     ours = {a.dest: a.default for a in R.build_parser()._actions if a.dest != "help"}
-    ref_py = "/root/reference/vlp/run_img2txt_dist.py"
-    if os.path.exists(ref_py):
-        live = "\n".join(l for l in open(ref_py).read().splitlines() if not l.lstrip().startswith("#"))
-        flags = set(re.findall(r"add_argument\(\s*['\"]--([a-z_0-9]+)['\"]", live))
-        assert flags <= set(ours), flags - set(ours)
+    from oracle.make_golden import load_contract
+    flags = set(str(f) for f in load_contract()["entry_flags"])     # the reference entry script's flags (tests/golden/reference_contract.npz)
+    assert flags and flags <= set(ours), flags - set(ours)
     args = R.derive_args(R.build_parser().parse_args(["--enable_butd", "--fp16", "--max_len_b", "64", "--output_dir", "/tmp/x"]))
     assert args.max_seq_length == 167 and args.dist_url == "file:///tmp/x/nonexistent_file"
     with pytest.raises(AssertionError):

@@ -30,12 +30,12 @@ task_labsuite() {
 task_smoke() { timeout 300 python __graft_entry__.py > $OUT/smoke.log 2>&1; echo "smoke exit $?"; tail -n 1 $OUT/smoke.log; }
 task_bench() { local tag=${1:-default}; shift; timeout 600 python bench.py "$@" > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err; echo "bench exit $?"; cut -c1-2500 $OUT/bench_$tag.json; }
 task_shapes() {
-  timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-parity --s2s_prob 0.75 > $OUT/bench_cc.json 2>/dev/null; cut -c1-200 $OUT/bench_cc.json
-  timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-parity --tasks vqa2 --s2s_prob 0 > $OUT/bench_vqa.json 2>/dev/null; cut -c1-200 $OUT/bench_vqa.json; }
+  timeout 300 python bench.py --steps 10 --warmup 5 --full --no-cpu-baseline --no-parity --s2s_prob 0.75 > $OUT/bench_cc.json 2>/dev/null; cut -c1-200 $OUT/bench_cc.json
+  timeout 300 python bench.py --steps 10 --warmup 5 --full --no-cpu-baseline --no-parity --tasks vqa2 --s2s_prob 0 > $OUT/bench_vqa.json 2>/dev/null; cut -c1-200 $OUT/bench_vqa.json; }
 task_prof() {
   local mode=${1:-dense} steps=${2:-20} v=0; [ "$mode" = varlen ] && v=1
   rm -rf /tmp/prof_$mode
-  VLP_VARLEN=$v VLP_WGRAD_SIDE_STREAM=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$mode -o p -- python bench.py --steps $steps --warmup 5 --no-cpu-baseline --no-parity --no-varlen > $OUT/prof_bench_line_$mode.json 2> $OUT/prof_$mode.err; echo "rocprof $mode exit $?"
+  VLP_VARLEN=$v VLP_WGRAD_SIDE_STREAM=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$mode -o p -- python bench.py --steps $steps --warmup 5 --full --no-cpu-baseline --no-parity --no-varlen > $OUT/prof_bench_line_$mode.json 2> $OUT/prof_$mode.err; echo "rocprof $mode exit $?"
   python tools/prof_summary.py $(find /tmp/prof_$mode -name "*kernel_trace.csv" | head -1) 0.45 > $OUT/prof_summary_$mode.txt 2>&1; head -n 24 $OUT/prof_summary_$mode.txt | cut -c1-170
   cp $(find /tmp/prof_$mode -name "*kernel_stats.csv" | head -1) $OUT/prof_kernel_stats_$mode.csv 2>/dev/null; }
 task_pmc() { bash tools/gpu_pmc_bench.sh > $OUT/pmc_run.log 2>&1; tail -n 30 $OUT/pmc_run.log; }
@@ -52,7 +52,7 @@ task_decode() {
   python tools/prof_summary.py /tmp/profd/dec_kernel_trace.csv 0.25 > $OUT/prof_decode_steady.txt; head -n 30 $OUT/prof_decode_steady.txt | cut -c1-170; }
 task_loader() { N_IMAGES=${1:-2048} timeout 900 python tools/loader_bench.py > $OUT/loader_bench.json 2> $OUT/loader_bench.err; cat $OUT/loader_bench.json; }
 task_soak() { bash tools/gpu_soak.sh > /dev/null 2>&1; grep -v "^    " $OUT/soak.txt; }
-task_evidence() { task_suite; task_smoke; task_bench default; task_shapes; task_prof dense; task_prof varlen; task_decode; task_loader; }
+task_evidence() { task_suite; task_smoke; task_bench default --full; task_shapes; task_prof dense; task_prof varlen; task_decode; task_loader; }
 
 [ $# -eq 0 ] && { sed -n 2,22p "$0"; exit 0; }
 args=()
