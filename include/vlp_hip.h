@@ -28,6 +28,8 @@ extern "C" {
 #endif
 
 #define VLP_ABI_VERSION 5      /* 5 (round 6): + vlp_dec_gemm, vlp_dec_reduce_ln, vlp_argmax_rows2 (no existing struct changed) */
+/* + vlp_mlm_loss_ls_fwd / vlp_mlm_loss_ls_bwd with their own argument structs: purely additive (no existing struct or entry point
+ * changed), so a binding written against version 5 keeps working and the version number stays 5. */
 
 typedef enum {
     VLP_OK = 0,
@@ -523,6 +525,42 @@ typedef struct {
     int32_t rows, V;
 } vlp_mlm_loss_bwd_args;
 int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream);
+
+/* Label-smoothed masked-LM loss (loss.py LabelSmoothingLoss, used at modeling.py:995-999, 1104-1106 when
+ * config.label_smoothing is set): per row the KL divergence sum_w q[w] * (log q[w] - log_softmax(logits[r])[w])
+ * in fp32 (0 log 0 = 0) with q[w] = smooth for w != ignore_index, q[label] = confidence, and q == 0 on a row
+ * whose label is ignore_index; then the same masking / drop-worst / normalisation as vlp_mlm_loss_fwd.
+ * smooth, confidence, q_sum = (V-2) * smooth + confidence and q_log_q = sum_w q[w] log q[w] of a row (the
+ * label-independent term of the KL) are the values of the caller's smoothed one-hot buffer in ITS dtype: an fp16
+ * model rounds smooth / confidence, and the reference rounds every q log q term to fp16 (xlogy on the fp16
+ * target), so q_log_q = (V-2) * half(s log s) + half(c log c) there.  Requires V > 2, 0 <= ignore_index < V.
+ * vlp_mlm_loss_ls_bwd writes dlogits[r, v] = grad_scale * coef[r] * (softmax(logits[r])[v] * q_sum - q[v])
+ * for v < V, 0 for V <= v < ld_dlogits, and 0 on every column of a row whose label is ignore_index.
+ * Labels are clamped to [0, V) like the plain CE entry points. */
+typedef struct {
+    const void* logits; int64_t ld_logits;    /* [B*P, V] fp16 */
+    const int64_t* labels;                    /* [B*P] */
+    const int64_t* weights;                   /* [B*P] masked_weights */
+    float* loss;                              /* [1] out */
+    float* lse; float* coef;                  /* [B*P] out */
+    float* row_loss;                          /* [B*P] scratch */
+    int32_t B, P, V;
+    float drop_worst_ratio;
+    float smooth, confidence, q_sum, q_log_q;
+    int32_t ignore_index;
+} vlp_mlm_loss_ls_fwd_args;
+int vlp_mlm_loss_ls_fwd(const vlp_mlm_loss_ls_fwd_args* a, void* stream);
+typedef struct {
+    const void* logits; int64_t ld_logits;
+    const int64_t* labels;
+    const float* lse; const float* coef;      /* written by vlp_mlm_loss_ls_fwd */
+    const float* grad_scale;                  /* [1] device scalar (upstream gradient x loss scale) */
+    void* dlogits; int64_t ld_dlogits;        /* [B*P, ld] fp16 out */
+    int32_t rows, V;
+    float smooth, confidence, q_sum;
+    int32_t ignore_index;
+} vlp_mlm_loss_ls_bwd_args;
+int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

@@ -134,6 +134,14 @@ class MlmLossBwdArgs(C.Structure):
                 ("dlogits", vp), ("ld_dlogits", i64), ("rows", i32), ("V", i32)]
 
 
+class MlmLossLsFwdArgs(C.Structure):
+    _fields_ = MlmLossFwdArgs._fields_ + [("smooth", f32), ("confidence", f32), ("q_sum", f32), ("q_log_q", f32), ("ignore_index", i32)]
+
+
+class MlmLossLsBwdArgs(C.Structure):
+    _fields_ = MlmLossBwdArgs._fields_ + [("smooth", f32), ("confidence", f32), ("q_sum", f32), ("ignore_index", i32)]
+
+
 class FusedAdamArgs(C.Structure):
     _fields_ = [("p32", vp), ("m", vp), ("v", vp), ("g16", vp), ("p16", vp), ("n", i64),
                 ("b1", f32), ("b2", f32), ("eps", f32), ("decay", f32), ("eps_inside_sqrt", i32), ("hyper", vp)]
@@ -202,6 +210,8 @@ SYMBOLS = {
     "vlp_gelu_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
+    "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
+    "vlp_mlm_loss_ls_bwd": (C.c_int, [C.POINTER(MlmLossLsBwdArgs), vp]),
     "vlp_bce_loss_fwd": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp]),
     "vlp_bce_loss_bwd": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, i64, vp]),
     "vlp_sumsq": (C.c_int, [vp, i64, vp, vp, vp]),
@@ -664,6 +674,23 @@ def mlm_loss_bwd(logits, ld, labels, lse, coef, grad_scale, dlogits, ldd, rows, 
     _req_cuda(logits, labels, lse, coef, grad_scale, dlogits)
     a = MlmLossBwdArgs(ptr(logits), ld, ptr(labels), ptr(lse), ptr(coef), ptr(grad_scale), ptr(dlogits), ldd, rows, V)
     _check(load().vlp_mlm_loss_bwd(C.byref(a), stream_ptr()))
+
+
+def mlm_loss_ls_fwd(logits, ld, labels, weights, loss, lse, coef, row_loss, B, P, V, smooth, confidence, q_sum, q_log_q, ignore_index=0,
+                    drop_worst_ratio=0.0):
+    """Label-smoothed masked-LM loss; smooth / confidence / q_sum / q_log_q are the smoothed one-hot's values in the model's dtype
+    (vlp_amd.loss.LabelSmoothingLoss.kernel_scalars)."""
+    _req_cuda(logits, labels, weights, loss, lse, coef, row_loss)
+    a = MlmLossLsFwdArgs(ptr(logits), ld, ptr(labels), ptr(weights), ptr(loss), ptr(lse), ptr(coef), ptr(row_loss), B, P, V, drop_worst_ratio,
+                         smooth, confidence, q_sum, q_log_q, ignore_index)
+    _check(load().vlp_mlm_loss_ls_fwd(C.byref(a), stream_ptr()))
+
+
+def mlm_loss_ls_bwd(logits, ld, labels, lse, coef, grad_scale, dlogits, ldd, rows, V, smooth, confidence, q_sum, ignore_index=0):
+    _req_cuda(logits, labels, lse, coef, grad_scale, dlogits)
+    a = MlmLossLsBwdArgs(ptr(logits), ld, ptr(labels), ptr(lse), ptr(coef), ptr(grad_scale), ptr(dlogits), ldd, rows, V,
+                         smooth, confidence, q_sum, ignore_index)
+    _check(load().vlp_mlm_loss_ls_bwd(C.byref(a), stream_ptr()))
 
 
 def bce_loss_fwd(logits, ld, labels, ldl, B, N, loss257):

@@ -1,6 +1,7 @@
 // Loss kernels of the VLP hot path for gfx950.
 //   masked-LM: CrossEntropyLoss(reduction='none') in fp32 over the tied-decoder logits, masked_weights,
 //              per-sample sum, drop-worst top-k, normalisation (modeling.py:1083-1111);
+//              with label smoothing the per-row KL of loss.py LabelSmoothingLoss instead of the CE (modeling.py:1104-1106);
 //   VQA:       BCEWithLogitsLoss(mean) * num_answers (modeling.py:1030, 1140).
 #include "common.h"
 
@@ -151,6 +152,141 @@ extern "C" int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream) {
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits, a->labels,
                        a->lse, a->coef, a->grad_scale, (f16*)a->dlogits, a->ld_dlogits, a->V);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_bwd");
+    return VLP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Label-smoothed masked-LM loss (loss.py LabelSmoothingLoss, modeling.py:995-999, 1104-1106):
+//   q[w] = smooth for w != ignore, q[label] = confidence, q == 0 on a row whose label is `ignore`;
+//   row_loss = sum_w q[w] (log q[w] - logp[w])        (0 log 0 = 0)
+// With m = max, S = sum exp(z - m), A = sum_{w != ignore} (z_w - m) and logp_w = z_w - m - log S:
+//   sum_w q log q    = (V-2) s log s + c log c   (q_log_q: a constant of the buffer, passed in as the caller rounds it)
+//   sum_w q logp     = s (A - (V-1) log S - logp_t) + c logp_t
+// so the same two passes as ce_row_kernel give the row's KL without a third one.
+// ---------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(CE_THREADS) void ce_ls_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                               float* __restrict__ lse, float* __restrict__ row_loss, int V, float smooth,
+                                                               float confidence, float q_log_q, int ignore) {
+    __shared__ float sh[8];
+    const int row = blockIdx.x;
+    const f16* x = logits + (int64_t)row * ld;
+    const int v8 = V >> 3;
+    float mx = -INFINITY;
+    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
+        f16x8 t = ld8(x + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)t[e]);
+    }
+    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) mx = fmaxf(mx, (float)x[i]);
+    mx = block_reduce_max(mx, sh);
+    float s = 0.f, a = 0.f;
+    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
+        f16x8 t = ld8(x + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float d = (float)t[e] - mx;
+            s += __expf(d);
+            a += d;
+        }
+    }
+    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) {
+        const float d = (float)x[i] - mx;
+        s += __expf(d);
+        a += d;
+    }
+    s = block_reduce_sum(s, sh);
+    a = block_reduce_sum(a, sh);
+    if (threadIdx.x == 0) {
+        const float ls = __logf(s);
+        int64_t lab = labels[row];
+        lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
+        lse[row] = mx + ls;
+        float r = 0.f;
+        if (lab != ignore) {
+            a -= (float)x[ignore] - mx;                                   // A runs over w != ignore
+            const float lpt = (float)x[lab] - mx - ls;                    // logp[label]
+            const float sum_lp = a - (float)(V - 1) * ls;                 // sum_{w != ignore} logp[w]
+            r = q_log_q - smooth * (sum_lp - lpt) - confidence * lpt;
+        }
+        row_loss[row] = r;
+    }
+}
+
+extern "C" int vlp_mlm_loss_ls_fwd(const vlp_mlm_loss_ls_fwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->labels && a->weights && a->loss && a->lse && a->coef && a->row_loss, "vlp_mlm_loss_ls_fwd: null operand");
+    VLP_ENTER(a->logits, "vlp_mlm_loss_ls_fwd");
+    VLP_CHECK_ARG(a->B > 0 && a->P > 0 && a->V > 2 && a->B <= 4096, "vlp_mlm_loss_ls_fwd: bad shape (B <= 4096, V > 2)");
+    VLP_CHECK_ARG(a->ld_logits % 8 == 0 && a->ld_logits >= a->V && (uintptr_t)a->logits % 16 == 0, "vlp_mlm_loss_ls_fwd: logits layout");
+    VLP_CHECK_ARG(a->drop_worst_ratio >= 0.f && a->drop_worst_ratio < 1.f, "vlp_mlm_loss_ls_fwd: drop_worst_ratio");
+    VLP_CHECK_ARG(a->smooth >= 0.f && a->confidence >= 0.f && a->q_sum > 0.f && a->ignore_index >= 0 && a->ignore_index < a->V,
+                  "vlp_mlm_loss_ls_fwd: smoothing parameters");
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = a->B * a->P;
+    hipLaunchKernelGGL(ce_ls_row_kernel, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)a->logits, a->ld_logits, a->labels, a->lse, a->row_loss,
+                       a->V, a->smooth, a->confidence, a->q_log_q, a->ignore_index);
+    VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(row)");
+    const int keep_n = (int)((double)a->B * (1.0 - (double)a->drop_worst_ratio));
+    hipLaunchKernelGGL(mlm_finish_kernel, dim3(1), dim3(1024), 3 * a->B * sizeof(float), s, a->row_loss, a->weights, a->loss, a->coef, a->B, a->P, keep_n);
+    VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(finish)");
+    return VLP_OK;
+}
+
+// d row_loss / d z[w] = p[w] * sum(q) - q[w]; zero on a row whose label is `ignore` and in the pad columns V..ldd
+__global__ __launch_bounds__(CE_THREADS) void ce_ls_bwd_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                               const float* __restrict__ lse, const float* __restrict__ coef,
+                                                               const float* __restrict__ gscale, f16* __restrict__ dl, int64_t ldd, int V,
+                                                               float smooth, float confidence, float q_sum, int ignore) {
+    const int row = blockIdx.y;
+    const f16* x = logits + (int64_t)row * ld;
+    f16* d = dl + (int64_t)row * ldd;
+    int64_t lab = labels[row];
+    lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
+    const int n8 = (int)(ldd >> 3);
+    if (lab == ignore) {
+        f16x8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[e] = (f16)0.f;
+        for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) st8(d + ch * 8, z);
+        return;
+    }
+    const float c = coef[row] * gscale[0];
+    const float l = lse[row];
+    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
+        const int v0 = ch * 8;
+        f16x8 o;
+        if (v0 + 8 <= V) {
+            f16x8 t = ld8(x + v0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int v = v0 + e;
+                const float q = v == lab ? confidence : (v == ignore ? 0.f : smooth);
+                o[e] = (f16)(c * (__expf((float)t[e] - l) * q_sum - q));
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int v = v0 + e;
+                const float q = v == lab ? confidence : (v == ignore ? 0.f : smooth);
+                o[e] = v < V ? (f16)(c * (__expf((float)x[v] - l) * q_sum - q)) : (f16)0.f;
+            }
+        }
+        st8(d + v0, o);
+    }
+}
+extern "C" int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->labels && a->lse && a->coef && a->grad_scale && a->dlogits, "vlp_mlm_loss_ls_bwd: null operand");
+    VLP_ENTER(a->logits, "vlp_mlm_loss_ls_bwd");
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 2 && a->ld_logits % 8 == 0 && a->ld_dlogits % 8 == 0 && a->ld_dlogits >= a->V && a->ld_logits >= a->V,
+                  "vlp_mlm_loss_ls_bwd: layout");
+    VLP_CHECK_ARG(((uintptr_t)a->logits | (uintptr_t)a->dlogits) % 16 == 0, "vlp_mlm_loss_ls_bwd: alignment");
+    VLP_CHECK_ARG(a->smooth >= 0.f && a->confidence >= 0.f && a->q_sum > 0.f && a->ignore_index >= 0 && a->ignore_index < a->V,
+                  "vlp_mlm_loss_ls_bwd: smoothing parameters");
+    int bx = cdiv(a->ld_dlogits / 8, CE_THREADS);
+    if (bx > 16) bx = 16;
+    hipLaunchKernelGGL(ce_ls_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits, a->labels,
+                       a->lse, a->coef, a->grad_scale, (f16*)a->dlogits, a->ld_dlogits, a->V, a->smooth, a->confidence, a->q_sum, a->ignore_index);
+    VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_bwd");
     return VLP_OK;
 }
 

@@ -47,7 +47,7 @@ class VlpPerformanceWarning(UserWarning):
 
 class _State(object):
     """What one forward leaves behind for its backward."""
-    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "task", "has_mlm", "task_labels", "pretext", "pk")
+    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "task", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth")
 
 
 class Engine(object):
@@ -675,6 +675,7 @@ class Engine(object):
         self.gen += 1
         st = _State()
         st.gen, st.B, st.L, st.P, st.ws = self.gen, B, L, P, ws
+        st.mlm_smooth = None
         p = cfg.hidden_dropout_prob if train else 0.0
         pa = cfg.attention_probs_dropout_prob if train else 0.0
         st.p_drop = (p, pa)
@@ -847,10 +848,21 @@ class Engine(object):
     def mlm_loss(self, st, labels, weights, drop_worst_ratio):
         """modeling.py:1083-1111 on the logits of this forward; returns a [1] f32 view holding the loss."""
         ws = st.ws
-        V = self._model().config.vocab_size
+        model = self._model()
+        V = model.config.vocab_size
         st.task_labels = labels.contiguous()
-        K.mlm_loss_fwd(ws["logits"], ws["Vp"], st.task_labels, weights.to(torch.long).contiguous(), ws["loss"], ws["lse_ce"], ws["coef"],
-                       ws["row_loss"], st.B, st.P, V, drop_worst_ratio=float(drop_worst_ratio))
+        crit = getattr(model, "crit_mask_lm_smoothed", None)
+        if crit is None:
+            st.mlm_smooth = None
+            K.mlm_loss_fwd(ws["logits"], ws["Vp"], st.task_labels, weights.to(torch.long).contiguous(), ws["loss"], ws["lse_ce"], ws["coef"],
+                           ws["row_loss"], st.B, st.P, V, drop_worst_ratio=float(drop_worst_ratio))
+        else:
+            # label smoothing (modeling.py:1104-1106): the KL kernels; the choice is recorded on st so that backward follows this forward
+            s, c, q_sum, q_log_q = crit.kernel_scalars()
+            K.mlm_loss_ls_fwd(ws["logits"], ws["Vp"], st.task_labels, weights.to(torch.long).contiguous(), ws["loss"], ws["lse_ce"], ws["coef"],
+                              ws["row_loss"], st.B, st.P, V, s, c, q_sum, q_log_q, ignore_index=crit.ignore_index,
+                              drop_worst_ratio=float(drop_worst_ratio))
+            st.mlm_smooth = (s, c, q_sum, crit.ignore_index)          # the arguments of the matching backward launch
         return ws["loss"][0:1]
 
     def vqa_loss(self, st, ans_labels):
@@ -1356,7 +1368,10 @@ class Engine(object):
         else:
             C = "cls.predictions."
             R, Vp = B * P, ws["Vp"]
-            K.mlm_loss_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
+            if st.mlm_smooth is None:
+                K.mlm_loss_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
+            else:
+                K.mlm_loss_ls_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V, *st.mlm_smooth)
             # tied decoder (modeling.py:445-448): dE[V,H] = dlogits^T . t ; the embedding scatter adds to it later
             head_wgrads.append(lambda: self._tn(ws["dlogits"], ws["tln"], self.G(E + "word_embeddings.weight"), R, V, H, ws, beta, bias=self.G(C + "bias")))
             # dgrad through the tied decoder: dt[R,H] = dlogits[R,V] . E[V,H].  As an NT GEMM this is 12 workgroups walking

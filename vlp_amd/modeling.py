@@ -7,8 +7,8 @@ arithmetic of `BertForPreTrainingLossMask.forward` runs as hand-written HIP kern
 libvlp_hip.so, sequenced by vlp_amd.engine.Engine (one fused forward/backward, no per-op autograd graph).
 
 Not implemented (raise loudly; see DESIGN.md "out of scope"): fp32 execution, `enable_butd=False`
-(the reference asserts it is True, run_img2txt_dist.py:199), `relax_projection`, label smoothing, and the dead HF heads
-(:878-978, :1497-1966).  `mask_image_regions` / `vis_pretext_loss` (:1049-1056, 1113-1131) and the pooler they use are built.
+(the reference asserts it is True, run_img2txt_dist.py:199), `relax_projection`, and the dead HF heads
+(:878-978, :1497-1966).  Label smoothing (`config.label_smoothing`, loss.py) runs on its own HIP loss kernels.  `mask_image_regions` / `vis_pretext_loss` (:1049-1056, 1113-1131) and the pooler they use are built.
 """
 import copy
 import json
@@ -22,6 +22,7 @@ from torch import nn
 
 from . import _lib as K
 from .engine import Engine
+from .loss import LabelSmoothingLoss
 
 logger = logging.getLogger(__name__)
 
@@ -469,9 +470,10 @@ class BertForPreTrainingLossMask(PreTrainedBertModel):
         self.num_labels = num_labels
         self.len_vis_input = len_vis_input
         self.enable_butd = enable_butd
-        if getattr(config, "label_smoothing", None):
-            raise NotImplementedError("label smoothing (loss.py) is off in every reference config and not implemented in vlp_amd")
-        self.crit_mask_lm_smoothed = None
+        if getattr(config, "label_smoothing", None):                   # :995-999; a buffer, never a parameter of the engine's flat layout
+            self.crit_mask_lm_smoothed = LabelSmoothingLoss(config.label_smoothing, config.vocab_size, ignore_index=0, reduction="none")
+        else:
+            self.crit_mask_lm_smoothed = None
         _region_embedders(self, config, enable_butd, allow_random_fc7)
         _load_fc7(self, allow_random_fc7)
         self.tasks = tasks
