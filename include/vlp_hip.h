@@ -30,6 +30,8 @@ extern "C" {
 #define VLP_ABI_VERSION 5      /* 5 (round 6): + vlp_dec_gemm, vlp_dec_reduce_ln, vlp_argmax_rows2 (no existing struct changed) */
 /* + vlp_mlm_loss_ls_fwd / vlp_mlm_loss_ls_bwd with their own argument structs: purely additive (no existing struct or entry point
  * changed), so a binding written against version 5 keeps working and the version number stays 5. */
+/* + vlp_scst_layout, vlp_embed_bwd_pos, vlp_token_logprob_fwd / vlp_token_logprob_bwd (self-critical sequence training), each with its own
+ * argument struct: purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -341,6 +343,16 @@ typedef struct {
                                                                halves read dpre and write disjoint outputs: a caller may run them on two streams. */
 } vlp_embed_bwd_args;
 int vlp_embed_bwd(const vlp_embed_bwd_args* a, void* stream);
+/* vlp_embed_bwd with explicit position ids (the SCST scoring pass, whose slots carry the logical positions of the incremental decoder's rows,
+ * modeling.py:856-865, 1210-1222): the dpre row (b, l) of a token position adds into d_pos_emb[position_ids[b, l]] (clamped to [0, max_pos)
+ * like vlp_embed_fwd); everything else is vlp_embed_bwd on `base`.  Deterministic like it: every table row sums its rows in (b, l) order in
+ * fp32, no atomics; position_ids = 0..L-1 gives vlp_embed_bwd's bits.  max_pos = rows of d_pos_emb. */
+typedef struct {
+    vlp_embed_bwd_args base;
+    const int64_t* position_ids;                            /* [B, L] */
+    int32_t max_pos;
+} vlp_embed_bwd_pos_args;
+int vlp_embed_bwd_pos(const vlp_embed_bwd_pos_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * small data-movement helpers
@@ -456,6 +468,24 @@ int vlp_vis_pe_prep(const vlp_vis_pe_prep_args* a, void* stream);
  * distribution is the same; logp[r*logp_stride] = log_softmax(logits[r])[ids[r]]. */
 int vlp_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, uint64_t seed, uint32_t rng_stream, int64_t* ids,
                     int64_t ids_stride, float* logp, int64_t logp_stride, void* stream);
+/* SCST scoring layout: the teacher-forced sequence whose training forward reproduces, for every sampled position, the hidden states of the
+ * incremental decoder (replaces differentiating the decoder itself, modeling.py:1210-1251 under autograd in run_img2txt_dist.py:506-507).
+ * With T sampled tokens y_0..y_{T-1} the scoring sequence has L' = in_len + 2T - 1 <= 256 slots:
+ *   [prefix 0..in_len-1 | y_0..y_{T-2} at logical positions in_len..in_len+T-2 | [MASK]_0..[MASK]_{T-1} at logical positions in_len..in_len+T-1];
+ * ids / token types / position ids are read at each slot's logical position ([MASK] slots get mask_word_id), masked_pos[b, t] = slot of
+ * [MASK]_t.  With am = mask[b] ([L, L]): a prefix / real slot at logical p keeps am[p, p'] for prefix / real slots p' <= max(p, in_len - 1)
+ * and am[p, q] for the [MASK] slot at logical q = max(p + 1, in_len); [MASK] at logical q keeps am[q, p'] for prefix / real slots p' <= q - 1
+ * and am[q, q] for itself; every other entry is 0.  Outputs int64: out_ids / out_segment_ids / out_position_ids [B, L'], out_mask
+ * [B, L', L'] (pack it with vlp_mask_pack), masked_pos [B, T].  Inputs: prefix_ids [B, in_len], sample_ids [B, T], segment_ids /
+ * position_ids [B, L], mask [B, L, L] (all contiguous int64), in_len + T <= L. */
+typedef struct {
+    const int64_t* prefix_ids; const int64_t* sample_ids;
+    const int64_t* segment_ids; const int64_t* position_ids; const int64_t* mask;
+    int64_t* out_ids; int64_t* out_segment_ids; int64_t* out_position_ids; int64_t* out_mask; int64_t* masked_pos;
+    int32_t B, L, in_len, T;
+    int64_t mask_word_id;
+} vlp_scst_layout_args;
+int vlp_scst_layout(const vlp_scst_layout_args* a, void* stream);
 /* Beam search (modeling.py:1255-1494):
  *   vlp_logsoftmax_topk: per row log_softmax over V (fp32 from fp16 logits), -10000 added on forbidden words (uint8 [rows, V], may be
  *       NULL; :1298-1299), the eos column forced to -10000 while the minimum length is not reached (:1300-1301), then the K best
@@ -561,6 +591,27 @@ typedef struct {
     int32_t ignore_index;
 } vlp_mlm_loss_ls_bwd_args;
 int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stream);
+
+/* Log-probability of one chosen token per row (SCST, the sampled caption's log-probs: modeling.py:1232-1235, without the fp16 rounding of
+ * the reference's log_softmax): fwd logp[r] = logits[r, ids[r]] - lse[r] with lse[r] = logsumexp(logits[r, :V]), both fp32 from the fp16
+ * logits (the arithmetic of vlp_mlm_loss_fwd); bwd dlogits[r, v] = g[r] * ([v == ids[r]] - exp(logits[r, v] - lse[r])) for v < V and 0 for
+ * V <= v < ld_dlogits.  g: device [rows] fp32 upstream gradient (carries the loss scale; either sign).  ids are clamped to [0, V). */
+typedef struct {
+    const void* logits; int64_t ld_logits;    /* [rows, V] fp16 */
+    const int64_t* ids;                       /* [rows] */
+    float* logp; float* lse;                  /* [rows] out */
+    int32_t rows, V;
+} vlp_token_logprob_fwd_args;
+int vlp_token_logprob_fwd(const vlp_token_logprob_fwd_args* a, void* stream);
+typedef struct {
+    const void* logits; int64_t ld_logits;
+    const int64_t* ids;
+    const float* lse;                         /* written by vlp_token_logprob_fwd */
+    const float* g;                           /* [rows] device upstream gradient */
+    void* dlogits; int64_t ld_dlogits;        /* [rows, ld] fp16 out */
+    int32_t rows, V;
+} vlp_token_logprob_bwd_args;
+int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

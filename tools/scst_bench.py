@@ -1,0 +1,100 @@
+"""Per-phase timing of one self-critical (--scst) training step on one MI355X -> profiles/scst_step.json.
+
+    python tools/scst_bench.py [--batches 16 64] [--steps 5] [--warmup 2] [--out profiles/scst_step.json]
+
+Every step is the entry script's own vlp_amd.run_img2txt_dist.scst_step (the model's sample_mode paths, the reward, RewardCriterion, the fp16
+optimizer) at L = 123 (COCO's --max_len_b 20), 12 layers, the bert-base-cased vocabulary, on a seeded synthetic batch.  scst_step reports the
+end of each phase through its `mark` hook; the tool additionally marks the entry of Engine.score_samples, which splits the model's sampled
+forward into its two halves:
+  greedy_decode    eval() + no_grad greedy decode (the baseline captions; graph-planned token steps)
+  sample_decode    the sampled decode of the train() forward (not graph-planned: its seed changes every step)
+  score_fwd        Engine.score_samples: scoring layout + training forward + LM head + log-probs
+  reward_host      caption cleaning, one device -> host copy, CIDEr-D of 2B captions on the host, the rewards back
+  score_bwd        RewardCriterion and the backward of the scoring forward
+  optimizer        FP16_Optimizer_State(FusedAdam).step()
+Each mark synchronises the device first (host wall clock), so phases do not overlap; their sum is a serialised step.  Nothing is asserted:
+this records what is measured."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from vlp_amd import run_img2txt_dist as R          # noqa: E402
+from vlp_amd import synthetic as S                 # noqa: E402
+from vlp_amd.modeling import BertConfig, BertForSeq2SeqDecoder   # noqa: E402
+from vlp_amd.optimization_fp16 import FP16_Optimizer_State, FusedAdam   # noqa: E402
+from vlp_amd.scst import RewardCriterion           # noqa: E402
+
+PHASES = ("greedy_decode", "sample_decode", "score_fwd", "reward_host", "score_bwd", "optimizer")
+RENAME = {"sample_forward": "score_fwd", "backward": "score_bwd"}      # scst_step's phase names -> the finer ones above
+NOTE = ("every phase ends with a device synchronisation (host wall clock), so phases do not overlap; sample_decode is not graph-planned "
+        "(its seed changes every step)")
+
+
+def bench(B, steps, warmup, dev):
+    cfg = BertConfig(28996, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, type_vocab_size=6)
+    torch.manual_seed(0)
+    m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=100).half().to(dev)
+    named = list(m.named_parameters())
+    nd = ["bias", "LayerNorm.bias", "LayerNorm.weight"]
+    groups = [{"params": [q for n, q in named if not any(x in n for x in nd)], "weight_decay": 0.01},
+              {"params": [q for n, q in named if any(x in n for x in nd)], "weight_decay": 0.0}]
+    opt = FP16_Optimizer_State(FusedAdam(groups, lr=1e-6, bias_correction=False, max_grad_norm=1.0), dynamic_loss_scale=True)
+    batch = S.batch_to(S.make_batch(B, max_len_b=20, len_vis_input=100, max_pred=0, mask_prob=0.0, seed=7), dev, half=True)
+    crit = RewardCriterion()
+    times = {k: [] for k in PHASES}
+    clock = {"t": 0.0, "rec": False}
+
+    def mark(phase):
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        if clock["rec"] and phase is not None:
+            times[RENAME.get(phase, phase)].append((now - clock["t"]) * 1e3)
+        clock["t"] = now
+
+    eng = m.engine
+    score = eng.score_samples
+
+    def score_marked(*a, **kw):             # the model's sampled forward calls this after its decode
+        mark("sample_decode")
+        return score(*a, **kw)
+    eng.score_samples = score_marked
+    for it in range(warmup + steps):
+        clock["rec"] = it >= warmup
+        mark(None)                          # the step starts here
+        R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark)
+    L = batch.input_ids.shape[1]
+    out = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v))} for k, v in times.items()}
+    out["step_ms_sum_of_medians"] = float(sum(out[k]["median_ms"] for k in PHASES))
+    out.update(B=B, L=L, T=L - 102, scoring_length=102 + 2 * (L - 102) - 1, layers=12, vocab=28996, steps=steps, warmup=warmup)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[16, 64])
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scst_step.json"))
+    a = ap.parse_args()
+    dev = torch.device("cuda")
+    res = {"device": torch.cuda.get_device_name(0), "note": NOTE, "runs": [],
+           "tool": "tools/scst_bench.py --batches %s --steps %d --warmup %d" % (" ".join(map(str, a.batches)), a.steps, a.warmup)}
+    for B in a.batches:
+        r = bench(B, a.steps, a.warmup, dev)
+        print(json.dumps(r, sort_keys=True), flush=True)
+        res["runs"].append(r)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=2, sort_keys=True)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -109,6 +109,25 @@ class EmbedBwdArgs(C.Structure):
                 ("drop_p", f32), ("seed", u64), ("vis_stream", u32), ("vispe_stream", u32), ("region_mask", vp), ("parts", i32)]
 
 
+class EmbedBwdPosArgs(C.Structure):
+    _fields_ = [("base", EmbedBwdArgs), ("position_ids", vp), ("max_pos", i32)]
+
+
+class ScstLayoutArgs(C.Structure):
+    _fields_ = [("prefix_ids", vp), ("sample_ids", vp), ("segment_ids", vp), ("position_ids", vp), ("mask", vp),
+                ("out_ids", vp), ("out_segment_ids", vp), ("out_position_ids", vp), ("out_mask", vp), ("masked_pos", vp),
+                ("B", i32), ("L", i32), ("in_len", i32), ("T", i32), ("mask_word_id", i64)]
+
+
+class TokenLogprobFwdArgs(C.Structure):
+    _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("logp", vp), ("lse", vp), ("rows", i32), ("V", i32)]
+
+
+class TokenLogprobBwdArgs(C.Structure):
+    _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("lse", vp), ("g", vp), ("dlogits", vp), ("ld_dlogits", i64),
+                ("rows", i32), ("V", i32)]
+
+
 class PretextFwdArgs(C.Structure):
     _fields_ = [("vis_h", vp), ("vispe_h", vp), ("pooled", vp), ("vis_masked_pos", vp), ("probs", vp), ("sample_loss", vp), ("loss", vp),
                 ("B", i32), ("Nv", i32), ("Pm", i32), ("H", i32)]
@@ -193,6 +212,10 @@ SYMBOLS = {
     "vlp_layernorm_bwd_reduce_batched": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "vlp_embed_fwd": (C.c_int, [C.POINTER(EmbedFwdArgs), vp]),
     "vlp_embed_bwd": (C.c_int, [C.POINTER(EmbedBwdArgs), vp]),
+    "vlp_embed_bwd_pos": (C.c_int, [C.POINTER(EmbedBwdPosArgs), vp]),
+    "vlp_scst_layout": (C.c_int, [C.POINTER(ScstLayoutArgs), vp]),
+    "vlp_token_logprob_fwd": (C.c_int, [C.POINTER(TokenLogprobFwdArgs), vp]),
+    "vlp_token_logprob_bwd": (C.c_int, [C.POINTER(TokenLogprobBwdArgs), vp]),
     "vlp_region_mask_build": (C.c_int, [vp, i32, i32, i32, vp, vp]),
     "vlp_pretext_fwd": (C.c_int, [C.POINTER(PretextFwdArgs), vp]),
     "vlp_pretext_bwd": (C.c_int, [C.POINTER(PretextBwdArgs), vp]),
@@ -562,6 +585,48 @@ def embed_bwd(dpre, input_ids, segment_ids, vis_h, vispe_h, d_word, d_pos, d_typ
                      ptr(d_vis_h), ptr(d_vispe_h), ptr(acc32), B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream,
                      ptr(region_mask), parts)
     _check(load().vlp_embed_bwd(C.byref(a), stream_ptr()))
+
+
+def embed_bwd_pos(dpre, input_ids, segment_ids, position_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
+                  B, L, Nv, H, vocab, type_vocab, drop_p=0.0, seed=0, vis_stream=0, vispe_stream=0, region_mask=None, parts=0):
+    """embed_bwd with position_ids (int64 [B, L], device): row (b, l) adds into d_pos[position_ids[b, l]]."""
+    _req_cuda(dpre, input_ids, segment_ids, position_ids, d_word, d_pos, d_type, acc32, region_mask)
+    base = EmbedBwdArgs(ptr(dpre), ptr(input_ids), ptr(segment_ids), ptr(vis_h), ptr(vispe_h), ptr(d_word), ptr(d_pos), ptr(d_type),
+                        ptr(d_vis_h), ptr(d_vispe_h), ptr(acc32), B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream,
+                        ptr(region_mask), parts)
+    a = EmbedBwdPosArgs(base, ptr(position_ids), d_pos.shape[0])
+    _check(load().vlp_embed_bwd_pos(C.byref(a), stream_ptr()))
+
+
+def scst_layout(prefix_ids, sample_ids, segment_ids, position_ids, mask, out_ids, out_segment_ids, out_position_ids, out_mask, masked_pos,
+                mask_word_id):
+    """The SCST scoring sequence (include/vlp_hip.h vlp_scst_layout); every tensor contiguous int64 on the device."""
+    _req_cuda(prefix_ids, sample_ids, segment_ids, position_ids, mask, out_ids, out_segment_ids, out_position_ids, out_mask, masked_pos)
+    B, in_len = prefix_ids.shape
+    T, L = sample_ids.shape[1], segment_ids.shape[1]
+    for t in (prefix_ids, sample_ids, segment_ids, position_ids, mask, out_ids, out_segment_ids, out_position_ids, out_mask, masked_pos):
+        if t.dtype != torch.long or not t.is_contiguous():
+            raise RuntimeError("vlp_amd.scst_layout: operands must be contiguous int64")
+    Lo = in_len + 2 * T - 1
+    if (tuple(sample_ids.shape) != (B, T) or tuple(position_ids.shape) != (B, L) or tuple(mask.shape) != (B, L, L) or
+            tuple(out_ids.shape) != (B, Lo) or tuple(out_segment_ids.shape) != (B, Lo) or tuple(out_position_ids.shape) != (B, Lo) or
+            tuple(out_mask.shape) != (B, Lo, Lo) or tuple(masked_pos.shape) != (B, T)):
+        raise RuntimeError("vlp_amd.scst_layout: shape mismatch")
+    a = ScstLayoutArgs(ptr(prefix_ids), ptr(sample_ids), ptr(segment_ids), ptr(position_ids), ptr(mask), ptr(out_ids), ptr(out_segment_ids),
+                       ptr(out_position_ids), ptr(out_mask), ptr(masked_pos), B, L, in_len, T, int(mask_word_id))
+    _check(load().vlp_scst_layout(C.byref(a), stream_ptr()))
+
+
+def token_logprob_fwd(logits, ld, ids, logp, lse, rows, V):
+    _req_cuda(logits, ids, logp, lse)
+    a = TokenLogprobFwdArgs(ptr(logits), ld, ptr(ids), ptr(logp), ptr(lse), rows, V)
+    _check(load().vlp_token_logprob_fwd(C.byref(a), stream_ptr()))
+
+
+def token_logprob_bwd(logits, ld, ids, lse, g, dlogits, ldd, rows, V):
+    _req_cuda(logits, ids, lse, g, dlogits)
+    a = TokenLogprobBwdArgs(ptr(logits), ld, ptr(ids), ptr(lse), ptr(g), ptr(dlogits), ldd, rows, V)
+    _check(load().vlp_token_logprob_bwd(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

@@ -10,7 +10,9 @@ modules, so that the import lines of vlp/run_img2txt_dist.py:23-30,405 and vlp/d
     from pytorch_pretrained_bert.optimization_fp16 import FP16_Optimizer_State
 
 `misc.data_parallel` (DataParallelImbalance, run_img2txt_dist.py:30) resolves to vlp_amd.data_parallel, and, when apex is not
-installed, an `apex.optimizers` module exposing `FusedAdam` is provided (run_img2txt_dist.py:406 imports it from there).
+installed, an `apex.optimizers` module exposing `FusedAdam` is provided (run_img2txt_dist.py:406 imports it from there).  Likewise, when
+pycocoevalcap is not installed, `pycocoevalcap.cider.cider.Cider` resolves to vlp_amd.scst.CiderD, so that vlp/scst_utils.py
+(`Cider(df='corpus')`, :10-12) imports and scores unmodified.
 The tokenizer (`pytorch_pretrained_bert.tokenization`) is NOT provided: it is CPU-side text processing outside the hot path; keep
 using the reference's file for it.  install() refuses to shadow an already imported package of that name unless force=True.
 """
@@ -20,7 +22,7 @@ import types
 _ALIASES = ("modeling", "optimization", "optimization_fp16")
 
 
-def install(force=False, with_apex_shim=True):
+def install(force=False, with_apex_shim=True, with_cider_shim=True):
     from . import modeling, optimization, optimization_fp16
     name = "pytorch_pretrained_bert"
     if name in sys.modules and not getattr(sys.modules[name], "__vlp_amd_alias__", False) and not force:
@@ -58,12 +60,32 @@ def install(force=False, with_apex_shim=True):
             opt.__vlp_amd_alias__ = True
             apex.optimizers = opt
             sys.modules["apex"], sys.modules["apex.optimizers"] = apex, opt
+    if with_cider_shim:
+        try:
+            import pycocoevalcap.cider.cider  # noqa: F401
+        except ImportError:
+            from . import scst
+            mods = {}
+            for k in _CIDER_CHAIN:
+                m = sys.modules.get(k)
+                if m is None or not getattr(m, "__vlp_amd_alias__", False):
+                    m = types.ModuleType(k)
+                    m.__vlp_amd_alias__ = True
+                    m.__path__ = []
+                mods[k] = m
+            mods["pycocoevalcap"].cider = mods["pycocoevalcap.cider"]
+            mods["pycocoevalcap.cider"].cider = mods["pycocoevalcap.cider.cider"]
+            mods["pycocoevalcap.cider.cider"].Cider = scst.CiderD
+            sys.modules.update(mods)
     return pkg
+
+
+_CIDER_CHAIN = ("pycocoevalcap", "pycocoevalcap.cider", "pycocoevalcap.cider.cider")
 
 
 def uninstall():
     for k in [k for k, v in list(sys.modules.items()) if (k == "pytorch_pretrained_bert" or k.startswith("pytorch_pretrained_bert.") or
-                                                           k in ("apex", "apex.optimizers", "misc", "misc.data_parallel"))
+                                                           k in ("apex", "apex.optimizers", "misc", "misc.data_parallel") + _CIDER_CHAIN)
               and (getattr(v, "__vlp_amd_alias__", False) or k.startswith("pytorch_pretrained_bert.") or k == "misc.data_parallel")]:
         if k.startswith("pytorch_pretrained_bert.") and not getattr(sys.modules.get("pytorch_pretrained_bert"), "__vlp_amd_alias__", False):
             continue

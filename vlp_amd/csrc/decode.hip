@@ -401,3 +401,66 @@ extern "C" int vlp_argmax_rows2(const void* logits, int64_t ld, int32_t rows, in
     VLP_CHECK_LAUNCH("vlp_argmax_rows2");
     return VLP_OK;
 }
+
+// =================================================================================================
+// SCST scoring layout (replaces running the incremental decoder under autograd, modeling.py:1210-1251): for in_len prefix slots and T sampled
+// tokens y_0..y_{T-1}, the sequence [prefix | y_0..y_{T-2} at logical in_len.. | [MASK]_0..[MASK]_{T-1} at logical in_len..] whose mask gives
+// every slot exactly the keys its row saw in the incremental decoder (include/vlp_hip.h, vlp_scst_layout).  One thread per output mask element;
+// the k == 0 thread of a row also writes the row's ids / token types / position ids (and masked_pos for a [MASK] row).
+// =================================================================================================
+__global__ __launch_bounds__(256) void scst_layout_kernel(vlp_scst_layout_args a, int Lo) {
+    const int64_t total = (int64_t)a.B * Lo * Lo;
+    const int in_len = a.in_len, T = a.T, nr = in_len + T - 1;       // nr = prefix + real slots; [MASK]_t sits at slot nr + t
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(idx % Lo);
+        const int64_t bi = idx / Lo;
+        const int i = (int)(bi % Lo), b = (int)(bi / Lo);
+        const bool mi = i >= nr, mk = k >= nr;
+        const int pi = mi ? in_len + (i - nr) : i;                  // logical positions
+        const int pk = mk ? in_len + (k - nr) : k;
+        const int64_t* am = a.mask + (int64_t)b * a.L * a.L;
+        int64_t v = 0;
+        if (!mi) {
+            if (!mk) {
+                if (pk <= max(pi, in_len - 1)) v = am[(int64_t)pi * a.L + pk];
+            } else if (pk == max(pi + 1, in_len)) {
+                v = am[(int64_t)pi * a.L + pk];
+            }
+        } else {
+            if (!mk) {
+                if (pk <= pi - 1) v = am[(int64_t)pi * a.L + pk];
+            } else if (k == i) {
+                v = am[(int64_t)pi * a.L + pi];
+            }
+        }
+        a.out_mask[idx] = v;
+        if (k == 0) {
+            const int64_t o = (int64_t)b * Lo + i;
+            int64_t id;
+            if (mi) {
+                id = a.mask_word_id;
+                a.masked_pos[(int64_t)b * T + (i - nr)] = i;
+            } else {
+                id = pi < in_len ? a.prefix_ids[(int64_t)b * in_len + pi] : a.sample_ids[(int64_t)b * T + (pi - in_len)];
+            }
+            a.out_ids[o] = id;
+            a.out_segment_ids[o] = a.segment_ids[(int64_t)b * a.L + pi];
+            a.out_position_ids[o] = a.position_ids[(int64_t)b * a.L + pi];
+        }
+    }
+}
+
+extern "C" int vlp_scst_layout(const vlp_scst_layout_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->prefix_ids && a->sample_ids && a->segment_ids && a->position_ids && a->mask && a->out_ids && a->out_segment_ids &&
+                  a->out_position_ids && a->out_mask && a->masked_pos, "vlp_scst_layout: null operand");
+    VLP_ENTER(a->out_mask, "vlp_scst_layout");
+    VLP_CHECK_ARG(a->B > 0 && a->in_len > 0 && a->T > 0 && a->in_len + a->T <= a->L, "vlp_scst_layout: bad shape (0 < in_len, 0 < T, in_len + T <= L)");
+    const int Lo = a->in_len + 2 * a->T - 1;
+    VLP_CHECK_ARG(Lo <= 256, "vlp_scst_layout: scoring length in_len + 2T - 1 = %d exceeds 256 (the attention kernels' limit)", Lo);
+    const int64_t total = (int64_t)a->B * Lo * Lo;
+    int blocks = cdiv(total, 256);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(scst_layout_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *a, Lo);
+    VLP_CHECK_LAUNCH("vlp_scst_layout");
+    return VLP_OK;
+}

@@ -282,7 +282,45 @@ extern "C" int64_t vlp_embed_bwd_workspace_floats(int32_t B, int32_t L, int32_t 
     const int64_t nt = (int64_t)B * (L - Nv);
     return (int64_t)EMB_TSPLITS * EMB_MAXT * H + nt * H + nt;
 }
-extern "C" int vlp_embed_bwd(const vlp_embed_bwd_args* a, void* stream) {
+// d_pos_emb[r] += the dpre rows (b, l) of token positions whose position_ids[b, l] == r (clamped to [0, max_pos) like the forward):
+// one workgroup per table row compacts its rows in (b, l) order and sums them in fp32 in that order -- no atomics.  With
+// position_ids = 0..L-1 the rows of table row l are (0, l), (1, l), ... : the additions of embed_bwd_pos_kernel, in its order.
+__global__ __launch_bounds__(256) void embed_bwd_pos_ids_kernel(const f16* dpre, const int64_t* pid, f16* dpos, int B, int L, int Nv, int H, int max_pos) {
+    __shared__ int list[256];
+    __shared__ int wcnt[4];
+    const int r = blockIdx.x, tid = threadIdx.x, nch = H >> 3;
+    const int NT = B * L;
+    auto pred = [&](int u) {
+        const int l = u % L;
+        if (l >= 1 && l <= Nv) return false;
+        int64_t pi = pid[u];
+        pi = pi < 0 ? 0 : (pi >= max_pos ? max_pos - 1 : pi);
+        return pi == (int64_t)r;
+    };
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    int total = 0;
+    for (int u0 = 0; u0 < NT; u0 += 256) {
+        const int n = ewb_compact(list, wcnt, 0, u0, NT, pred);
+        total += n;
+        if (tid < nch) {
+            for (int i = 0; i < n; ++i) {
+                const f16x8 d = ld8(dpre + (int64_t)list[i] * H + tid * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += (float)d[e];
+            }
+        }
+    }
+    if (total == 0 || tid >= nch) return;
+    f16* dst = dpos + (int64_t)r * H + tid * 8;
+    f16x8 o = ld8(dst);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (f16)((float)o[e] + acc[e]);
+    st8(dst, o);
+}
+// position_ids == NULL: vlp_embed_bwd (table row l gets the rows of position l)
+static int embed_bwd_run(const vlp_embed_bwd_args* a, const int64_t* position_ids, int max_pos, void* stream) {
     VLP_CHECK_ARG(a && a->dpre && a->input_ids && a->segment_ids && a->d_word_emb && a->d_pos_emb && a->d_type_emb && a->acc32, "vlp_embed_bwd: null operand");
     VLP_ENTER(a->dpre, "vlp_embed_bwd");
     VLP_CHECK_ARG(a->H % 8 == 0 && a->H <= 2048 && a->B > 0 && a->L > a->Nv && a->type_vocab >= 1 && a->type_vocab <= EMB_MAXT,
@@ -309,9 +347,15 @@ extern "C" int vlp_embed_bwd(const vlp_embed_bwd_args* a, void* stream) {
         hipLaunchKernelGGL(embed_word_reduce_kernel, dim3(g.NT), dim3(256), 0, s, g, a->H, (const int*)rank, (const float*)partial, (f16*)a->d_word_emb);
         VLP_CHECK_LAUNCH("vlp_embed_word_reduce");
     }
-    hipLaunchKernelGGL(embed_bwd_pos_kernel, dim3(cdiv((int64_t)a->L * (a->H / 8), 256)), dim3(256), 0, s, (const f16*)a->dpre,
-                       (f16*)a->d_pos_emb, a->B, a->L, a->Nv, a->H);
-    VLP_CHECK_LAUNCH("vlp_embed_bwd_pos");
+    if (position_ids) {
+        hipLaunchKernelGGL(embed_bwd_pos_ids_kernel, dim3(max_pos), dim3(256), 0, s, (const f16*)a->dpre, position_ids, (f16*)a->d_pos_emb,
+                           a->B, a->L, a->Nv, a->H, max_pos);
+        VLP_CHECK_LAUNCH("vlp_embed_bwd_pos(ids)");
+    } else {
+        hipLaunchKernelGGL(embed_bwd_pos_kernel, dim3(cdiv((int64_t)a->L * (a->H / 8), 256)), dim3(256), 0, s, (const f16*)a->dpre,
+                           (f16*)a->d_pos_emb, a->B, a->L, a->Nv, a->H);
+        VLP_CHECK_LAUNCH("vlp_embed_bwd_pos");
+    }
     const int64_t rows = (int64_t)a->B * a->L;
     int splits = rows >= EMB_TSPLITS * 8 ? EMB_TSPLITS : (int)((rows + 7) / 8);
     hipLaunchKernelGGL(embed_bwd_type_kernel, dim3(cdiv(a->H, 256), splits), dim3(256), 0, s, (const f16*)a->dpre, a->segment_ids, a->acc32,
@@ -321,6 +365,12 @@ extern "C" int vlp_embed_bwd(const vlp_embed_bwd_args* a, void* stream) {
                        (f16*)a->d_type_emb, a->type_vocab, a->H);
     VLP_CHECK_LAUNCH("vlp_embed_bwd_type_reduce");
     return VLP_OK;
+}
+extern "C" int vlp_embed_bwd(const vlp_embed_bwd_args* a, void* stream) { return embed_bwd_run(a, nullptr, 0, stream); }
+extern "C" int vlp_embed_bwd_pos(const vlp_embed_bwd_pos_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->position_ids, "vlp_embed_bwd_pos: null position_ids");
+    VLP_CHECK_ARG(a->max_pos > 0 && (int64_t)a->base.B * a->base.L <= (1ll << 30), "vlp_embed_bwd_pos: bad shape (max_pos > 0)");
+    return embed_bwd_run(&a->base, a->position_ids, a->max_pos, stream);
 }
 
 // =================================================================================================

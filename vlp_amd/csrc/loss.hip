@@ -291,6 +291,96 @@ extern "C" int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stre
 }
 
 // ---------------------------------------------------------------------------------------------
+// Log-probability of one chosen token per row (SCST: the sampled caption's log-probs, modeling.py:1229-1235):
+//   logp[r] = logit[r, id[r]] - lse_r;  backward dlogits[r, v] = g[r] * ([v == id[r]] - exp(logit[r, v] - lse_r)).
+// The same two passes as ce_row_kernel / ce_bwd_kernel; g is a per-row upstream gradient of either sign (it carries the loss scale).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CE_THREADS) void token_logprob_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
+                                                                       float* __restrict__ logp, float* __restrict__ lse, int V) {
+    __shared__ float sh[8];
+    const int row = blockIdx.x;
+    const f16* x = logits + (int64_t)row * ld;
+    const int v8 = V >> 3;
+    float mx = -INFINITY;
+    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
+        f16x8 t = ld8(x + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)t[e]);
+    }
+    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) mx = fmaxf(mx, (float)x[i]);
+    mx = block_reduce_max(mx, sh);
+    float s = 0.f;
+    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
+        f16x8 t = ld8(x + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += __expf((float)t[e] - mx);
+    }
+    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) s += __expf((float)x[i] - mx);
+    s = block_reduce_sum(s, sh);
+    if (threadIdx.x == 0) {
+        const float l = mx + __logf(s);
+        int64_t id = ids[row];
+        id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+        lse[row] = l;
+        logp[row] = (float)x[id] - l;
+    }
+}
+
+extern "C" int vlp_token_logprob_fwd(const vlp_token_logprob_fwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->ids && a->logp && a->lse, "vlp_token_logprob_fwd: null operand");
+    VLP_ENTER(a->logits, "vlp_token_logprob_fwd");
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->ld_logits % 8 == 0 && a->ld_logits >= a->V && (uintptr_t)a->logits % 16 == 0,
+                  "vlp_token_logprob_fwd: layout");
+    hipLaunchKernelGGL(token_logprob_row_kernel, dim3(a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits,
+                       a->ids, a->logp, a->lse, a->V);
+    VLP_CHECK_LAUNCH("vlp_token_logprob_fwd");
+    return VLP_OK;
+}
+
+__global__ __launch_bounds__(CE_THREADS) void token_logprob_bwd_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
+                                                                       const float* __restrict__ lse, const float* __restrict__ g,
+                                                                       f16* __restrict__ dl, int64_t ldd, int V) {
+    const int row = blockIdx.y;
+    const f16* x = logits + (int64_t)row * ld;
+    f16* d = dl + (int64_t)row * ldd;
+    const float c = g[row];
+    const float l = lse[row];
+    int64_t id = ids[row];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    const int n8 = (int)(ldd >> 3);
+    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
+        const int v0 = ch * 8;
+        f16x8 o;
+        if (v0 + 8 <= V) {
+            f16x8 t = ld8(x + v0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (f16)(c * (((v0 + e) == id ? 1.f : 0.f) - __expf((float)t[e] - l)));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int v = v0 + e;
+                o[e] = v < V ? (f16)(c * ((v == id ? 1.f : 0.f) - __expf((float)x[v] - l))) : (f16)0.f;
+            }
+        }
+        st8(d + v0, o);
+    }
+}
+
+extern "C" int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->ids && a->lse && a->g && a->dlogits, "vlp_token_logprob_bwd: null operand");
+    VLP_ENTER(a->logits, "vlp_token_logprob_bwd");
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->ld_logits % 8 == 0 && a->ld_logits >= a->V && a->ld_dlogits % 8 == 0 && a->ld_dlogits >= a->V,
+                  "vlp_token_logprob_bwd: layout");
+    VLP_CHECK_ARG(((uintptr_t)a->logits | (uintptr_t)a->dlogits) % 16 == 0, "vlp_token_logprob_bwd: alignment");
+    int bx = cdiv(a->ld_dlogits / 8, CE_THREADS);
+    if (bx > 16) bx = 16;
+    hipLaunchKernelGGL(token_logprob_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits,
+                       a->ids, a->lse, a->g, (f16*)a->dlogits, a->ld_dlogits, a->V);
+    VLP_CHECK_LAUNCH("vlp_token_logprob_bwd");
+    return VLP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // BCE with logits.  loss = sum_{b,n} [max(x,0) - x*y + log(1 + exp(-|x|))] / (B*N) * N
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bce_fwd_kernel(const f16* x, int64_t ld, const float* y, int64_t ldl, int B, int N, float* part) {

@@ -47,7 +47,7 @@ class VlpPerformanceWarning(UserWarning):
 
 class _State(object):
     """What one forward leaves behind for its backward."""
-    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "task", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth")
+    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "task", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids")
 
 
 class Engine(object):
@@ -653,10 +653,11 @@ class Engine(object):
         return ent[0], ent[1], ent[2]
 
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, attention_mask, masked_pos, train, want_mlm, want_vqa,
-                vis_masked_pos=None):
+                vis_masked_pos=None, position_ids=None, dropout=True, dense=False):
         """Runs embeddings + encoder (+ heads' forward up to the logits).  Returns the _State.  vis_masked_pos ([B, Pm] int64, values
         1..Nv): the mask_image_regions branch -- those region rows enter the encoder as zeros and the pooled output is computed
-        for the pretext loss (pretext_loss())."""
+        for the pretext loss (pretext_loss()).  position_ids ([B, L] int64): explicit position ids (default 0..L-1); dropout=False: a
+        training forward without dropout; dense=True: never the padding-free step (the SCST scoring pass, score_samples)."""
         self.pack()
         model = self._model()
         cfg = model.config
@@ -676,8 +677,9 @@ class Engine(object):
         st = _State()
         st.gen, st.B, st.L, st.P, st.ws = self.gen, B, L, P, ws
         st.mlm_smooth = None
-        p = cfg.hidden_dropout_prob if train else 0.0
-        pa = cfg.attention_probs_dropout_prob if train else 0.0
+        st.pos_ids = position_ids
+        p = cfg.hidden_dropout_prob if (train and dropout) else 0.0
+        pa = cfg.attention_probs_dropout_prob if (train and dropout) else 0.0
         st.p_drop = (p, pa)
         if train and (p > 0 or pa > 0):
             self.step_seed += 1
@@ -685,7 +687,7 @@ class Engine(object):
         M, Mv = B * L, B * Nv
         # ---- padding-free layout (opt-in): row_off / row_map / M' from the mask's own kept lengths --------------------------------
         ro = rm = None
-        if self.varlen and (train or torch.is_grad_enabled()) and L <= 192 and os.environ.get("VLP_ATTN_BWD") is None:
+        if self.varlen and not dense and (train or torch.is_grad_enabled()) and L <= 192 and os.environ.get("VLP_ATTN_BWD") is None:
             lens = self._kept_lengths(attention_mask, masked_pos if P > 0 else None, B, L, Nv)
             if lens is not None and sum(lens) < M:
                 ro, rm, M = self._packing(lens, B, L)
@@ -787,7 +789,7 @@ class Engine(object):
         E = "bert.embeddings."
         K.embed_fwd(st.batch[1], st.batch[2], self.P(E + "word_embeddings.weight"), self.P(E + "position_embeddings.weight"),
                     self.P(E + "token_type_embeddings.weight"), ws["vis_h"], ws["vispe_h"], ws["emb_pre"], B, L, Nv, H,
-                    region_mask=pt["rmask"] if pt is not None else None, row_map=rm, rows=M if rm is not None else 0)
+                    position_ids=position_ids, region_mask=pt["rmask"] if pt is not None else None, row_map=rm, rows=M if rm is not None else 0)
         K.layernorm_fwd(ws["emb_pre"], self.P(E + "LayerNorm.weight"), self.P(E + "LayerNorm.bias"), ws["x0"], M, H, ws["stat0"][0], ws["stat0"][1],
                         dropout_p=p, seed=seed, rng_stream=1000, row_map=rm)
         # ---- encoder (modeling.py:268-372) -----------------------------------------------------------
@@ -962,8 +964,12 @@ class Engine(object):
             img = ws["img16"]
         else:
             img = vf.contiguous()
-        vp = vis_pe.reshape(Mv, PE_DIM).contiguous()
-        K.copy2d(vp, PE_DIM, vp.dtype == torch.float32, ws["vpe_in"], PE_PAD, Mv, PE_DIM, PE_PAD)
+        if isinstance(vis_pe, RawRegions):         # the packed loader's raw boxes + class probabilities (seq2seq_loader.py:338-351)
+            vis_pe.check(vis_feats.shape[0], Nv)
+            K.vis_pe_prep(vis_pe.bbox, vis_pe.cls_prob.reshape(Mv, PE_DIM - 6), ws["vpe_in"], vis_feats.shape[0], Nv, PE_DIM - 6, PE_PAD)
+        else:
+            vp = vis_pe.reshape(Mv, PE_DIM).contiguous()
+            K.copy2d(vp, PE_DIM, vp.dtype == torch.float32, ws["vpe_in"], PE_PAD, Mv, PE_DIM, PE_PAD)
         K.copy2d(self.P("vis_pe_embed.0.weight"), PE_DIM, False, ws["wpe_pad"], PE_PAD, H, PE_DIM, PE_PAD)
         self._nt(img, self.P("vis_embed.0.weight"), ws["h1"], Mv, 2048, 2048, bias=self.P("vis_embed.0.bias"), act=K.ACT_RELU)
         self._nt(ws["h1"], self.P("vis_embed.2.weight"), ws["vis_h"], Mv, H, 2048, bias=self.P("vis_embed.2.bias"), act=K.ACT_RELU)
@@ -1247,6 +1253,47 @@ class Engine(object):
         return tot[:n_steps].clone(), wids[:n_steps].clone(), ptrs[:n_steps].clone()
 
     # ------------------------------------------------------------------------------------------
+    # self-critical sequence training: the gradient of the sampled captions' log-probabilities
+    # ------------------------------------------------------------------------------------------
+    def score_samples(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, sample_ids, mask_word_id):
+        """Teacher-forced scoring of sampled captions (the gradient the reference gets by running its incremental decoder under autograd,
+        modeling.py:1210-1251 / run_img2txt_dist.py:506-507).  Takes the decoder's inputs and its sampled ids [B, T]; builds the scoring
+        sequence on the device (vlp_scst_layout: every sampled position sees exactly the hidden states the incremental decoder computed),
+        runs the training forward on it densely and without dropout, the LM head over the T [MASK] slots and vlp_token_logprob_fwd.
+        Returns (state, logp [B, T] f32 -- a workspace view, overwritten by the next call); backward(state, None, "logprob", g_rows=...)."""
+        self.pack()
+        model = self._model()
+        V = model.config.vocab_size
+        B, in_len, out_len = self._decode_check(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask)
+        T = out_len - in_len
+        if tuple(sample_ids.shape) != (B, T):
+            raise RuntimeError("vlp_amd: score_samples expects sampled ids [B, %d] (output length - input length), got %s" % (T, tuple(sample_ids.shape)))
+        Lo = in_len + 2 * T - 1
+        if Lo > 256:
+            raise RuntimeError("vlp_amd: the SCST scoring sequence has %d + 2 x %d - 1 = %d positions, more than the attention kernels' 256; "
+                               "lower --max_len_b" % (in_len, T, Lo))
+        key = ("scst", B, in_len, T)
+        sw = self._ws.get(key)
+        if sw is None:
+            dev = self.device
+
+            def i64(*sh):
+                return torch.empty(*sh, device=dev, dtype=torch.long)
+            sw = self._ws[key] = dict(ids=i64(B, Lo), seg=i64(B, Lo), pos=i64(B, Lo), mask=i64(B, Lo, Lo), mpos=i64(B, T), labels=i64(B, T),
+                                      logp=torch.empty(B, T, device=dev, dtype=torch.float32))
+        am = attention_mask[:, :out_len, :out_len].to(torch.long).contiguous()
+        tt = token_type_ids[:, :out_len].to(torch.long).contiguous()
+        pid = position_ids[:, :out_len].to(torch.long).contiguous()
+        sw["labels"].copy_(sample_ids)
+        K.scst_layout(input_ids.to(torch.long).contiguous(), sw["labels"], tt, pid, am, sw["ids"], sw["seg"], sw["pos"], sw["mask"], sw["mpos"],
+                      mask_word_id)
+        st = self.forward(vis_feats, vis_pe, sw["ids"], sw["seg"], sw["mask"], sw["mpos"], True, True, False, position_ids=sw["pos"],
+                          dropout=False, dense=True)
+        st.task_labels = sw["labels"].view(-1)
+        K.token_logprob_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V)
+        return st, sw["logp"]
+
+    # ------------------------------------------------------------------------------------------
     # backward
     # ------------------------------------------------------------------------------------------
     def _tn_splits(self, a, b, c, M, N, Kd, ws):
@@ -1292,9 +1339,11 @@ class Engine(object):
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(idx)
 
-    def backward(self, st, gscale, task, g_pretext=None):
+    def backward(self, st, gscale, task, g_pretext=None, g_rows=None):
         """gscale: device f32 tensor [1] = upstream gradient of the task loss (x loss scale); g_pretext: the same for the pretext loss of
-        a mask_image_regions forward.  Writes every parameter gradient into the flat gradient buffers."""
+        a mask_image_regions forward.  task="logprob" (a score_samples forward): g_rows = device f32 [B*T], the upstream gradient of every
+        sampled token's log-probability (x loss scale) in place of the masked-LM loss.  Writes every parameter gradient into the flat
+        gradient buffers."""
         if st.gen != self.gen:
             raise RuntimeError("vlp_amd: the activations of this forward were overwritten by a later forward "
                                "(one in-flight forward per model; run backward before the next forward)")
@@ -1368,7 +1417,11 @@ class Engine(object):
         else:
             C = "cls.predictions."
             R, Vp = B * P, ws["Vp"]
-            if st.mlm_smooth is None:
+            if task == "logprob":
+                if g_rows is None or g_rows.numel() != R:
+                    raise RuntimeError("vlp_amd: backward(task='logprob') needs g_rows with %d elements" % R)
+                K.token_logprob_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V)
+            elif st.mlm_smooth is None:
                 K.mlm_loss_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
             else:
                 K.mlm_loss_ls_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V, *st.mlm_smooth)
@@ -1508,10 +1561,16 @@ class Engine(object):
             # slot order = table order) and the three embedding tables (five launches); their gradient slice is announced from here
             if defer:
                 K.layernorm_bwd_reduce_batched(ws["ln_slots"], self._ln_table(), 2 * NL + 1, M, H, beta=beta)
-            K.embed_bwd(dpre, input_ids, token_type_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
-                        self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
-                        ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
-                        region_mask=pt[0]["rmask"] if pt is not None else None, parts=2)
+            if st.pos_ids is not None:          # explicit position ids (score_samples): the position table follows them
+                K.embed_bwd_pos(dpre, input_ids, token_type_ids, st.pos_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
+                                self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
+                                ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
+                                region_mask=pt[0]["rmask"] if pt is not None else None, parts=2)
+            else:
+                K.embed_bwd(dpre, input_ids, token_type_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
+                            self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
+                            ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
+                            region_mask=pt[0]["rmask"] if pt is not None else None, parts=2)
             self._bucket_done(NL + 1)           # position / type / word embedding tables (tied decoder wgrad + embedding backward) are final
 
         # region rows first (the region-projection dgrad / wgrads below wait for d_vis_h / d_vispe_h only); the tables and the LayerNorm

@@ -459,6 +459,22 @@ class _LossFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+class _LogprobFn(torch.autograd.Function):
+    """The sampled captions' log-probabilities [B, T] of a train-mode `sample_mode='sample'` forward as an autograd output: any torch loss
+    on them (RewardCriterion, scst_utils.py:66-78) reaches Engine.backward(task="logprob") with dL/dlogp, which carries the fp16 loss scale."""
+
+    @staticmethod
+    def forward(ctx, anchor, logp, engine, state):
+        ctx.engine, ctx.state = engine, state
+        return logp.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        g = grad.detach().to(torch.float32).contiguous().reshape(-1)
+        ctx.engine.backward(ctx.state, None, "logprob", g_rows=g)
+        return None, None, None, None
+
+
 class BertForPreTrainingLossMask(PreTrainedBertModel):
     """The VLP training / VQA model (:982-1143) on the fused HIP path."""
 
@@ -552,7 +568,9 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     """Incremental caption decoder (:1147-1494): same parameter tree as BertForPreTrainingLossMask (checkpoint compatible);
     greedy decoding (:1189-1253) and beam search (:1255-1494) run on the HIP engine with per-layer K/V caches
     (Engine.decode_greedy / Engine.decode_beam); the host keeps only what the reference keeps on the host (n-gram blocking
-    over python lists, back-tracking of the frames).  sample_mode='sample' draws with the library's counter-based RNG."""
+    over python lists, back-tracking of the frames).  sample_mode='sample' draws with the library's counter-based RNG; in train() mode with gradients enabled
+    it also returns differentiable log-probabilities (SCST, run_img2txt_dist.py:506-507): a teacher-forced scoring pass of the sampled ids on
+    the training engine (Engine.score_samples), without dropout."""
     tasks = "img2txt"
 
     def __init__(self, config, mask_word_id=0, num_labels=2, search_beam_size=1, length_penalty=1.0, eos_id=0,
@@ -584,6 +602,14 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
                 return self.beam_search(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=task_idx)
         if sample_mode not in ("greedy", "sample"):
             raise NotImplementedError("sample_mode=%r (the reference knows 'greedy' and 'sample', modeling.py:1227-1237)" % (sample_mode,))
+        if sample_mode == "sample" and self.training and torch.is_grad_enabled():
+            # SCST (run_img2txt_dist.py:505-507): draw on the K/V-cache decoder, then score the drawn ids with one training forward whose
+            # [MASK] slots see exactly the decoder's hidden states; the log-probs' backward is that forward's backward
+            eng = self.engine
+            with torch.no_grad():
+                ids, _ = eng.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id, sample=True)
+            st, logp = eng.score_samples(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, ids, self.mask_word_id)
+            return ids, _LogprobFn.apply(eng._anchor, logp, eng, st)
         with torch.no_grad():
             return self.engine.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
                                              sample=(sample_mode == "sample"))

@@ -30,7 +30,8 @@ import torch
 
 from . import synthetic
 from .distributed import DistributedDataParallel as DDP
-from .modeling import BertConfig, BertForPreTrainingLossMask, load_checkpoint_state
+from .input_prep import MaskSpec
+from .modeling import BertConfig, BertForPreTrainingLossMask, BertForSeq2SeqDecoder, load_checkpoint_state
 from .optimization import BertAdam, warmup_linear           # noqa: F401  (re-exported like the reference imports them)
 from .optimization_fp16 import FP16_Optimizer_State, FusedAdam
 
@@ -156,12 +157,19 @@ def derive_args(args):
     args.dist_url = args.dist_url.replace("[PT_OUTPUT_DIR]", args.output_dir)
     assert args.tasks in ("img2txt", "vqa2")
     assert args.enable_butd is True, "only support region attn! featmap attn deprecated"
-    if args.scst:
-        raise NotImplementedError("--scst needs the coco-caption CIDEr scorer (empty submodule in the reference checkout); out of scope")
+    assert (not args.scst) or args.dataset == "coco", "scst support on coco only!"
+    if args.scst:                                        # :201-204
+        assert args.max_pred == 0 and args.mask_prob == 0, "no mask for scst!"
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
     return args
+
+
+def check_scst_start(args, recover_step):
+    """:322: SCST fine-tunes a maximum-likelihood checkpoint (--model_recover_path, or a resume of this output directory)."""
+    if (recover_step is None) and (args.model_recover_path is None):
+        assert args.scst is False, "must init from maximum likelihood training"
 
 
 def model_config(args):
@@ -208,8 +216,13 @@ def build_model(args, device):
         if not wpath or not os.path.exists(wpath):
             raise EnvironmentError("no pretrained weights available offline: pass --from_scratch or --model_recover_path")
         state = torch.load(wpath, map_location="cpu")
-    model = BertForPreTrainingLossMask(config, num_labels=2, enable_butd=args.enable_butd, len_vis_input=args.len_vis_input,
-                                       tasks=args.tasks, allow_random_fc7=bool(args.synthetic))
+    if args.scst:
+        # :355-361: the incremental decoder, built from the maximum-likelihood checkpoint; [MASK] / [SEP] as mask_word_id / eos_id (:319-320)
+        model = BertForSeq2SeqDecoder(config, mask_word_id=synthetic.MASK_ID, num_labels=2, search_beam_size=1, eos_id=synthetic.SEP_ID,
+                                      enable_butd=args.enable_butd, len_vis_input=args.len_vis_input)
+    else:
+        model = BertForPreTrainingLossMask(config, num_labels=2, enable_butd=args.enable_butd, len_vis_input=args.len_vis_input,
+                                           tasks=args.tasks, allow_random_fc7=bool(args.synthetic))
     if state is not None:
         # the reference always goes through from_pretrained(state_dict=...) (:324-336): gamma/beta renames, segment table 2 -> 6
         # rows for --new_segment_ids, position-table tiling for --max_position_embeddings, and an ERROR on any other size mismatch
@@ -269,6 +282,55 @@ def train_step(model, optimizer, batch, lr_this_step, mask_image_regions=False, 
         optimizer.step()
         optimizer.zero_grad()
     return loss_tuple
+
+
+def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None):
+    """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
+    train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
+    baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
+    called at the end of each phase: "greedy_decode", "sample_forward" (sampled decode + scoring forward), "reward_host", "backward" and,
+    unless accumulating, "optimizer" (tools/scst_bench.py times them)."""
+    if mark is None:
+        def mark(phase):
+            pass
+    from .scst import clean_captions, self_critical_reward
+    (input_ids, segment_ids, input_mask, lm_label_ids, masked_pos, masked_weights, is_next, task_idx, img, vis_masked_pos, vis_pe,
+     ans_labels) = batch
+    L = input_ids.shape[1]
+    if isinstance(input_mask, MaskSpec):
+        input_mask = input_mask.dense(L)                  # the decoder reads the dense [B, L, L] mask
+    position_ids = torch.arange(L, dtype=input_ids.dtype, device=input_ids.device).unsqueeze(0).expand_as(input_ids)
+    input_dummy = input_ids[:, :len_vis_input + 2]        # +2 for [CLS] and [SEP]
+    model.eval()
+    with torch.no_grad():
+        greedy_raw, _ = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="greedy")
+    mark("greedy_decode")
+    model.train()
+    gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample")
+    mark("sample_forward")
+    greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
+    gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
+    gt_ids = input_ids[:, len_vis_input + 2:]
+    reward, _ = self_critical_reward(greedy_res, gt_ids, gen_result, gt_ids.size(0))
+    reward = torch.from_numpy(reward).float().to(gen_result.device)
+    mean_reward = reward.mean()
+    mark("reward_host")
+    loss = rl_crit(sample_logprobs, gen_result, reward)
+    bwd = loss / accum_steps if accum_steps > 1 else loss
+    if hasattr(optimizer, "backward"):
+        optimizer.backward(bwd)
+    else:
+        gs = getattr(optimizer, "grad_scale", 1.0)
+        bwd.float().backward(gradient=torch.full_like(bwd, gs, dtype=torch.float32) if gs != 1.0 else None)
+    mark("backward")
+    if not accumulate:
+        if hasattr(optimizer, "backward"):
+            for g in optimizer.param_groups:
+                g["lr"] = lr_this_step
+        optimizer.step()
+        optimizer.zero_grad()
+        mark("optimizer")
+    return loss, mean_reward
 
 
 def build_packed_loader(args, device):
@@ -343,9 +405,17 @@ def main(argv=None):
     t_total = int(steps_per_epoch * args.num_train_epochs * 1. / args.gradient_accumulation_steps)
 
     recover_step = _get_max_epoch_model(args.output_dir)     # :310: resume from the newest epoch that has model AND optimizer files
+    check_scst_start(args, recover_step)
     if recover_step:
         logger.info("***** Recover model: %d *****", recover_step)
         args.model_recover_path = os.path.join(args.output_dir, "model.{0}.bin".format(recover_step))
+    rl_crit = None
+    if args.scst:
+        from .scst import RewardCriterion
+        rl_crit = RewardCriterion()
+        if args.drop_prob > 0:
+            logger.info("--scst: --drop_prob %g is inert: the sampled decode and the scoring pass both run without dropout (INTEGRATION.md)",
+                        args.drop_prob)
     model = build_model(args, device)
     if distributed:
         model = DDP(model, device_ids=[args.local_rank], output_device=args.local_rank, find_unused_parameters=True)
@@ -374,20 +444,29 @@ def main(argv=None):
     stop_after = args.stop_after_epoch if args.stop_after_epoch > 0 else args.num_train_epochs
     for i_epoch in range((recover_step or 0) + 1, min(args.num_train_epochs, stop_after) + 1):
         t0 = time.time()
-        losses = []
+        losses, rewards = [], []
         if loader is not None:
             loader.set_epoch(i_epoch - 1)                                                             # train_sampler.set_epoch(i_epoch-1), :455
         for step, batch in enumerate(loader if loader is not None else synthetic_batches(args, device, steps_per_epoch, args.global_rank)):
             acc = (step + 1) % args.gradient_accumulation_steps != 0
             lr = args.learning_rate * warmup_linear(global_step / t_total, args.warmup_proportion)
-            lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,
-                            drop_worst_ratio=args.max_drop_worst_ratio if i_epoch > args.drop_after else 0,
-                            accumulate=acc, accum_steps=args.gradient_accumulation_steps)
+            if args.scst:
+                loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
+                                         accum_steps=args.gradient_accumulation_steps)
+                rewards.append(mean_r.detach())
+            else:
+                lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,
+                                drop_worst_ratio=args.max_drop_worst_ratio if i_epoch > args.drop_after else 0,
+                                accumulate=acc, accum_steps=args.gradient_accumulation_steps)
             if not acc:
                 global_step += 1
             if step % args.log_every == 0:        # the only host read-back; the reference does 4 per step (:535-538)
-                losses.append(float((lt[0] + lt[1] + lt[2]).detach()))
-                logger.info("Epoch %d, Iter %d, Loss %.3f", i_epoch, step, losses[-1])
+                if args.scst:                     # :540 adds the mean reward
+                    losses.append(float(loss.detach()))
+                    logger.info("Epoch %d, Iter %d, Loss %.3f, Mean R %.3f", i_epoch, step, losses[-1], float(torch.stack(rewards).mean()))
+                else:
+                    losses.append(float((lt[0] + lt[1] + lt[2]).detach()))
+                    logger.info("Epoch %d, Iter %d, Loss %.3f", i_epoch, step, losses[-1])
         torch.cuda.synchronize()
         dt = time.time() - t0
         if hasattr(optimizer, "consolidate"):
