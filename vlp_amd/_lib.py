@@ -336,6 +336,10 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _nbytes(t):
+    return 0 if t is None else t.numel() * t.element_size()
+
+
 def _req_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -345,16 +349,23 @@ def _req_cuda(*ts):
 # --------------------------------------------------------------------------------------------------
 # thin typed wrappers
 # --------------------------------------------------------------------------------------------------
+def _gemm_nt_args(x, w, y, M, N, K, ldx, ldw, ldy, bias, residual, ldr, preact, ldp, mul_src, ldm, act, mul_mode, alpha, dropout_p, seed, rng_stream,
+                  variant=0, row_map=None):
+    """GemmNtArgs of gemm_nt / gemm_nt_splitk: a pitch left None is the tensor's row stride (0 without the tensor)."""
+    return GemmNtArgs(ptr(x), ldx if ldx is not None else x.stride(0), ptr(w), ldw if ldw is not None else w.stride(0),
+                      ptr(y), ldy if ldy is not None else y.stride(0), ptr(bias),
+                      ptr(residual), (ldr if ldr is not None else (residual.stride(0) if residual is not None else 0)),
+                      ptr(preact), (ldp if ldp is not None else (preact.stride(0) if preact is not None else 0)),
+                      ptr(mul_src), (ldm if ldm is not None else (mul_src.stride(0) if mul_src is not None else 0)),
+                      M, N, K, act, mul_mode, alpha, dropout_p, seed, rng_stream, variant, ptr(row_map))
+
+
 def gemm_nt(x, w, y, M, N, K, ldx=None, ldw=None, ldy=None, bias=None, residual=None, ldr=None, preact=None, ldp=None,
             mul_src=None, ldm=None, act=ACT_NONE, mul_mode=MUL_NONE, alpha=1.0, dropout_p=0.0, seed=0, rng_stream=0,
             variant=0, row_map=None):
     _req_cuda(x, w, y, row_map)
-    a = GemmNtArgs(ptr(x), ldx if ldx is not None else x.stride(0), ptr(w), ldw if ldw is not None else w.stride(0),
-                   ptr(y), ldy if ldy is not None else y.stride(0), ptr(bias),
-                   ptr(residual), (ldr if ldr is not None else (residual.stride(0) if residual is not None else 0)),
-                   ptr(preact), (ldp if ldp is not None else (preact.stride(0) if preact is not None else 0)),
-                   ptr(mul_src), (ldm if ldm is not None else (mul_src.stride(0) if mul_src is not None else 0)),
-                   M, N, K, act, mul_mode, alpha, dropout_p, seed, rng_stream, variant, ptr(row_map))
+    a = _gemm_nt_args(x, w, y, M, N, K, ldx, ldw, ldy, bias, residual, ldr, preact, ldp, mul_src, ldm, act, mul_mode, alpha, dropout_p, seed,
+                      rng_stream, variant, row_map)
     _check(load().vlp_gemm_nt(C.byref(a), stream_ptr()))
 
 
@@ -370,13 +381,9 @@ def gemm_nt_splitk_workspace_bytes(M, N, splits):
 def gemm_nt_splitk(x, w, y, M, N, K, splits, workspace, ldx=None, ldw=None, ldy=None, bias=None, residual=None, ldr=None, preact=None, ldp=None,
                    mul_src=None, ldm=None, act=ACT_NONE, mul_mode=MUL_NONE, alpha=1.0, dropout_p=0.0, seed=0, rng_stream=0):
     _req_cuda(x, w, y, workspace)
-    a = GemmNtArgs(ptr(x), ldx if ldx is not None else x.stride(0), ptr(w), ldw if ldw is not None else w.stride(0),
-                   ptr(y), ldy if ldy is not None else y.stride(0), ptr(bias),
-                   ptr(residual), (ldr if ldr is not None else (residual.stride(0) if residual is not None else 0)),
-                   ptr(preact), (ldp if ldp is not None else (preact.stride(0) if preact is not None else 0)),
-                   ptr(mul_src), (ldm if ldm is not None else (mul_src.stride(0) if mul_src is not None else 0)),
-                   M, N, K, act, mul_mode, alpha, dropout_p, seed, rng_stream, 0, None)
-    _check(load().vlp_gemm_nt_splitk(C.byref(a), splits, ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()))
+    a = _gemm_nt_args(x, w, y, M, N, K, ldx, ldw, ldy, bias, residual, ldr, preact, ldp, mul_src, ldm, act, mul_mode, alpha, dropout_p, seed,
+                      rng_stream)
+    _check(load().vlp_gemm_nt_splitk(C.byref(a), splits, ptr(workspace), _nbytes(workspace), stream_ptr()))
 
 
 def gemm_tn_workspace_bytes(M, N, K):
@@ -387,7 +394,7 @@ def gemm_tn(a_, b_, c_, M, N, K, lda=None, ldb=None, ldc=None, beta=0, workspace
     _req_cuda(a_, b_, c_)
     a = GemmTnArgs(ptr(a_), lda if lda is not None else a_.stride(0), ptr(b_), ldb if ldb is not None else b_.stride(0),
                    ptr(c_), ldc if ldc is not None else c_.stride(0), M, N, K, beta,
-                   ptr(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0, variant, splits,
+                   ptr(workspace), _nbytes(workspace), variant, splits,
                    ptr(bias_out))
     _check(load().vlp_gemm_tn(C.byref(a), stream_ptr()))
 
@@ -406,7 +413,7 @@ def gemm_tn_grouped(problems, workspace=None):
         if w is not None:
             _req_cuda(w)
         arr[i] = GemmTnArgs(ptr(a_), a_.stride(0), ptr(b_), b_.stride(0), ptr(c_), c_.stride(0), M, N, K, beta, ptr(w),
-                            (w.numel() * w.element_size()) if w is not None else 0, 0, 0, ptr(bias_out))
+                            _nbytes(w), 0, 0, ptr(bias_out))
     _check(load().vlp_gemm_tn_grouped(arr, len(problems), stream_ptr()))
 
 
@@ -417,7 +424,7 @@ def colsum_workspace_bytes(M, N):
 def colsum(a_, out, M, N, lda=None, beta=0, workspace=None):
     _req_cuda(a_, out)
     a = ColsumArgs(ptr(a_), lda if lda is not None else a_.stride(0), M, N, ptr(out), beta, ptr(workspace),
-                   workspace.numel() * workspace.element_size())
+                   _nbytes(workspace))
     _check(load().vlp_colsum(C.byref(a), stream_ptr()))
 
 
@@ -552,7 +559,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, M, H, workspace, 
     a = LayerNormBwdArgs(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), dx.stride(0),
                          ptr(dx_drop), dx_drop.stride(0) if dx_drop is not None else 0, ptr(dgamma), ptr(dbeta), M, H, beta,
                          dy_drop[0], dy_drop[1], dy_drop[2], out_drop[0], out_drop[1], out_drop[2],
-                         ptr(workspace), workspace.numel() * workspace.element_size(), 1 if defer_reduce else 0, ptr(row_map))
+                         ptr(workspace), _nbytes(workspace), 1 if defer_reduce else 0, ptr(row_map))
     _check(load().vlp_layernorm_bwd(C.byref(a), stream_ptr()))
 
 
@@ -577,23 +584,28 @@ def embed_bwd_workspace_floats(B, L, Nv, H):
     return int(load().vlp_embed_bwd_workspace_floats(B, L, Nv, H))
 
 
+def _embed_bwd_args(dpre, input_ids, segment_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
+                    B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream, region_mask, parts):
+    _req_cuda(dpre, input_ids, segment_ids, d_word, d_pos, d_type, acc32, region_mask)
+    return EmbedBwdArgs(ptr(dpre), ptr(input_ids), ptr(segment_ids), ptr(vis_h), ptr(vispe_h), ptr(d_word), ptr(d_pos), ptr(d_type),
+                        ptr(d_vis_h), ptr(d_vispe_h), ptr(acc32), B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream,
+                        ptr(region_mask), parts)
+
+
 def embed_bwd(dpre, input_ids, segment_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
               B, L, Nv, H, vocab, type_vocab, drop_p=0.0, seed=0, vis_stream=0, vispe_stream=0, region_mask=None, parts=0):
     """parts: 0 = everything, 1 = region rows only (d_vis_h / d_vispe_h), 2 = the embedding tables only."""
-    _req_cuda(dpre, input_ids, segment_ids, d_word, d_pos, d_type, acc32, region_mask)
-    a = EmbedBwdArgs(ptr(dpre), ptr(input_ids), ptr(segment_ids), ptr(vis_h), ptr(vispe_h), ptr(d_word), ptr(d_pos), ptr(d_type),
-                     ptr(d_vis_h), ptr(d_vispe_h), ptr(acc32), B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream,
-                     ptr(region_mask), parts)
+    a = _embed_bwd_args(dpre, input_ids, segment_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
+                        B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream, region_mask, parts)
     _check(load().vlp_embed_bwd(C.byref(a), stream_ptr()))
 
 
 def embed_bwd_pos(dpre, input_ids, segment_ids, position_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
                   B, L, Nv, H, vocab, type_vocab, drop_p=0.0, seed=0, vis_stream=0, vispe_stream=0, region_mask=None, parts=0):
     """embed_bwd with position_ids (int64 [B, L], device): row (b, l) adds into d_pos[position_ids[b, l]]."""
-    _req_cuda(dpre, input_ids, segment_ids, position_ids, d_word, d_pos, d_type, acc32, region_mask)
-    base = EmbedBwdArgs(ptr(dpre), ptr(input_ids), ptr(segment_ids), ptr(vis_h), ptr(vispe_h), ptr(d_word), ptr(d_pos), ptr(d_type),
-                        ptr(d_vis_h), ptr(d_vispe_h), ptr(acc32), B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream,
-                        ptr(region_mask), parts)
+    _req_cuda(position_ids)
+    base = _embed_bwd_args(dpre, input_ids, segment_ids, vis_h, vispe_h, d_word, d_pos, d_type, d_vis_h, d_vispe_h, acc32,
+                           B, L, Nv, H, vocab, type_vocab, drop_p, seed, vis_stream, vispe_stream, region_mask, parts)
     a = EmbedBwdPosArgs(base, ptr(position_ids), d_pos.shape[0])
     _check(load().vlp_embed_bwd_pos(C.byref(a), stream_ptr()))
 

@@ -47,7 +47,19 @@ class VlpPerformanceWarning(UserWarning):
 
 class _State(object):
     """What one forward leaves behind for its backward."""
-    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "task", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids")
+    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids")
+
+    def __init__(self):
+        self.gen = self.B = self.L = self.P = 0      # engine generation, batch, sequence length, masked positions per sample
+        self.ws = None               # the (B, L, P) workspace holding the activations
+        self.seed, self.p_drop = 0, (0.0, 0.0)       # dropout: seed of the step, (hidden, attention) probabilities
+        self.batch = None            # (img, input_ids, token_type_ids, masked_pos) as the kernels read them
+        self.has_mlm = False         # P > 0: the masked-LM head ran
+        self.pos_ids = None          # explicit position ids ([B, L] int64) or None = 0..L-1
+        self.pk = None               # (row_off, row_map, M') of a packed forward
+        self.pretext = None          # (pretext workspace, vis_masked_pos) of a mask_image_regions forward
+        self.task_labels = None      # set by the loss of this forward (mlm_loss / vqa_loss / score_samples), read by its backward
+        self.mlm_smooth = None       # label-smoothed loss: the scalar arguments of the matching backward launch
 
 
 class Engine(object):
@@ -61,9 +73,6 @@ class Engine(object):
     # single-kernel timings under rocprofv3).  bench.py's live roofline samples stay single-kernel measurements: a sampled launch
     # first lets the side stream drain (see _nt).
     WGRAD_SIDE_STREAM = os.environ.get("VLP_WGRAD_SIDE_STREAM", "1") == "1"
-    LN_DEFER = os.environ.get("VLP_LN_DEFER", "1") == "1"               # LayerNorm dgamma / dbeta second stages batched into one launch per backward
-    TAIL_ON_SIDE = os.environ.get("VLP_TAIL_SIDE", "1") == "1"          # embedding-table gradients + that batched launch on the side stream, under the region-projection backward
-    SHADOW_ON_SIDE = os.environ.get("VLP_SHADOW_SIDE", "1") == "1"      # W^T shadows transposed on the side stream during the forward
     # mask_image_regions: the reference's loader line `input_mask[:, vis_masked_pos].fill_(0)` (seq2seq_loader.py:303-304) indexes with a
     # numpy array -- advanced indexing, i.e. it fills a COPY and leaves the mask untouched (checked on torch 2.10 and, against the unmodified
     # loader, by the reference-pinning CPU tests): masked regions enter the encoder as zeros but stay attendable.
@@ -89,12 +98,7 @@ class Engine(object):
     # one partial-sum launch per finished gradient slice on the side stream during backward LOSES, 9.738 / 9.722 vs 9.666 / 9.671 ms/step;
     # summing the 93 % of the buffer that is final when the side stream reaches the embedding tables, under the region-projection backward,
     # is a wash, 9.568 / 9.548 vs 9.558 / 9.573 -- profiles/r05_instep_ab_norm_per_slice.txt.  Both forms were removed.)
-    GROUPED_WGRAD = os.environ.get("VLP_GROUPED_WGRAD", "1") == "1"     # one vlp_gemm_tn_grouped launch per layer instead of 4 split-M wgrads + 4 reduces
-    TN_SPLITS = None         # None -> vlp_amd.tuning (variant flags, split-M factor) per (M, N, K)
-    # split-M factor: the wgrad outputs are small (36..144 tiles of 128x128) and the contraction long (M = 10 688), so the
-    # workgroup count tiles*splits has to land just under a multiple of the 256 CUs x 2 resident workgroups: 3 (432 workgroups)
-    # beats 4 (576) by 25 % on the FFN wgrads, 14 beats 8 on the 768x768 ones (microbench, profiles/r01_tn_split_sweep.json)
-    TN_SPLIT_CANDIDATES = (0, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16)
+    TN_SPLITS = None         # None -> vlp_amd.tuning (variant flags, split-M factor) per (M, N, K); candidates: tuning.TN_SPLIT_CANDIDATES
     TN_VARIANT_CANDIDATES = (2, 26)     # 26 = LDS-DMA kernel + XCD-aware tile order + split-major block order
     # bench.py's live roofline: an event pair around a launch costs ~2 x 2.5 us of serialisation (5-6 % of the step when all 103
     # NT launches of a step are bracketed), so every 8th launch is sampled; 103 is coprime to 8, so successive steps sample
@@ -102,6 +106,7 @@ class Engine(object):
     PROF_EVERY = 8
     _nt_choice = {}          # shared across engines of one process: (M, N, K) -> variant
     _tn_choice = {}          # (M, N, K) -> splits
+    _skinny_choice = {}      # (M, N, K) -> ("v", variant) | ("s", splits)
 
     def __init__(self, model):
         self._model = weakref.ref(model)
@@ -112,8 +117,19 @@ class Engine(object):
         self.grads_dirty = False          # False -> next backward overwrites (beta = 0), True -> accumulates
         self.grad_ready_hook = None       # callable(bucket_index) set by the DDP wrapper
         self.post_backward_hook = None    # callable() set by the DDP wrapper
+        self.names = self.offsets = self.sizes = self.buckets = None      # plan_layout() of the packed model (pack)
+        self.flat = self.gflat = None     # {"decay" | "nodecay": flat fp16 parameter / gradient buffer} (pack)
+        self._params = None               # name -> parameter (pack)
+        self._unused = None               # names of the parameters the task never gives a gradient (pack)
+        self._anchor = None               # autograd anchor of the hand-off in modeling.py (pack)
+        self.device = None
         self._ws = {}
         self._shadow = None
+        self._shadow_ev = None            # event behind the W^T shadows a training forward transposed on the side stream, consumed by its backward
+        self._ln_tab = None               # _ln_table()
+        self._zero1 = None                # zero_placeholder()
+        self._pretext_on = False          # the latest forward ran with mask_image_regions
+        self._pooler_dirty = False        # the latest backward wrote pooler gradients (pretext branch)
         self.prof = None                  # list -> every PROF_EVERY-th NT-GEMM launch is bracketed by HIP events (bench.py roofline)
         self._opt_stream = None           # optimizer stream of the pipelined FusedAdam step (optimization_fp16._step_pipelined)
         self._param_events = None         # {"nodecay" | bucket index: event} of the last pipelined optimizer step, consumed by forward
@@ -121,7 +137,8 @@ class Engine(object):
         self.shard_plan = None            # vlp_amd.distributed.ShardPlan when the optimizer step is sharded over the ranks (VLP_DDP_MODE=sharded)
         self._param_works = None          # {"nodecay" | reducer bucket: collective work} of the last sharded step's parameter all-gather
         self.param_gather_stamps = None   # list -> (before, after) event pairs around every wait for a parameter all-gather (comm profile)
-        self._side = None                 # second HIP stream for the layer wgrads (created on first use)
+        self._side = None                 # second HIP stream for the layer wgrads (_side_stream: created on first use)
+        self._side_done = None            # with it: per dY-set parity, the event behind the last layer wgrads that read the set
         self._side_busy = False           # True while backward may have work queued on it
         self._prof_ctr = 0
         self.varlen = self.VARLEN         # padding-free (packed) training step: True | False | "auto", see VARLEN
@@ -129,6 +146,7 @@ class Engine(object):
         self._rb_streak = 0               # consecutive read-backs without a cache hit in between
         self._rb_warned = False
         self._pk_stage = None             # ring of pinned row_off staging buffers (+ events) for _packing
+        self._pk_stage_i = 0              # next slot of that ring
         self._pk_cache = {}               # kept-length tuple -> (row_off, row_map device tensors, M'): batches repeat in bench / epochs
         self._pk_lens = {}                # id(mask tensor) -> (weakref, version, ..., lens): lengths derived from a dense mask, once per tensor
         self.last_packed_rows = None      # M' of the latest packed forward (None: dense) -- bench.py / tests read it
@@ -242,6 +260,7 @@ class Engine(object):
         self.packed = False
         self._ws = {}
         self._shadow = None
+        self._shadow_ev = None
         self._ln_tab = None
 
     def P(self, name):
@@ -253,7 +272,7 @@ class Engine(object):
     def unused_parameter_names(self):
         """Parameters that receive no gradient (static per task).  The pooler is used by the vis_pretext branch only:
         it leaves the set while the latest forward ran with mask_image_regions."""
-        if getattr(self, "_pretext_on", False):
+        if self._pretext_on:
             return set(self._unused) - {"bert.pooler.dense.weight", "bert.pooler.dense.bias"}
         return set(self._unused)
 
@@ -295,21 +314,19 @@ class Engine(object):
                 prof.append((e0, e1))
         if self._params_done is None:
             return
-        if key is None:
-            if host:
-                self._params_done.synchronize()
-            else:
-                torch.cuda.current_stream().wait_event(self._params_done)
-            if host:
-                self._param_events, self._params_done = None, None
-            return
-        ev = self._param_events.get(key) if self._param_events else None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
+        if key is not None:          # one chunk: the current stream waits for that chunk's event (no event: nothing was written to it)
+            ev = self._param_events.get(key) if self._param_events else None
+            if ev is not None:
+                torch.cuda.current_stream().wait_event(ev)
+        elif host:                   # everything, on the calling thread: the step is over and its events are spent
+            self._params_done.synchronize()
+            self._param_events, self._params_done = None, None
+        else:                        # everything, on the current stream: the events stay for the other streams' waits
+            torch.cuda.current_stream().wait_event(self._params_done)
 
     def zero_placeholder(self, device):
         """The shared read-only [1] fp32 zero that stands for a loss the task does not have (modeling.py:1096-1098, 1133)."""
-        z = getattr(self, "_zero1", None)
+        z = self._zero1
         if z is None or z.device != device:
             z = self._zero1 = torch.zeros(1, device=device, dtype=torch.float32)
         return z
@@ -317,7 +334,7 @@ class Engine(object):
     def is_zero_placeholder(self, t):
         """True when `t` is the shared zero a forward hands out for a loss the task does not have (train loops skip it instead of
         launching `+ 0`).  The placeholder is shared by every forward of this engine: do not modify it in place."""
-        return t is getattr(self, "_zero1", None)
+        return t is self._zero1
 
     def zero_grad(self):
         """optimizer.zero_grad() of the train loop (run_img2txt_dist.py:585): no memset -- the next
@@ -413,7 +430,7 @@ class Engine(object):
     def _ln_table(self):
         """Device table [2 * layers + 1, 2] of (dgamma, dbeta) addresses: slot 2i = attention.output.LayerNorm of layer i, 2i + 1 =
         output.LayerNorm of layer i, last = embeddings.LayerNorm (addresses of the flat gradient buffer are stable)."""
-        if getattr(self, "_ln_tab", None) is None:
+        if self._ln_tab is None:
             NL = self._model().config.num_hidden_layers
             rows = []
             for i in range(NL):
@@ -464,24 +481,13 @@ class Engine(object):
         if not tuning.AUTOTUNE:
             v = Engine._nt_choice[key] = tuning.nt_variant(M, N, Kd)
             return v
-        best, best_t = self.NT_CANDIDATES[0], float("inf")
-        cands = self.NT_CANDIDATES_SKINNY if M <= 1024 else self.NT_CANDIDATES
+        best = self.NT_CANDIDATES[0]
         if M * N >= 128 * 128 * 4:          # tiny problems: not worth timing
+            # (256-wide n tiles leave most CUs idle on narrow outputs: not candidates there)
+            cands = [c for c in (self.NT_CANDIDATES_SKINNY if M <= 1024 else self.NT_CANDIDATES)
+                     if not ((c & 7 == 5 and c < 64 or c == 73) and N < 1024)]
             torch.cuda.synchronize()        # nothing else (e.g. side-stream wgrads) may run while candidates are timed
-            for rnd in range(2):              # two interleaved rounds, best-of: robust against clock / neighbour noise
-                for cand in cands:
-                    if (cand & 7 == 5 and cand < 64 or cand == 73) and N < 1024:
-                        continue                  # 256-wide n tiles leave most CUs idle on narrow outputs
-                    K.gemm_nt(x, w, y, M, N, Kd, variant=cand, **kw)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(4 if M > 1024 else 12):
-                        K.gemm_nt(x, w, y, M, N, Kd, variant=cand, **kw)
-                    e1.record()
-                    e1.synchronize()
-                    t = e0.elapsed_time(e1)
-                    if t < best_t:
-                        best, best_t = cand, t
+            best = tuning.best_of(cands, lambda c, i: K.gemm_nt(x, w, y, M, N, Kd, variant=c, **kw), rounds=2, reps=4 if M > 1024 else 12)
         Engine._nt_choice[key] = best
         tuning.remember("nt", M, N, Kd, best)
         return best
@@ -507,9 +513,6 @@ class Engine(object):
             side.wait_stream(main)
         self.prof.append((e0, e1, 2.0 * M * N * Kd))
 
-    SKINNY_SPLITS = (2, 3, 4, 6, 8, 12, 16)
-    _skinny_choice = {}      # (M, N, K) -> ("v", variant) | ("s", splits)
-
     def _nt_skinny(self, x, w, y, M, N, Kd, skws, tune_ws=None, **kw):
         """NT GEMM of the incremental decoder (M = sequences x 2 rows): the ordinary kernels have only N/128 workgroups to run, so the
         split-K form (vlp_gemm_nt_splitk) and every ordinary variant are timed once per shape.  `tune_ws()` returns same-shaped weight
@@ -523,28 +526,17 @@ class Engine(object):
             ch = Engine._skinny_choice[key] = tuning.skinny_choice(M, N, Kd)
         if ch is None:
             wl = list(tune_ws()) if tune_ws is not None else [w]
-            reps = max(12, len(wl))
+            cands = [("v", v) for v in self.NT_CANDIDATES_SKINNY] + [("s", sp) for sp in tuning.SKINNY_SPLITS if Kd // 64 >= sp]
 
-            def timed(fn):
-                fn(wl[0])
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(reps):
-                    fn(wl[i % len(wl)])
-                e1.record()
-                e1.synchronize()
-                return e0.elapsed_time(e1)
+            def launch(c, i):
+                ww = wl[i % len(wl)]
+                if c[0] == "v":
+                    K.gemm_nt(x, ww, y, M, N, Kd, variant=c[1], **kw)
+                else:
+                    K.gemm_nt_splitk(x, ww, y, M, N, Kd, c[1], skws, **kw)
             torch.cuda.synchronize()
-            cands = [("v", v) for v in self.NT_CANDIDATES_SKINNY] + [("s", sp) for sp in self.SKINNY_SPLITS if Kd // 64 >= sp]
-            score = {c: float("inf") for c in cands}
-            for rnd in range(3):                     # interleaved rounds, best-of per candidate: these are 5-40 us kernels, one noisy
-                for c in cands:                      # sample would otherwise pin a bad choice for the life of the process
-                    if c[0] == "v":
-                        t = timed(lambda ww, v=c[1]: K.gemm_nt(x, ww, y, M, N, Kd, variant=v, **kw))
-                    else:
-                        t = timed(lambda ww, sp=c[1]: K.gemm_nt_splitk(x, ww, y, M, N, Kd, sp, skws, **kw))
-                    score[c] = min(score[c], t)
-            ch = min(cands, key=lambda c: score[c])
+            # three rounds: these are 5-40 us kernels, one noisy sample would otherwise pin a bad choice for the life of the process
+            ch = tuning.best_of(cands, launch, rounds=3, reps=max(12, len(wl)))
             K.gemm_nt(x, w, y, M, N, Kd, variant=1, **kw)        # leave y as computed from the caller's weight
             Engine._skinny_choice[key] = ch
             tuning.remember("sk", M, N, Kd, ch)
@@ -652,6 +644,46 @@ class Engine(object):
             ent = self._pk_cache[key] = (row_off, row_map, Mp)
         return ent[0], ent[1], ent[2]
 
+    def _check_regions(self, vis_feats, vis_pe):
+        model = self._model()
+        H, A, Nv = model.config.hidden_size, model.config.num_attention_heads, model.len_vis_input
+        if H != A * 64:
+            raise RuntimeError("vlp_amd: attention kernels need head_dim == 64 (hidden %d, heads %d)" % (H, A))
+        if vis_feats.shape[1] != Nv or vis_feats.shape[2] != 2048 or vis_pe.shape[2] != PE_DIM:
+            raise RuntimeError("vlp_amd: expected vis_feats [B,%d,2048] and vis_pe [B,%d,%d]" % (Nv, Nv, PE_DIM))
+
+    def _region_inputs(self, ws, vis_feats, vis_pe):
+        """Operands of the three region GEMMs.  Launches the fp16 cast of fp32 image features and returns (img, prep_pe): prep_pe() launches
+        the K-padded box / class encoding into ws["vpe_in"] and the K-padded copy of its weight into ws["wpe_pad"] (a training forward
+        runs it on its side stream)."""
+        B, Nv, H = vis_feats.shape[0], vis_feats.shape[1], self._model().config.hidden_size
+        Mv = B * Nv
+        vf = vis_feats.reshape(Mv, 2048)
+        if vf.dtype == torch.float32:
+            K.copy2d(vf.contiguous(), 2048, True, ws["img16"], 2048, Mv, 2048, 2048)
+            img = ws["img16"]
+        else:
+            img = vf.contiguous()
+
+        def prep_pe():
+            if isinstance(vis_pe, RawRegions):  # raw boxes + class probabilities -> K-padded encoding (seq2seq_loader.py:338-351)
+                vis_pe.check(B, Nv)
+                K.vis_pe_prep(vis_pe.bbox, vis_pe.cls_prob.reshape(Mv, PE_DIM - 6), ws["vpe_in"], B, Nv, PE_DIM - 6, PE_PAD)
+            else:
+                vp = vis_pe.reshape(Mv, PE_DIM).contiguous()
+                K.copy2d(vp, PE_DIM, vp.dtype == torch.float32, ws["vpe_in"], PE_PAD, Mv, PE_DIM, PE_PAD)
+            # parameters written by a pipelined optimizer step become readable chunk by chunk (wait_params is a no-op otherwise)
+            # (reads a parameter of the embeddings bucket: AFTER the wait, or a pipelined step would project with last step's weight)
+            self.wait_params(len(self.buckets) - 1, consume=False)      # region projections (this may run on the side stream)
+            K.copy2d(self.P("vis_pe_embed.0.weight"), PE_DIM, False, ws["wpe_pad"], PE_PAD, H, PE_DIM, PE_PAD)
+        return img, prep_pe
+
+    def _side_stream(self):
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+            self._side_done = [None, None]
+        return self._side
+
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, attention_mask, masked_pos, train, want_mlm, want_vqa,
                 vis_masked_pos=None, position_ids=None, dropout=True, dense=False):
         """Runs embeddings + encoder (+ heads' forward up to the logits).  Returns the _State.  vis_masked_pos ([B, Pm] int64, values
@@ -663,27 +695,18 @@ class Engine(object):
         cfg = model.config
         H, I, A, NL, Nv, V = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers, model.len_vis_input, cfg.vocab_size
         B, L = input_ids.shape
-        if H != A * 64:
-            raise RuntimeError("vlp_amd: attention kernels need head_dim == 64 (hidden %d, heads %d)" % (H, A))
-        if vis_feats.shape[1] != Nv or vis_feats.shape[2] != 2048 or vis_pe.shape[2] != PE_DIM:
-            raise RuntimeError("vlp_amd: expected vis_feats [B,%d,2048] and vis_pe [B,%d,%d]" % (Nv, Nv, PE_DIM))
-        raw_regions = isinstance(vis_pe, RawRegions)
+        self._check_regions(vis_feats, vis_pe)
         mask_spec = isinstance(attention_mask, MaskSpec)
         if L < Nv + 2:
             raise RuntimeError("vlp_amd: sequence length %d too short for %d regions" % (L, Nv))
         P = masked_pos.shape[1] if (want_mlm and masked_pos is not None and masked_pos.numel() > 0) else 0
         ws = self._workspace(B, L, P)
         self.gen += 1
-        st = _State()
-        st.gen, st.B, st.L, st.P, st.ws = self.gen, B, L, P, ws
-        st.mlm_smooth = None
-        st.pos_ids = position_ids
         p = cfg.hidden_dropout_prob if (train and dropout) else 0.0
         pa = cfg.attention_probs_dropout_prob if (train and dropout) else 0.0
-        st.p_drop = (p, pa)
         if train and (p > 0 or pa > 0):
             self.step_seed += 1
-        seed = st.seed = self.base_seed + self.step_seed
+        seed = self.base_seed + self.step_seed
         M, Mv = B * L, B * Nv
         # ---- padding-free layout (opt-in): row_off / row_map / M' from the mask's own kept lengths --------------------------------
         ro = rm = None
@@ -691,7 +714,6 @@ class Engine(object):
             lens = self._kept_lengths(attention_mask, masked_pos if P > 0 else None, B, L, Nv)
             if lens is not None and sum(lens) < M:
                 ro, rm, M = self._packing(lens, B, L)
-        st.pk = (ro, rm, M) if ro is not None else None
         self.last_packed_rows = M if ro is not None else None
 
         # ---- inputs -----------------------------------------------------------------------------
@@ -703,27 +725,13 @@ class Engine(object):
             st_vmp = vis_masked_pos.to(torch.long).contiguous()
             K.region_mask_build(st_vmp, pt["rmask"], B, Pm, Nv)
         self._pretext_on = pt is not None
-        st.pretext = (pt, st_vmp) if pt is not None else None
-        vf = vis_feats.reshape(Mv, 2048)
-        if vf.dtype == torch.float32:
-            K.copy2d(vf.contiguous(), 2048, True, ws["img16"], 2048, Mv, 2048, 2048)
-            img = ws["img16"]
-        else:
-            img = vf.contiguous()
+        img, prep_pe = self._region_inputs(ws, vis_feats, vis_pe)
+        st = _State()
+        st.gen, st.B, st.L, st.P, st.ws, st.has_mlm = self.gen, B, L, P, ws, P > 0
+        st.seed, st.p_drop, st.pos_ids = seed, (p, pa), position_ids
         st.batch = (img, input_ids.contiguous(), token_type_ids.contiguous(), masked_pos)
-
-        def prep_pe():
-            # K-padded box / class encoding (operand of the third region GEMM) and the K-padded copy of its weight
-            if raw_regions:                     # raw boxes + class probabilities -> K-padded encoding (seq2seq_loader.py:338-351)
-                vis_pe.check(B, Nv)
-                K.vis_pe_prep(vis_pe.bbox, vis_pe.cls_prob.reshape(Mv, PE_DIM - 6), ws["vpe_in"], B, Nv, PE_DIM - 6, PE_PAD)
-            else:
-                vp = vis_pe.reshape(Mv, PE_DIM).contiguous()
-                K.copy2d(vp, PE_DIM, vp.dtype == torch.float32, ws["vpe_in"], PE_PAD, Mv, PE_DIM, PE_PAD)
-            # parameters written by a pipelined optimizer step become readable chunk by chunk (wait_params is a no-op otherwise)
-            # (reads a parameter of the embeddings bucket: AFTER the wait, or a pipelined step would project with last step's weight)
-            self.wait_params(len(self.buckets) - 1, consume=False)      # region projections (this may run on the side stream)
-            K.copy2d(self.P("vis_pe_embed.0.weight"), PE_DIM, False, ws["wpe_pad"], PE_PAD, H, PE_DIM, PE_PAD)
+        st.pk = (ro, rm, M) if ro is not None else None
+        st.pretext = (pt, st_vmp) if pt is not None else None
 
         def prep_mask(am):
             if mask_spec:                       # per-sample lengths -> packed masks on the device (seq2seq_loader.py:292-301)
@@ -745,21 +753,18 @@ class Engine(object):
         # projections at once and waits for (1) / (2) where it first reads them.
         self._shadow_ev = None
         pe_ev = mask_ev = None
-        if (train or torch.is_grad_enabled()) and self.WGRAD_SIDE_STREAM and self.SHADOW_ON_SIDE:
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-                self._side_done = [None, None]
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
+        if (train or torch.is_grad_enabled()) and self.WGRAD_SIDE_STREAM:
+            side = self._side_stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
                 prep_pe()
                 pe_ev = torch.cuda.Event()
-                pe_ev.record(self._side)
+                pe_ev.record(side)
                 prep_mask(attention_mask)
                 mask_ev = torch.cuda.Event()
-                mask_ev.record(self._side)
+                mask_ev.record(side)
                 if self._params_done is not None:
-                    self._side.wait_event(self._params_done)        # the transposes read every weight matrix
+                    side.wait_event(self._params_done)        # the transposes read every weight matrix
                 if self._param_works is not None:
                     # sharded optimizer step: the parameters arrive by per-bucket all-gathers that may still be in flight; the
                     # transposes read EVERY weight matrix, so this stream waits for all of them (the main stream keeps waiting per
@@ -769,7 +774,7 @@ class Engine(object):
                             w.wait()
                 self._refresh_shadows()
                 self._shadow_ev = torch.cuda.Event()
-                self._shadow_ev.record(self._side)
+                self._shadow_ev.record(side)
         else:
             prep_mask(attention_mask)
             prep_pe()
@@ -818,7 +823,6 @@ class Engine(object):
             x = a["x2"]
         # ---- heads ------------------------------------------------------------------------------------
         self.wait_params(0)
-        st.has_mlm = P > 0
         if P > 0:
             C = "cls.predictions."
             R = B * P
@@ -855,7 +859,6 @@ class Engine(object):
         st.task_labels = labels.contiguous()
         crit = getattr(model, "crit_mask_lm_smoothed", None)
         if crit is None:
-            st.mlm_smooth = None
             K.mlm_loss_fwd(ws["logits"], ws["Vp"], st.task_labels, weights.to(torch.long).contiguous(), ws["loss"], ws["lse_ce"], ws["coef"],
                            ws["row_loss"], st.B, st.P, V, drop_worst_ratio=float(drop_worst_ratio))
         else:
@@ -927,7 +930,7 @@ class Engine(object):
                   mask_static=i64(R, Lcap, Lcap), tt_steps=i64(Lcap, R, 2), pid_steps=i64(Lcap, R, 2),
                   out_ids=i64(B, Lcap), out_val=f(B, Lcap), plans={}, calls=0, plan_stream=None,
                   slab=f(self.DEC_SPLITS, R * 2, H),      # fp32 split-K partial sums of the token-step out-projection / FFN-down (vlp_dec_gemm -> vlp_dec_reduce_ln)
-                  sk_ws=torch.empty(K.gemm_nt_splitk_workspace_bytes(min(M, 1024), max(I, 3 * H), max(self.SKINNY_SPLITS)), device=dev,
+                  sk_ws=torch.empty(K.gemm_nt_splitk_workspace_bytes(min(M, 1024), max(I, 3 * H), max(tuning.SKINNY_SPLITS)), device=dev,
                                     dtype=torch.uint8))
         if Kb > 1:
             # beams: two caches per layer (select_beam_items permutes rows: gather from one into the other, then swap)
@@ -938,15 +941,10 @@ class Engine(object):
         return ws
 
     def _decode_check(self, vis_feats, vis_pe, input_ids, token_type_ids, attention_mask):
-        model = self._model()
-        cfg = model.config
-        H, A, Nv = cfg.hidden_size, cfg.num_attention_heads, model.len_vis_input
+        Nv = self._model().len_vis_input
         B, in_len = input_ids.shape
         out_len = token_type_ids.shape[1]
-        if H != A * 64:
-            raise RuntimeError("vlp_amd: attention kernels need head_dim == 64 (hidden %d, heads %d)" % (H, A))
-        if vis_feats.shape[1] != Nv or vis_feats.shape[2] != 2048 or vis_pe.shape[2] != PE_DIM:
-            raise RuntimeError("vlp_amd: expected vis_feats [B,%d,2048] and vis_pe [B,%d,%d]" % (Nv, Nv, PE_DIM))
+        self._check_regions(vis_feats, vis_pe)
         if in_len < Nv + 2 or out_len <= in_len or out_len > 256:
             raise RuntimeError("vlp_amd: decode needs %d <= input length < output length <= 256 (got %d, %d)" % (Nv + 2, in_len, out_len))
         if attention_mask.dim() != 3 or attention_mask.shape[1] < out_len or attention_mask.shape[2] < out_len:
@@ -958,19 +956,8 @@ class Engine(object):
         model = self._model()
         H, Nv = model.config.hidden_size, model.len_vis_input
         Mv = vis_feats.shape[0] * Nv
-        vf = vis_feats.reshape(Mv, 2048)
-        if vf.dtype == torch.float32:
-            K.copy2d(vf.contiguous(), 2048, True, ws["img16"], 2048, Mv, 2048, 2048)
-            img = ws["img16"]
-        else:
-            img = vf.contiguous()
-        if isinstance(vis_pe, RawRegions):         # the packed loader's raw boxes + class probabilities (seq2seq_loader.py:338-351)
-            vis_pe.check(vis_feats.shape[0], Nv)
-            K.vis_pe_prep(vis_pe.bbox, vis_pe.cls_prob.reshape(Mv, PE_DIM - 6), ws["vpe_in"], vis_feats.shape[0], Nv, PE_DIM - 6, PE_PAD)
-        else:
-            vp = vis_pe.reshape(Mv, PE_DIM).contiguous()
-            K.copy2d(vp, PE_DIM, vp.dtype == torch.float32, ws["vpe_in"], PE_PAD, Mv, PE_DIM, PE_PAD)
-        K.copy2d(self.P("vis_pe_embed.0.weight"), PE_DIM, False, ws["wpe_pad"], PE_PAD, H, PE_DIM, PE_PAD)
+        img, prep_pe = self._region_inputs(ws, vis_feats, vis_pe)
+        prep_pe()           # (the decoders have waited for every parameter already: its wait_params orders nothing new)
         self._nt(img, self.P("vis_embed.0.weight"), ws["h1"], Mv, 2048, 2048, bias=self.P("vis_embed.0.bias"), act=K.ACT_RELU)
         self._nt(ws["h1"], self.P("vis_embed.2.weight"), ws["vis_h"], Mv, H, 2048, bias=self.P("vis_embed.2.bias"), act=K.ACT_RELU)
         self._nt(ws["vpe_in"], ws["wpe_pad"], ws["vispe_h"], Mv, H, PE_PAD, bias=self.P("vis_pe_embed.0.bias"), act=K.ACT_RELU)
@@ -980,12 +967,16 @@ class Engine(object):
     # slices, reduce + LayerNorm).  VLP_DECODE_FUSED=0: the round-2 path (split-K skinny GEMMs, separate reduces / kv_append / LayerNorms).
     DECODE_FUSED = os.environ.get("VLP_DECODE_FUSED", "1") == "1"
     DEC_SPLITS = 4
-    # VLP_DECODE_LN_PROLOGUE=1: the attention-output LayerNorm as a PROLOGUE of the FFN-up launch (6 launches per layer).  Built, tested and measured in
-    # round 6, NOT the default: every one of the 192 workgroups of the FFN-up grid normalises its 64 rows itself (16 rows per wave, ~25 VALU ops per
-    # element on one wave per SIMD): the launch goes 6.4 -> 15.5 us, more than the 4.8 us LayerNorm launch + boundary it removes
-    # (0.645 vs 0.559 ms per token step, profiles/r06_decode_ln_prologue_ab.txt).
-    DEC_LN_PROLOGUE = os.environ.get("VLP_DECODE_LN_PROLOGUE", "0") == "1"
-    DEC_VOCAB = os.environ.get("VLP_DECODE_VOCAB_BURST", "1") == "1"      # the tied vocabulary projection of a token step on vlp_dec_gemm too
+
+    def _decode_attn(self, ws, kv, i, maskb, R, T, Lk, Lcap, prefix):
+        """Attention of the T new rows of R sequences over layer i's cache `kv` (and, under beam search, the per-sample prefix cache)."""
+        cfg = self._model().config
+        H, A = cfg.hidden_size, cfg.num_attention_heads
+        kw = {}
+        if prefix is not None:
+            pk = prefix[0][i]
+            kw = dict(k_prefix=pk, v_prefix=pk[:, :, H:], prefix_rows=Lcap, n_prefix=prefix[1], beams=prefix[2])
+        K.attn_decode(ws["qkv"], 3 * H, T, kv, kv[:, :, H:], 2 * H, Lcap, maskb, ws["ctx"], R, T, Lk, A, 1.0 / math.sqrt(H // A), **kw)
 
     def _decode_layers_fused(self, ws, caches, Lcap, x, alt, maskb, R, T, st, prefix):
         """The 12 BertLayers of a token step (M = R * T <= a few hundred rows) on vlp_dec_gemm / vlp_dec_reduce_ln.  Same arithmetic and
@@ -993,8 +984,7 @@ class Engine(object):
         summation order of the contractions differs."""
         model = self._model()
         cfg = model.config
-        H, I, A, NL = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
-        scale = 1.0 / math.sqrt(H // A)
+        H, I, NL = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
         Lk, M, S = st + T, R * T, self.DEC_SPLITS
         slab = ws["slab"].view(-1)[:S * M * H].view(S, M, H)        # slab s holds rows [s * M, (s + 1) * M)
         for i in range(NL):
@@ -1002,25 +992,45 @@ class Engine(object):
             kv = caches[i]
             K.dec_gemm(x, self.P(Ln + "attention.self.query.weight"), M, 3 * H, H, y=ws["qkv"], bias=self.P(Ln + "attention.self.query.bias"),
                        kv_cache=kv, kv_col0=H, kv_Lcap=Lcap, kv_T=T, kv_start=st)
-            if prefix is None:
-                K.attn_decode(ws["qkv"], 3 * H, T, kv, kv[:, :, H:], 2 * H, Lcap, maskb, ws["ctx"], R, T, Lk, A, scale)
-            else:
-                pk = prefix[0][i]
-                K.attn_decode(ws["qkv"], 3 * H, T, kv, kv[:, :, H:], 2 * H, Lcap, maskb, ws["ctx"], R, T, Lk, A, scale, k_prefix=pk,
-                              v_prefix=pk[:, :, H:], prefix_rows=Lcap, n_prefix=prefix[1], beams=prefix[2])
-            if self.DEC_LN_PROLOGUE:
-                # out-projection + bias + residual -> fp16 pre-LayerNorm rows; FFN-up normalises them in its prologue (and writes x1 for the next residual)
-                K.dec_gemm(ws["ctx"], self.P(Ln + "attention.output.dense.weight"), M, H, H, y=ws["pre"], bias=self.P(Ln + "attention.output.dense.bias"), residual=x)
-                K.dec_gemm(ws["pre"], self.P(Ln + "intermediate.dense.weight"), M, I, H, y=ws["g"], bias=self.P(Ln + "intermediate.dense.bias"), act=K.ACT_GELU,
-                           ln_gamma=self.P(Ln + "attention.output.LayerNorm.weight"), ln_beta=self.P(Ln + "attention.output.LayerNorm.bias"), ln_out=ws["x1"])
-            else:
-                K.dec_gemm(ws["ctx"], self.P(Ln + "attention.output.dense.weight"), M, H, H, slab=slab, splits=S)
-                K.dec_reduce_ln(slab, S, self.P(Ln + "attention.output.dense.bias"), x, self.P(Ln + "attention.output.LayerNorm.weight"),
-                                self.P(Ln + "attention.output.LayerNorm.bias"), ws["x1"], M, H)
-                K.dec_gemm(ws["x1"], self.P(Ln + "intermediate.dense.weight"), M, I, H, y=ws["g"], bias=self.P(Ln + "intermediate.dense.bias"), act=K.ACT_GELU)
+            self._decode_attn(ws, kv, i, maskb, R, T, Lk, Lcap, prefix)
+            # (this LayerNorm as a prologue of the FFN-up launch, which vlp_dec_gemm can do, measured slower and is not used: 0.645 against
+            # 0.559 ms per token step, profiles/r06_decode_ln_prologue_ab.txt)
+            K.dec_gemm(ws["ctx"], self.P(Ln + "attention.output.dense.weight"), M, H, H, slab=slab, splits=S)
+            K.dec_reduce_ln(slab, S, self.P(Ln + "attention.output.dense.bias"), x, self.P(Ln + "attention.output.LayerNorm.weight"),
+                            self.P(Ln + "attention.output.LayerNorm.bias"), ws["x1"], M, H)
+            K.dec_gemm(ws["x1"], self.P(Ln + "intermediate.dense.weight"), M, I, H, y=ws["g"], bias=self.P(Ln + "intermediate.dense.bias"), act=K.ACT_GELU)
             K.dec_gemm(ws["g"], self.P(Ln + "output.dense.weight"), M, H, I, slab=slab, splits=S)
             K.dec_reduce_ln(slab, S, self.P(Ln + "output.dense.bias"), ws["x1"], self.P(Ln + "output.LayerNorm.weight"),
                             self.P(Ln + "output.LayerNorm.bias"), alt, M, H)
+            x, alt = alt, x
+        return x
+
+    def _decode_layers_unfused(self, ws, caches, Lcap, x, alt, maskb, R, T, st, prefix):
+        """The same layers on the round-2 path (split-K skinny GEMMs, separate kv_append / LayerNorm launches): the first step of a decode
+        call and every shape the fused kernels do not take."""
+        cfg = self._model().config
+        H, I, NL = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+        Lk, M = st + T, R * T
+
+        def same_in_all_layers(suffix):
+            return lambda: [self.P("bert.encoder.layer.%d.%s" % (j, suffix)) for j in range(NL)]
+
+        def nt(xin, Ln, name, y, N, Kd, **kw):
+            self._nt_skinny(xin, self.P(Ln + name + ".weight"), y, M, N, Kd, ws["sk_ws"], tune_ws=same_in_all_layers(name + ".weight"),
+                            bias=self.P(Ln + name + ".bias"), **kw)
+
+        for i in range(NL):
+            Ln = "bert.encoder.layer.%d." % i
+            kv = caches[i]
+            nt(x, Ln, "attention.self.query", ws["qkv"], 3 * H, H)
+            K.kv_append(ws["qkv"], 3 * H, kv, Lcap, R, T, st, H)
+            self._decode_attn(ws, kv, i, maskb, R, T, Lk, Lcap, prefix)
+            nt(ws["ctx"], Ln, "attention.output.dense", ws["pre"], H, H, residual=x)
+            K.layernorm_fwd(ws["pre"], self.P(Ln + "attention.output.LayerNorm.weight"), self.P(Ln + "attention.output.LayerNorm.bias"),
+                            ws["x1"], M, H)
+            nt(ws["x1"], Ln, "intermediate.dense", ws["g"], I, H, act=K.ACT_GELU)
+            nt(ws["g"], Ln, "output.dense", ws["pre"], H, I, residual=ws["x1"])
+            K.layernorm_fwd(ws["pre"], self.P(Ln + "output.LayerNorm.weight"), self.P(Ln + "output.LayerNorm.bias"), alt, M, H)
             x, alt = alt, x
         return x
 
@@ -1032,9 +1042,8 @@ class Engine(object):
         the generated positions of every beam."""
         model = self._model()
         cfg = model.config
-        H, I, A, NL, Nv, V = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers, model.len_vis_input, cfg.vocab_size
+        H, I, Nv, V = cfg.hidden_size, cfg.intermediate_size, model.len_vis_input, cfg.vocab_size
         E, C = "bert.embeddings.", "cls.predictions."
-        scale = 1.0 / math.sqrt(H // A)
         Lk = st + T
         Lkp = _ru(Lk, 32)
         M = R * T
@@ -1045,32 +1054,10 @@ class Engine(object):
                     position_ids=pid)
         x, alt = ws["xa"], ws["xb"]
         K.layernorm_fwd(ws["emb_pre"], self.P(E + "LayerNorm.weight"), self.P(E + "LayerNorm.bias"), x, M, H)
-        def same_in_all_layers(suffix):
-            return lambda: [self.P("bert.encoder.layer.%d.%s" % (j, suffix)) for j in range(NL)]
         fused = (self.DECODE_FUSED and not first and M <= 1024 and H % 256 == 0 and H <= 768 and I % (64 * self.DEC_SPLITS) == 0 and
                  I // self.DEC_SPLITS <= 768 and H % (64 * self.DEC_SPLITS) == 0)
-        if fused:
-            x = self._decode_layers_fused(ws, caches, Lcap, x, alt, maskb, R, T, st, prefix)
-        for i in range(0 if not fused else NL, NL):
-            Ln = "bert.encoder.layer.%d." % i
-            kv = caches[i]
-            self._nt_skinny(x, self.P(Ln + "attention.self.query.weight"), ws["qkv"], M, 3 * H, H, ws["sk_ws"], tune_ws=same_in_all_layers("attention.self.query.weight"), bias=self.P(Ln + "attention.self.query.bias"))
-            K.kv_append(ws["qkv"], 3 * H, kv, Lcap, R, T, st, H)
-            if prefix is None:
-                K.attn_decode(ws["qkv"], 3 * H, T, kv, kv[:, :, H:], 2 * H, Lcap, maskb, ws["ctx"], R, T, Lk, A, scale)
-            else:
-                pk = prefix[0][i]
-                K.attn_decode(ws["qkv"], 3 * H, T, kv, kv[:, :, H:], 2 * H, Lcap, maskb, ws["ctx"], R, T, Lk, A, scale, k_prefix=pk,
-                              v_prefix=pk[:, :, H:], prefix_rows=Lcap, n_prefix=prefix[1], beams=prefix[2])
-            self._nt_skinny(ws["ctx"], self.P(Ln + "attention.output.dense.weight"), ws["pre"], M, H, H, ws["sk_ws"], tune_ws=same_in_all_layers("attention.output.dense.weight"), bias=self.P(Ln + "attention.output.dense.bias"),
-                     residual=x)
-            K.layernorm_fwd(ws["pre"], self.P(Ln + "attention.output.LayerNorm.weight"), self.P(Ln + "attention.output.LayerNorm.bias"),
-                            ws["x1"], M, H)
-            self._nt_skinny(ws["x1"], self.P(Ln + "intermediate.dense.weight"), ws["g"], M, I, H, ws["sk_ws"], tune_ws=same_in_all_layers("intermediate.dense.weight"), bias=self.P(Ln + "intermediate.dense.bias"),
-                     act=K.ACT_GELU)
-            self._nt_skinny(ws["g"], self.P(Ln + "output.dense.weight"), ws["pre"], M, H, I, ws["sk_ws"], tune_ws=same_in_all_layers("output.dense.weight"), bias=self.P(Ln + "output.dense.bias"), residual=ws["x1"])
-            K.layernorm_fwd(ws["pre"], self.P(Ln + "output.LayerNorm.weight"), self.P(Ln + "output.LayerNorm.bias"), alt, M, H)
-            x, alt = alt, x
+        layers = self._decode_layers_fused if fused else self._decode_layers_unfused
+        x = layers(ws, caches, Lcap, x, alt, maskb, R, T, st, prefix)
         # ---- LM head on the [MASK] slot (:1226-1228 / :1293-1296) ----------------------------------
         if fused:
             # the [MASK] slot is the LAST of the T new rows of every sequence: a strided view of x (row pitch T * H), no gather launch
@@ -1080,7 +1067,7 @@ class Engine(object):
             K.gather_rows(x, H, ws["last_first"] if first else ws["last_step"], ws["sel"], H, R, 1, T, H)
             self._nt(ws["sel"], self.P(C + "transform.dense.weight"), ws["tg"], R, H, H, bias=self.P(C + "transform.dense.bias"), act=K.ACT_GELU)
         K.layernorm_fwd(ws["tg"], self.P(C + "transform.LayerNorm.weight"), self.P(C + "transform.LayerNorm.bias"), ws["tln"], R, H)
-        if fused and self.DEC_VOCAB:
+        if fused:
             K.dec_gemm(ws["tln"], self.P("bert.embeddings.word_embeddings.weight"), R, V, H, y=ws["logits"], bias=self.P(C + "bias"))
         else:
             self._nt(ws["tln"], self.P("bert.embeddings.word_embeddings.weight"), ws["logits"], R, V, H, bias=self.P(C + "bias"), ldy=ws["Vp"])
@@ -1306,25 +1293,13 @@ class Engine(object):
         if not tuning.AUTOTUNE:
             sp = Engine._tn_choice[key] = tuning.tn_choice(M, N, Kd)
             return sp
-        best, best_t = (self.GEMM_TN_VARIANT, 0), float("inf")
+        best = (self.GEMM_TN_VARIANT, 0)
         if M >= 1024:
+            cands = [(var, sp) for var in self.TN_VARIANT_CANDIDATES for sp in tuning.TN_SPLIT_CANDIDATES if not (sp > 1 and M // sp < 128)]
             torch.cuda.synchronize()
             scratch = torch.empty(N, Kd, device=c.device, dtype=torch.float16)   # never time into the live gradient buffer
-            for rnd in range(2):
-                for var in self.TN_VARIANT_CANDIDATES:
-                    for cand in self.TN_SPLIT_CANDIDATES:
-                        if cand > 1 and M // cand < 128:
-                            continue
-                        K.gemm_tn(a, b, scratch, M, N, Kd, beta=0, workspace=ws["tn_ws"], variant=var, splits=cand)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for _ in range(3):
-                            K.gemm_tn(a, b, scratch, M, N, Kd, beta=0, workspace=ws["tn_ws"], variant=var, splits=cand)
-                        e1.record()
-                        e1.synchronize()
-                        t = e0.elapsed_time(e1)
-                        if t < best_t:
-                            best, best_t = (var, cand), t
+            best = tuning.best_of(cands, lambda vs, i: K.gemm_tn(a, b, scratch, M, N, Kd, beta=0, workspace=ws["tn_ws"], variant=vs[0], splits=vs[1]),
+                                  rounds=2, reps=3)
         Engine._tn_choice[key] = best
         tuning.remember("tn", M, N, Kd, best)
         return best
@@ -1362,7 +1337,7 @@ class Engine(object):
                                "accumulated over several backward passes (--gradient_accumulation_steps > 1); use allreduce or rs_ag")
         img, input_ids, token_type_ids, masked_pos = st.batch
         self.wait_params()           # the optimizer stream has read the previous gradients and written every parameter
-        if getattr(self, "_shadow_ev", None) is not None:
+        if self._shadow_ev is not None:
             torch.cuda.current_stream().wait_event(self._shadow_ev)     # transposed during the forward (side stream)
             self._shadow_ev = None
         else:
@@ -1379,12 +1354,7 @@ class Engine(object):
 
         main = torch.cuda.current_stream()
         use_side = self.WGRAD_SIDE_STREAM
-        if use_side and self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-            self._side_done = [None, None]
-        if use_side and getattr(self, "_side_done", None) is None:
-            self._side_done = [None, None]
-        side = self._side if use_side else None
+        side = self._side_stream() if use_side else None
 
         def on_side(fn):
             if not use_side:
@@ -1401,7 +1371,7 @@ class Engine(object):
         # ---- heads ------------------------------------------------------------------------------------
         if task == "vqa2":
             NA, NAp = model.num_answers, ws["NAp"]
-            K.bce_loss_bwd(ws["vq_logits"], NAp, st_labels(st), st_labels(st).stride(0), B, NA, gscale, ws["vq_dlogits"], NAp)
+            K.bce_loss_bwd(ws["vq_logits"], NAp, st.task_labels, st.task_labels.stride(0), B, NA, gscale, ws["vq_dlogits"], NAp)
             self._tn(ws["vq_dlogits"], ws["vq_a1"], self.G("ans_classifier.2.weight"), B, NA, 2 * H, ws, beta, bias=self.G("ans_classifier.2.bias"))
             self._nt(ws["vq_dlogits"], sh["a2T"], ws["vq_dz1"], B, 2 * H, NAp, mul_src=ws["vq_a1"], mul_mode=K.MUL_RELU_MASK)
             self._tn(ws["vq_dz1"], ws["vq_e"], self.G("ans_classifier.0.weight"), B, 2 * H, H, ws, beta, bias=self.G("ans_classifier.0.bias"))
@@ -1420,11 +1390,11 @@ class Engine(object):
             if task == "logprob":
                 if g_rows is None or g_rows.numel() != R:
                     raise RuntimeError("vlp_amd: backward(task='logprob') needs g_rows with %d elements" % R)
-                K.token_logprob_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V)
+                K.token_logprob_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V)
             elif st.mlm_smooth is None:
-                K.mlm_loss_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
+                K.mlm_loss_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
             else:
-                K.mlm_loss_ls_bwd(ws["logits"], Vp, st_labels(st), ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V, *st.mlm_smooth)
+                K.mlm_loss_ls_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V, *st.mlm_smooth)
             # tied decoder (modeling.py:445-448): dE[V,H] = dlogits^T . t ; the embedding scatter adds to it later
             head_wgrads.append(lambda: self._tn(ws["dlogits"], ws["tln"], self.G(E + "word_embeddings.weight"), R, V, H, ws, beta, bias=self.G(C + "bias")))
             # dgrad through the tied decoder: dt[R,H] = dlogits[R,V] . E[V,H].  As an NT GEMM this is 12 workgroups walking
@@ -1452,7 +1422,7 @@ class Engine(object):
             K.transpose(self.P("bert.pooler.dense.weight"), H, ptw["pT"], H, H, H, H)
             self._nt(ptw["dpool"], ptw["pT"], ptw["dsel0"], B, H, H)
             K.scatter_add_rows(ptw["dsel0"], H, ptw["pos0"], dx, H, B, 1, L, H, row_off=ro)
-        elif beta == 0 and getattr(self, "_pooler_dirty", False):
+        elif beta == 0 and self._pooler_dirty:
             self.G("bert.pooler.dense.weight").zero_()           # a previous pretext step left gradients there; unused now
             self.G("bert.pooler.dense.bias").zero_()
         self._pooler_dirty = pt is not None
@@ -1461,10 +1431,7 @@ class Engine(object):
             for fn in head_wgrads:
                 fn()
             self._bucket_done(0)
-        if self.TAIL_ON_SIDE:
-            on_side(head_tail)      # (the side stream is ordered behind everything the main stream has issued so far)
-        else:
-            head_tail()
+        on_side(head_tail)          # (the side stream is ordered behind everything the main stream has issued so far)
 
         # ---- encoder layers, last to first ----------------------------------------------------------------
         # The dgrad chain (LN-bwd -> dgrad GEMMs -> attention-bwd) is the critical path; the four weight-gradient GEMMs of a
@@ -1474,12 +1441,13 @@ class Engine(object):
         dctx = ws["dctx"]
         scale = 1.0 / math.sqrt(H // A)
         slot_bytes = ws["ln_slot_bytes"]
-        defer = self.LN_DEFER
 
         def ln_slot(k):
             return ws["ln_slots"][k * slot_bytes:(k + 1) * slot_bytes]
 
-        grouped = self.GROUPED_WGRAD and M >= 2048       # enough rows for a long contraction per workgroup; tiny batches keep split-M
+        # one vlp_gemm_tn_grouped launch per layer instead of 4 split-M wgrads + 4 reduces where there are enough rows for a long contraction
+        # per workgroup; tiny batches keep split-M
+        grouped = M >= 2048
         for i in reversed(range(NL)):
             Ln = "bert.encoder.layer.%d." % i
             a = ws["layers"][i]
@@ -1492,7 +1460,7 @@ class Engine(object):
             dpre = ds["dpre2"]
             K.layernorm_bwd(dx, a["pre2"], self.P(Ln + "output.LayerNorm.weight"), a["st2"][0], a["st2"][1], dpre,
                             self.G(Ln + "output.LayerNorm.weight"), self.G(Ln + "output.LayerNorm.bias"), M, H, ln_slot(2 * i + 1), beta=beta,
-                            dx_drop=ds["dpre2_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 3), defer_reduce=defer, row_map=rm)
+                            dx_drop=ds["dpre2_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 3), defer_reduce=True, row_map=rm)
             dy2 = ds["dpre2_d"] if p > 0 else dpre
             if not grouped:
                 on_side(lambda: self._tn(dy2, a["g"], self.G(Ln + "output.dense.weight"), M, H, I, ws, beta, bias=self.G(Ln + "output.dense.bias")))
@@ -1506,7 +1474,7 @@ class Engine(object):
             dpre = ds["dpre1"]
             K.layernorm_bwd(dx, a["pre1"], self.P(Ln + "attention.output.LayerNorm.weight"), a["st1"][0], a["st1"][1], dpre,
                             self.G(Ln + "attention.output.LayerNorm.weight"), self.G(Ln + "attention.output.LayerNorm.bias"), M, H, ln_slot(2 * i),
-                            beta=beta, dx_drop=ds["dpre1_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 2), defer_reduce=defer, row_map=rm)
+                            beta=beta, dx_drop=ds["dpre1_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 2), defer_reduce=True, row_map=rm)
             dy1 = ds["dpre1_d"] if p > 0 else dpre
             if not grouped:
                 on_side(lambda: self._tn(dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), M, H, H, ws, beta,
@@ -1536,10 +1504,10 @@ class Engine(object):
                     self._side_done[i & 1] = ev
             on_side(last_wgrad)
             self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre)
-        if use_side and not (grouped and self.TAIL_ON_SIDE):
+        if use_side and not grouped:
             main.wait_stream(side)          # all layer wgrads (and their bucket hand-offs) precede the rest of backward (split-M wgrads share tn_ws)
             self._side_busy = False
-        # (grouped wgrads + TAIL_ON_SIDE: the main stream does NOT wait here -- layer 0's weight gradients (170 us, issued a moment ago) and the
+        # (grouped wgrads: the main stream does NOT wait here -- layer 0's weight gradients (170 us, issued a moment ago) and the
         # embedding tables run on the side stream underneath the embedding / region-projection backward below, which touches none of their
         # operands; the streams join once, at the end of backward)
         dpre = ws["dpre"]
@@ -1547,7 +1515,7 @@ class Engine(object):
         # ---- embeddings -------------------------------------------------------------------------------------
         K.layernorm_bwd(dx, ws["emb_pre"], self.P(E + "LayerNorm.weight"), ws["stat0"][0], ws["stat0"][1], dpre,
                         self.G(E + "LayerNorm.weight"), self.G(E + "LayerNorm.bias"), M, H, ln_slot(2 * NL), beta=beta, dy_drop=(p, seed, 1000),
-                        defer_reduce=defer, row_map=rm)
+                        defer_reduce=True, row_map=rm)
         if rm is not None:
             # the embedding backward sums over (batch, position) in the dense [B, L] geometry (position table: a column of the batch;
             # word table: id chains in row order): hand it the dense gradient -- exact zeros on the dropped positions, as in the dense run
@@ -1556,34 +1524,29 @@ class Engine(object):
             K.rows_unpack(dpre, rm, M, dense, H)
             dpre = dense
 
+        def embed_bwd(parts):
+            """parts = 1: the region rows (d_vis_h / d_vispe_h; they do not depend on position ids), 2: the three embedding tables."""
+            args = (ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"), self.G(E + "position_embeddings.weight"),
+                    self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"], ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size)
+            kw = dict(drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002, region_mask=pt[0]["rmask"] if pt is not None else None, parts=parts)
+            if parts == 2 and st.pos_ids is not None:       # explicit position ids (score_samples): the position table follows them
+                K.embed_bwd_pos(dpre, input_ids, token_type_ids, st.pos_ids, *args, **kw)
+            else:
+                K.embed_bwd(dpre, input_ids, token_type_ids, *args, **kw)
+
         def tables_and_ln_params():
             # the tail of backward that nothing on the main stream waits for: dgamma / dbeta of the 2 * layers + 1 LayerNorms (one launch,
             # slot order = table order) and the three embedding tables (five launches); their gradient slice is announced from here
-            if defer:
-                K.layernorm_bwd_reduce_batched(ws["ln_slots"], self._ln_table(), 2 * NL + 1, M, H, beta=beta)
-            if st.pos_ids is not None:          # explicit position ids (score_samples): the position table follows them
-                K.embed_bwd_pos(dpre, input_ids, token_type_ids, st.pos_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
-                                self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
-                                ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
-                                region_mask=pt[0]["rmask"] if pt is not None else None, parts=2)
-            else:
-                K.embed_bwd(dpre, input_ids, token_type_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
-                            self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
-                            ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
-                            region_mask=pt[0]["rmask"] if pt is not None else None, parts=2)
+            K.layernorm_bwd_reduce_batched(ws["ln_slots"], self._ln_table(), 2 * NL + 1, M, H, beta=beta)
+            embed_bwd(2)
             self._bucket_done(NL + 1)           # position / type / word embedding tables (tied decoder wgrad + embedding backward) are final
 
         # region rows first (the region-projection dgrad / wgrads below wait for d_vis_h / d_vispe_h only); the tables and the LayerNorm
         # parameter sums run on the side stream underneath them (round 5: six small launches, ~140 us, off the critical path)
-        K.embed_bwd(dpre, input_ids, token_type_ids, ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"),
-                    self.G(E + "position_embeddings.weight"), self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"],
-                    ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002,
-                    region_mask=pt[0]["rmask"] if pt is not None else None, parts=1)
-        if use_side and self.TAIL_ON_SIDE:
+        embed_bwd(1)
+        if use_side:
             self._side_busy = True
-            on_side(tables_and_ln_params)
-        else:
-            tables_and_ln_params()
+        on_side(tables_and_ln_params)
         # vis_pe_embed: Linear(1607, H) -- wgrad into the padded shadow, then crop-accumulate
         # vis_embed: Linear(2048,2048)+ReLU -> Linear(2048,H)+ReLU+Dropout
         self._nt(ws["d_vis_h"], sh["v2T"], ws["dz1v"], Mv, 2048, H, mul_src=ws["h1"], mul_mode=K.MUL_RELU_MASK)
@@ -1613,6 +1576,3 @@ class Engine(object):
         if self.post_backward_hook is not None:
             self.post_backward_hook()
 
-
-def st_labels(st):
-    return st.task_labels

@@ -20,7 +20,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 TABLE_PATH = os.environ.get("VLP_TUNE_TABLE") or os.path.join(_HERE, "tuned_gfx950.json")
 AUTOTUNE = os.environ.get("VLP_AUTOTUNE", "0") == "1"
 
-SKINNY_SPLITS = (2, 3, 4, 6, 8, 12, 16)
+SKINNY_SPLITS = (2, 3, 4, 6, 8, 12, 16)      # split-K factors of the decoder's skinny GEMMs (vlp_gemm_nt_splitk)
+# split-M factor of vlp_gemm_tn: the wgrad outputs are small (36..144 tiles of 128x128) and the contraction long (M = 10 688), so the
+# workgroup count tiles*splits has to land just under a multiple of the 256 CUs x 2 resident workgroups: 3 (432 workgroups)
+# beats 4 (576) by 25 % on the FFN wgrads, 14 beats 8 on the 768x768 ones (microbench, profiles/r01_tn_split_sweep.json)
 TN_SPLIT_CANDIDATES = (0, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16)
 
 _table = None
@@ -62,6 +65,26 @@ def dump(path):
     with open(path, "w") as f:
         json.dump(cur, f, indent=0, sort_keys=True)
     return cur
+
+
+def best_of(candidates, launch, rounds, reps):
+    """The timing search of VLP_AUTOTUNE=1: the fastest of `candidates` (hashable; all compute the same thing).  `launch(cand, i)` issues one
+    launch of a candidate; i is the repetition index, for callers that rotate operands.  A candidate is warmed once, then `reps` launches are
+    bracketed by two events; `rounds` interleaved rounds, best-of per candidate: robust against clock / neighbour noise.  The caller
+    synchronises the device first."""
+    import torch
+    score = {c: float("inf") for c in candidates}
+    for _ in range(rounds):
+        for c in candidates:
+            launch(c, 0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(reps):
+                launch(c, i)
+            e1.record()
+            e1.synchronize()
+            score[c] = min(score[c], e0.elapsed_time(e1))
+    return min(candidates, key=score.get)
 
 
 # ---- heuristics ------------------------------------------------------------------------------------------------------
