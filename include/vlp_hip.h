@@ -361,8 +361,9 @@ int vlp_embed_bwd_pos(const vlp_embed_bwd_pos_args* a, void* stream);
  * src_f32 != 0 reads fp32 input (features arrive as fp32 then .half(): run_img2txt_dist.py:466-468). */
 int vlp_copy2d(const void* src, int64_t lds, int32_t src_f32, void* dst, int64_t ldd, int32_t rows,
                int32_t cols_src, int32_t cols_dst, int32_t beta, void* stream);
-/* dst[c, r] = src[r, c] for r < rows, c < cols; dst columns in [rows, ldd) of rows c < cols_pad are 0
- * (weight shadows W^T for the dgrad GEMMs; zero padding keeps K % 64 == 0). */
+/* dst[c, r] = src[r, c] for r < rows, c < cols; dst columns in [rows, rows_pad) of the rows c < cols are written as 0
+ * (weight shadows W^T for the dgrad GEMMs; zero padding keeps K % 64 == 0); columns in [rows_pad, ldd) are not written
+ * (rows_pad >= rows, ldd >= rows_pad). */
 int vlp_transpose(const void* src, int64_t lds, void* dst, int64_t ldd, int32_t rows, int32_t cols,
                   int32_t rows_pad, void* stream);
 /* Batched form: n independent transposes in one launch.  descs / tile_start live in DEVICE memory; tile_start[i] is the
@@ -534,6 +535,12 @@ int vlp_gelu_bwd(const void* dy, const void* z, void* dz, int64_t n, void* strea
  * coef[B*P] = keep * weight / denominator; vlp_mlm_loss_bwd writes
  * dlogits[r, v] = grad_scale * coef[r] * (softmax(logits[r])[v] - [v == label[r]]) for v < V and 0 for
  * V <= v < ld_dlogits.
+ * drop_worst_ratio is a float field (ABI) while the reference computes int(B * (1 - ratio)) with the caller's double, and the
+ * widened float is not that double (1 - 0.2f is 1.2e-8 short of 0.8: B = 40 would keep 31, Python keeps 32).  The launcher (both
+ * vlp_mlm_loss_fwd and vlp_mlm_loss_ls_fwd, csrc/keep_count.h) therefore recovers the caller's double before the double
+ * arithmetic: the double nearest to the float's shortest round-tripping decimal when that has at most 6 significant digits
+ * (0.2f -> 0.2), else the simplest fraction p / q inside the float's rounding interval (0.33333334f -> 1.0 / 3); then double
+ * difference, double product, truncation, as Python does.  A caller who passes such a Python float r gets Python's count.
  */
 typedef struct {
     const void* logits; int64_t ld_logits;    /* [B*P, V] fp16 */
@@ -566,7 +573,8 @@ int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream);
  * target), so q_log_q = (V-2) * half(s log s) + half(c log c) there.  Requires V > 2, 0 <= ignore_index < V.
  * vlp_mlm_loss_ls_bwd writes dlogits[r, v] = grad_scale * coef[r] * (softmax(logits[r])[v] * q_sum - q[v])
  * for v < V, 0 for V <= v < ld_dlogits, and 0 on every column of a row whose label is ignore_index.
- * Labels are clamped to [0, V) like the plain CE entry points. */
+ * Labels are clamped to [0, V) like the plain CE entry points.  drop_worst_ratio: the launcher recovers the caller's double from the
+ * float field exactly as vlp_mlm_loss_fwd does (one shared helper), so the kept-sample count is Python's int(B * (1 - r)). */
 typedef struct {
     const void* logits; int64_t ld_logits;    /* [B*P, V] fp16 */
     const int64_t* labels;                    /* [B*P] */

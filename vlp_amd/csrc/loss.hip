@@ -4,6 +4,7 @@
 //              with label smoothing the per-row KL of loss.py LabelSmoothingLoss instead of the CE (modeling.py:1104-1106);
 //   VQA:       BCEWithLogitsLoss(mean) * num_answers (modeling.py:1030, 1140).
 #include "common.h"
+#include "keep_count.h"
 
 #define CE_THREADS 256
 
@@ -107,8 +108,7 @@ extern "C" int vlp_mlm_loss_fwd(const vlp_mlm_loss_fwd_args* a, void* stream) {
     const int rows = a->B * a->P;
     hipLaunchKernelGGL(ce_row_kernel, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)a->logits, a->ld_logits, a->labels, a->lse, a->row_loss, a->V);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_fwd(ce)");
-    // int(loss.size(0) * (1 - ratio)) computed like python: double arithmetic, truncation
-    const int keep_n = (int)((double)a->B * (1.0 - (double)a->drop_worst_ratio));
+    const int keep_n = vlp_drop_worst_keep_count(a->B, a->drop_worst_ratio);
     hipLaunchKernelGGL(mlm_finish_kernel, dim3(1), dim3(1024), 3 * a->B * sizeof(float), s, a->row_loss, a->weights, a->loss, a->coef, a->B, a->P, keep_n);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_fwd(finish)");
     return VLP_OK;
@@ -226,7 +226,7 @@ extern "C" int vlp_mlm_loss_ls_fwd(const vlp_mlm_loss_ls_fwd_args* a, void* stre
     hipLaunchKernelGGL(ce_ls_row_kernel, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)a->logits, a->ld_logits, a->labels, a->lse, a->row_loss,
                        a->V, a->smooth, a->confidence, a->q_log_q, a->ignore_index);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(row)");
-    const int keep_n = (int)((double)a->B * (1.0 - (double)a->drop_worst_ratio));
+    const int keep_n = vlp_drop_worst_keep_count(a->B, a->drop_worst_ratio);
     hipLaunchKernelGGL(mlm_finish_kernel, dim3(1), dim3(1024), 3 * a->B * sizeof(float), s, a->row_loss, a->weights, a->loss, a->coef, a->B, a->P, keep_n);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(finish)");
     return VLP_OK;
