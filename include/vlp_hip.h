@@ -514,6 +514,19 @@ typedef struct {
     int64_t eos_id;
 } vlp_beam_select_args;
 int vlp_beam_select(const vlp_beam_select_args* a, void* stream);
+/* Duplicate n-gram blocking on the device (get_dup_ngram_candidates, modeling.py:1391-1406), for a search that never leaves the GPU:
+ *   vlp_ngram_candidates: wids / ptrs are the frames [frames, B, K] that vlp_beam_select writes (int64, contiguous).  Row r = b*K + k:
+ *       the hypothesis that ends in beam k of frame s is rebuilt by following ptrs back from frame s (length s + 1 <= 256); the words that
+ *       would complete a repeated n-gram (n = ngram_size >= 2) go to cand_ids[r * cand_ld + 0 .. cand_cnt[r]): every distinct
+ *       seq[i + n - 1] with seq[i .. i + n - 2] equal to the last n - 1 words, except words of the ignore list; the count is 0 when
+ *       s + 1 < n or when one of the last n - 1 words is in the ignore list (ignore_ids: n_ignore int64 on the device, NULL when 0).
+ *       cand_ld >= s + 1; nothing beyond the first cand_cnt[r] entries of a row is written.  K <= 64.
+ *   vlp_logsoftmax_topk_list: vlp_logsoftmax_topk with the forbidden words of row r given as that list instead of a dense mask (cand_ld <=
+ *       1024; a count is clamped to cand_ld); same ids, scores equal bit for bit to the dense form with the mask scattered from the lists. */
+int vlp_ngram_candidates(const int64_t* wids, const int64_t* ptrs, int32_t B, int32_t K, int32_t s, int32_t ngram_size, const int64_t* ignore_ids,
+                         int32_t n_ignore, int32_t* cand_ids, int64_t cand_ld, int32_t* cand_cnt, void* stream);
+int vlp_logsoftmax_topk_list(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t K, const int32_t* cand_ids, int64_t cand_ld,
+                             const int32_t* cand_cnt, int32_t eos_id, int32_t block_eos, float* out_scores, int64_t* out_ids, void* stream);
 int vlp_kv_gather(const void* src, int64_t src_rows_per_batch, void* dst, int64_t dst_rows_per_batch, const int64_t* idx, int32_t R, int32_t lo,
                   int32_t hi, int32_t row_elems, void* stream);
 /* VQA fusion (modeling.py:1044,1138): out[b,:] = h[b,0,:] * h[b,Nv+1,:]; backward adds into dh rows.  row_off ([B+1] or NULL, ABI 4):

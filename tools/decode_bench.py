@@ -1,4 +1,9 @@
-"""N1 measurement: captions/s of the K/V-cache decoder (12 layers, vocab 28 996, 100 regions, 20 generated tokens), greedy and beam."""
+"""N1 measurement: captions/s of the K/V-cache decoder (12 layers, vocab 28 996, 100 regions, 20 generated tokens), greedy and beam.
+
+    MODES=greedy,beam3,beam5[,beam3_ngram,beam5_ngram]   the *_ngram modes search with forbid_duplicate_ngrams=True, ngram_size=3
+    BLOCKING=device|host                                 where their n-gram blocking runs (BertForSeq2SeqDecoder.ngram_blocking); host mode
+                                                         only needs interfaces older trees have, so this file also times those
+"""
 import json
 import os
 import sys
@@ -26,9 +31,16 @@ am = torch.zeros(B, out_len, out_len, dtype=torch.long)
 am[:, :, :in_len] = 1
 am[:, in_len:, in_len:] = torch.tril(torch.ones(T, T, dtype=torch.long))
 am = am.to(dev)
-MODES = [m for m in (("greedy", dict(search_beam_size=1)), ("beam3", dict(search_beam_size=3)), ("beam5", dict(search_beam_size=5))) if m[0] in os.environ.get("MODES", "greedy,beam3,beam5").split(",")]
+BLOCKING = os.environ.get("BLOCKING", "device")
+assert BLOCKING in ("device", "host")
+NGRAM = dict(forbid_duplicate_ngrams=True, ngram_size=3)
+MODES = [m for m in (("greedy", dict(search_beam_size=1)), ("beam3", dict(search_beam_size=3)), ("beam5", dict(search_beam_size=5)),
+                     ("beam3_ngram", dict(search_beam_size=3, **NGRAM)), ("beam5_ngram", dict(search_beam_size=5, **NGRAM)))
+         if m[0] in os.environ.get("MODES", "greedy,beam3,beam5").split(",")]
 for name, kw in MODES:
     m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=Nv, allow_random_fc7=True, **kw).half().to(dev).eval()
+    if name.endswith("_ngram"):
+        m.ngram_blocking = BLOCKING
     for _ in range(2):
         m(img, vis_pe, input_ids, token_type, pos, am)
     torch.cuda.synchronize()
@@ -41,6 +53,8 @@ for name, kw in MODES:
     dt = (time.perf_counter() - t0) / n
     out[name] = {"ms_per_batch": round(dt * 1e3, 2), "captions_per_s": round(B / dt, 1), "ms_per_token_step": round(dt * 1e3 / T, 3),
                  "host_enqueue_ms": round(t_enq * 1e3, 2)}
+    if name.endswith("_ngram"):
+        out[name]["ngram_blocking"] = BLOCKING
     if name != "greedy":
         # beam_search() returns the best sequences, which needs one device -> host copy of the frames: the call itself waits for the GPU, so the
         # "enqueue" figure equals the wall time; the device work is enqueued in ~2 ms (Engine.decode_beam, hipGraph replays) -- decoding is not host-bound

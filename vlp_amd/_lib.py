@@ -199,6 +199,8 @@ SYMBOLS = {
     "vlp_argmax_rows2": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp]),
     "vlp_logsoftmax_topk": (C.c_int, [vp, i64, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "vlp_beam_select": (C.c_int, [C.POINTER(BeamSelectArgs), vp]),
+    "vlp_ngram_candidates": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp]),
+    "vlp_logsoftmax_topk_list": (C.c_int, [vp, i64, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     "vlp_kv_gather": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]),
     "vlp_embed_bwd_workspace_floats": (C.c_int64, [i32, i32, i32, i32]),
     "vlp_mask_build": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
@@ -499,6 +501,31 @@ def logsoftmax_topk(logits, ld, rows, V, K, out_scores, out_ids, forbid=None, eo
     _req_cuda(logits, out_scores, out_ids, forbid)
     _check(load().vlp_logsoftmax_topk(ptr(logits), ld, rows, V, K, ptr(forbid), eos_id, 1 if block_eos else 0, ptr(out_scores), ptr(out_ids),
                                       stream_ptr()))
+
+
+def ngram_candidates(wids, ptrs, B, K, s, ngram_size, cand_ids, cand_cnt, ignore_ids=None):
+    """wids / ptrs: contiguous int64 [frames, B, K]; cand_ids int32 [B*K, C] (row stride = stride(0) >= s + 1), cand_cnt int32 [B*K];
+    ignore_ids: int64 device vector or None."""
+    _req_cuda(wids, ptrs, cand_ids, cand_cnt, ignore_ids)
+    assert wids.dtype == torch.int64 and ptrs.dtype == torch.int64 and wids.is_contiguous() and ptrs.is_contiguous()
+    assert tuple(wids.shape[1:]) == (B, K) and tuple(ptrs.shape[1:]) == (B, K) and s < wids.shape[0] and s < ptrs.shape[0]
+    assert cand_ids.dtype == torch.int32 and cand_cnt.dtype == torch.int32 and cand_ids.stride(1) == 1 and cand_cnt.is_contiguous()
+    assert cand_ids.shape[0] >= B * K and cand_cnt.numel() >= B * K
+    n_ignore = 0
+    if ignore_ids is not None:
+        assert ignore_ids.dtype == torch.int64 and ignore_ids.is_contiguous()
+        n_ignore = ignore_ids.numel()
+    _check(load().vlp_ngram_candidates(ptr(wids), ptr(ptrs), B, K, s, ngram_size, ptr(ignore_ids) if n_ignore else None, n_ignore, ptr(cand_ids),
+                                       cand_ids.stride(0), ptr(cand_cnt), stream_ptr()))
+
+
+def logsoftmax_topk_list(logits, ld, rows, V, K, out_scores, out_ids, cand_ids, cand_cnt, eos_id=0, block_eos=False):
+    """logsoftmax_topk with row r's forbidden words = cand_ids[r, :cand_cnt[r]] (int32; what ngram_candidates writes)."""
+    _req_cuda(logits, out_scores, out_ids, cand_ids, cand_cnt)
+    assert cand_ids.dtype == torch.int32 and cand_cnt.dtype == torch.int32 and cand_ids.stride(1) == 1 and cand_cnt.is_contiguous()
+    assert cand_ids.shape[0] >= rows and cand_cnt.numel() >= rows
+    _check(load().vlp_logsoftmax_topk_list(ptr(logits), ld, rows, V, K, ptr(cand_ids), cand_ids.stride(0), ptr(cand_cnt), eos_id, 1 if block_eos else 0,
+                                           ptr(out_scores), ptr(out_ids), stream_ptr()))
 
 
 def beam_select(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, out_ptrs, out_eos, src_rows, next_ids, B, K, first, eos_id):

@@ -732,13 +732,35 @@ extern "C" int vlp_argmax_rows(const void* logits, int64_t ld, int32_t rows, int
 // ---------------------------------------------------------------------------------------------
 // per row: log_softmax over V, + (-10000) on forbidden words, eos column forced to -10000 when blocked, then the K best
 // (value descending, index ascending on ties)  -- :1297-1303
-__global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, int eos_id,
+// LIST (vlp_logsoftmax_topk_list): the row's forbidden words come as a short id list (vlp_ngram_candidates) instead of a dense mask.  The
+// list sits in LDS and is only scanned for an element whose unpenalised value would change the thread's state: the penalty can only lower a
+// value, so an element that fails that test fails it after the penalty too -- results equal the dense form bit for bit, no [rows, V] bytes read.
+#define TOPK_LIST_MAX 1024
+struct TopkList { const int32_t* ids; int64_t ld; const int32_t* cnt; };
+template <int NT>
+DEVFN int topk_list_load(const TopkList& tl, int row, int tid, int* lst) {
+    int n = tl.cnt[row];
+    const int cap = tl.ld < TOPK_LIST_MAX ? (int)tl.ld : TOPK_LIST_MAX;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    for (int j = tid; j < n; j += NT) lst[j] = tl.ids[(int64_t)row * tl.ld + j];
+    return n;                                    // visible to the block after its next __syncthreads()
+}
+DEVFN bool topk_list_has(const int* lst, int n, int v) {
+    bool hit = false;
+    for (int j = 0; j < n; ++j) hit |= lst[j] == v;
+    return hit;
+}
+template <bool LIST>
+__global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl, int eos_id,
                                                               int block_eos, float* out_scores, int64_t* out_ids) {
     __shared__ float sv[256];
     __shared__ int si[256];
+    __shared__ int lst[LIST ? TOPK_LIST_MAX : 1];
     const int row = blockIdx.x, tid = threadIdx.x;
     const f16* x = logits + (int64_t)row * ld;
-    const uint8_t* fb = forbid ? forbid + (int64_t)row * V : nullptr;
+    const uint8_t* fb = (!LIST && forbid) ? forbid + (int64_t)row * V : nullptr;
+    int ncand = 0;
+    if constexpr (LIST) ncand = topk_list_load<256>(tl, row, tid, lst);
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) mx = fmaxf(mx, (float)x[v]);
     sv[tid] = mx;
@@ -767,7 +789,14 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits,
         for (int v = tid; v < V; v += 256) {
             float val = (float)x[v] - lse;
             if (fb && fb[v]) val += -10000.0f;
-            if (block_eos && v == eos_id) val = -10000.0f;
+            const bool is_eos = block_eos && v == eos_id;
+            if (is_eos) val = -10000.0f;
+            if constexpr (LIST) {
+                // `best` restarts at -inf in every pass, so a thread scans the list for the first element of each pass, and again for every
+                // element taken in an earlier pass (its unpenalised value is >= pv): K * (1 + a few) scans of <= s + 1 ids per thread against
+                // V / 256 elements per pass.  `after` cannot serve as the gate: the penalty can move an element from "taken" to "not yet taken".
+                if (!is_eos && (val > best || (val == best && v < bi)) && topk_list_has(lst, ncand, v)) val += -10000.0f;
+            }
             const bool after = (val < pv) || (val == pv && v > pi);          // not yet taken
             if (after && (val > best || (val == best && v < bi))) { best = val; bi = v; }
         }
@@ -796,14 +825,17 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits,
 DEVFN void topk_better(float& bv, int& bi, float f, int j) {
     if (f > bv || (f == bv && j < bi)) { bv = f; bi = j; }
 }
-template <int KMAX>
-__global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, int eos_id,
-                                                                     int block_eos, float* out_scores, int64_t* out_ids) {
+template <int KMAX, bool LIST>
+__global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl,
+                                                                     int eos_id, int block_eos, float* out_scores, int64_t* out_ids) {
     __shared__ float sv[16];
     __shared__ int si[16];
+    __shared__ int lst[LIST ? TOPK_LIST_MAX : 1];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv_ = tid >> 6;
     const f16* x = logits + (int64_t)row * ld;
-    const uint8_t* fb = forbid ? forbid + (int64_t)row * V : nullptr;
+    const uint8_t* fb = (!LIST && forbid) ? forbid + (int64_t)row * V : nullptr;
+    int ncand = 0;
+    if constexpr (LIST) ncand = topk_list_load<1024>(tl, row, tid, lst);
     const int nv = V >> 3;                               // whole 8-element vectors (rows are 16-byte aligned: ld % 8 == 0 is checked by the launcher)
     float mx = -INFINITY;
     for (int i = tid; i < nv; i += 1024) {
@@ -841,8 +873,15 @@ __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* 
     auto offer = [&](float raw, int v) {
         float val = raw - lse;
         if (fb && fb[v]) val += -10000.0f;
-        if (block_eos && v == eos_id) val = -10000.0f;
+        const bool is_eos = block_eos && v == eos_id;
+        if (is_eos) val = -10000.0f;
         if (val > lv[KMAX - 1] || (val == lv[KMAX - 1] && v < lidx[KMAX - 1])) {
+            if constexpr (LIST) {
+                if (!is_eos && topk_list_has(lst, ncand, v)) {
+                    val += -10000.0f;
+                    if (!(val > lv[KMAX - 1] || (val == lv[KMAX - 1] && v < lidx[KMAX - 1]))) return;
+                }
+            }
             int vi = v;
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {         // insertion into the sorted list (compare-and-swap down the chain)
@@ -883,22 +922,118 @@ __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* 
         __syncthreads();
     }
 }
+static int topk_launch(const char* who, const void* logits, int64_t ld, int rows, int V, int K, const uint8_t* forbid, const TopkList* tl, int eos_id,
+                       int block_eos, float* out_scores, int64_t* out_ids, hipStream_t s) {
+    const bool vec_ok = ld % 8 == 0 && (uintptr_t)logits % 16 == 0;      // 16-byte row loads; anything else takes the scalar K+2-pass kernel
+    const TopkList none = {nullptr, 0, nullptr};
+#define LAUNCH_TOPK(KM)                                                                                                                          \
+    do {                                                                                                                                         \
+        if (tl) hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, true>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, nullptr, *tl, \
+                                   eos_id, block_eos, out_scores, out_ids);                                                                       \
+        else hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, false>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, forbid, none,  \
+                                eos_id, block_eos, out_scores, out_ids);                                                                          \
+    } while (0)
+    if (vec_ok && K <= 4) LAUNCH_TOPK(4);
+    else if (vec_ok && K <= 8) LAUNCH_TOPK(8);
+    else if (vec_ok && K <= 16) LAUNCH_TOPK(16);
+    else if (tl)
+        hipLaunchKernelGGL(logsoftmax_topk_kernel<true>, dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, nullptr, *tl, eos_id, block_eos,
+                           out_scores, out_ids);
+    else
+        hipLaunchKernelGGL(logsoftmax_topk_kernel<false>, dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, forbid, none, eos_id, block_eos,
+                           out_scores, out_ids);
+#undef LAUNCH_TOPK
+    VLP_CHECK_LAUNCH(who);
+    return VLP_OK;
+}
 extern "C" int vlp_logsoftmax_topk(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t K, const uint8_t* forbid, int32_t eos_id,
                                    int32_t block_eos, float* out_scores, int64_t* out_ids, void* stream) {
     VLP_CHECK_ARG(logits && out_scores && out_ids && rows > 0 && V > 0 && K > 0 && K <= V && ld >= V, "vlp_logsoftmax_topk: bad args");
     VLP_ENTER(logits, "vlp_logsoftmax_topk");
-    hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_TOPK(KM) hipLaunchKernelGGL(logsoftmax_topk_small_kernel<KM>, dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, forbid, eos_id, \
-                                           block_eos, out_scores, out_ids)
-    const bool vec_ok = ld % 8 == 0 && (uintptr_t)logits % 16 == 0;      // 16-byte row loads; anything else takes the scalar K+2-pass kernel
-    if (vec_ok && K <= 4) LAUNCH_TOPK(4);
-    else if (vec_ok && K <= 8) LAUNCH_TOPK(8);
-    else if (vec_ok && K <= 16) LAUNCH_TOPK(16);
-    else
-        hipLaunchKernelGGL(logsoftmax_topk_kernel, dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, forbid, eos_id, block_eos,
-                           out_scores, out_ids);
-#undef LAUNCH_TOPK
-    VLP_CHECK_LAUNCH("vlp_logsoftmax_topk");
+    return topk_launch("vlp_logsoftmax_topk", logits, ld, rows, V, K, forbid, nullptr, eos_id, block_eos, out_scores, out_ids, (hipStream_t)stream);
+}
+extern "C" int vlp_logsoftmax_topk_list(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t K, const int32_t* cand_ids, int64_t cand_ld,
+                                        const int32_t* cand_cnt, int32_t eos_id, int32_t block_eos, float* out_scores, int64_t* out_ids, void* stream) {
+    VLP_CHECK_ARG(logits && out_scores && out_ids && rows > 0 && V > 0 && K > 0 && K <= V && ld >= V, "vlp_logsoftmax_topk_list: bad args");
+    VLP_CHECK_ARG(cand_ids && cand_cnt && cand_ld >= 1 && cand_ld <= TOPK_LIST_MAX, "vlp_logsoftmax_topk_list: needs cand_ids / cand_cnt with 1 <= cand_ld <= %d",
+                  TOPK_LIST_MAX);
+    VLP_ENTER(logits, "vlp_logsoftmax_topk_list");
+    const TopkList tl = {cand_ids, cand_ld, cand_cnt};
+    return topk_launch("vlp_logsoftmax_topk_list", logits, ld, rows, V, K, nullptr, &tl, eos_id, block_eos, out_scores, out_ids, (hipStream_t)stream);
+}
+
+// One wave per hypothesis row r = b*K + k: the words that would complete a repeated n-gram (get_dup_ngram_candidates, modeling.py:1391-1406).
+// The sample's back pointers of frames 0..s go to LDS as bytes (K <= 64), lane 0 walks them from frame s (s + 1 LDS hops, no dependent global
+// loads), the lanes fetch the words along that path; then every start i is compared with the last n-1 words, and a match's follower is emitted
+// by the first start that produces it (distinct ids; ballot prefix -> a deterministic order, plain vector stores, no atomics).
+#define NGRAM_MAX_FRAMES 256
+__global__ __launch_bounds__(64) void ngram_candidates_kernel(const int64_t* wids, const int64_t* ptrs, int B, int K, int s, int n, const int64_t* ignore,
+                                                              int n_ignore, int32_t* cand_ids, int64_t cand_ld, int32_t* cand_cnt) {
+    __shared__ unsigned char bp[NGRAM_MAX_FRAMES * 64];
+    __shared__ int path[NGRAM_MAX_FRAMES];
+    __shared__ int seq[NGRAM_MAX_FRAMES];
+    __shared__ int hit[NGRAM_MAX_FRAMES];
+    __shared__ int dead;
+    const int r = blockIdx.x, b = r / K, k = r % K, lane = threadIdx.x, L = s + 1;
+    if (L < n) {
+        if (lane == 0) cand_cnt[r] = 0;
+        return;
+    }
+    for (int i = lane; i < L * K; i += 64) {
+        const int f = i / K, j = i - f * K;
+        const int64_t p = ptrs[((int64_t)f * B + b) * K + j];
+        bp[i] = (unsigned char)((p >= 0 && p < K) ? p : 0);
+    }
+    if (lane == 0) dead = 0;
+    __syncthreads();
+    if (lane == 0) {
+        int j = k;
+        for (int f = s; f >= 0; --f) {
+            path[f] = j;
+            j = bp[f * K + j];
+        }
+    }
+    __syncthreads();
+    for (int f = lane; f < L; f += 64) seq[f] = (int)wids[((int64_t)f * B + b) * K + path[f]];
+    __syncthreads();
+    const int t0 = L - (n - 1), nm = L - (n - 1);          // the tail starts at t0; starts i in [0, nm) have a follower seq[i + n - 1]
+    for (int i = lane; i < (n - 1) * n_ignore; i += 64)
+        if ((int64_t)seq[t0 + i / n_ignore] == ignore[i % n_ignore]) dead = 1;
+    for (int i = lane; i < nm; i += 64) {
+        bool m = true;
+        for (int j = 0; j < n - 1; ++j) m &= seq[i + j] == seq[t0 + j];
+        const int nxt = seq[i + n - 1];
+        if (m)
+            for (int q = 0; q < n_ignore; ++q) m &= ignore[q] != (int64_t)nxt;
+        hit[i] = m ? 1 : 0;
+    }
+    __syncthreads();
+    int cnt = 0;
+    if (!dead) {
+        for (int i0 = 0; i0 < nm; i0 += 64) {
+            const int i = i0 + lane;
+            bool first = i < nm && hit[i];
+            if (first) {
+                const int nxt = seq[i + n - 1];
+                for (int j = 0; j < i; ++j) first &= !(hit[j] && seq[j + n - 1] == nxt);
+            }
+            const unsigned long long mask = __ballot(first);
+            if (first) cand_ids[(int64_t)r * cand_ld + cnt + __popcll(mask & ((1ull << lane) - 1ull))] = seq[i + n - 1];
+            cnt += __popcll(mask);
+        }
+    }
+    if (lane == 0) cand_cnt[r] = cnt;
+}
+extern "C" int vlp_ngram_candidates(const int64_t* wids, const int64_t* ptrs, int32_t B, int32_t K, int32_t s, int32_t ngram_size, const int64_t* ignore_ids,
+                                    int32_t n_ignore, int32_t* cand_ids, int64_t cand_ld, int32_t* cand_cnt, void* stream) {
+    VLP_CHECK_ARG(wids && ptrs && cand_ids && cand_cnt, "vlp_ngram_candidates: null operand");
+    VLP_ENTER(wids, "vlp_ngram_candidates");
+    VLP_CHECK_ARG(B > 0 && K > 0 && K <= 64 && s >= 0 && s + 1 <= NGRAM_MAX_FRAMES && ngram_size >= 2 && cand_ld >= (int64_t)s + 1,
+                  "vlp_ngram_candidates: needs B > 0, 0 < K <= 64, 0 <= s < %d, ngram_size >= 2, cand_ld >= s + 1", NGRAM_MAX_FRAMES);
+    VLP_CHECK_ARG(n_ignore >= 0 && (n_ignore == 0 || ignore_ids), "vlp_ngram_candidates: n_ignore > 0 needs ignore_ids");
+    hipLaunchKernelGGL(ngram_candidates_kernel, dim3(B * K), dim3(64), 0, (hipStream_t)stream, wids, ptrs, B, K, s, ngram_size, ignore_ids, n_ignore, cand_ids,
+                       cand_ld, cand_cnt);
+    VLP_CHECK_LAUNCH("vlp_ngram_candidates");
     return VLP_OK;
 }
 

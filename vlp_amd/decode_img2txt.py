@@ -1,0 +1,274 @@
+"""Caption decoding from a fine-tuned checkpoint: the counterpart of the reference's vlp/decode_img2txt.py on packed region features.
+
+    python -m vlp_amd.decode_img2txt --bert_model DIR --model_recover_path 'out/model.*.bin' --packed_features STORE \\
+        --src_file dataset_coco.json --split val --fp16 --enable_butd --new_segment_ids --beam_size 3 --forbid_duplicate_ngrams
+
+Every flag of the reference script keeps its name and default.  What differs:
+  * region features come from a vlp_amd.data packed store (--packed_features, keyed by the file name's stem) and go to the model as stored:
+    fp16 features plus RawRegions (boxes, class probabilities); vlp_vis_pe_prep encodes them on the device (seq2seq_loader.py:459-470);
+  * the decoder inputs of Preprocess4Seq2seqDecoder (seq2seq_loader.py:390-429: [CLS] [UNK]*Nv [SEP], segments, positions, the prefix-visible /
+    target-causal mask) are built on the device, once per batch size;
+  * there is no tokenizer: the vocabulary file only maps the special tokens and --forbid_ignore_word to ids and the decoded ids back to word
+    pieces.  Without one the ids of vlp_amd.synthetic are used and captions are written as space-joined token ids;
+  * the predictions [{"image_id", "caption"}, ...] (input order; the list the reference hands to language_eval) are written to --output_file;
+    scoring them is left to the caller.
+--do_lower_case, --image_root, --region_bbox_file and --region_det_file_prefix are accepted for the reference's command lines and not used: there is
+no tokenizer, and the features come from the packed store.
+A short last batch is filled up with its last image (and the extra rows dropped), so every batch runs the same launches.
+"""
+import argparse
+import glob
+import json
+import logging
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import synthetic
+from .data import PackedRegionStore, FEAT_DIM, BOX_DIM
+from .input_prep import RawRegions, N_CLS
+from .modeling import BertForSeq2SeqDecoder, load_checkpoint_state
+from .run_img2txt_dist import model_config
+
+logger = logging.getLogger(__name__)
+
+
+# the reference script's command line, flag for flag: (name, type, default); its store_true switches follow
+_REFERENCE_OPTIONS = (
+    ("config_path", str, None), ("bert_model", str, "bert-base-cased"), ("model_recover_path", str, None), ("max_position_embeddings", int, 512),
+    ("seed", int, 123), ("batch_size", int, 4), ("beam_size", int, 1), ("length_penalty", float, 0), ("forbid_ignore_word", str, None),
+    ("min_len", int, None), ("ngram_size", int, 3), ("max_tgt_length", int, 20), ("src_file", str, "/mnt/dat/COCO/annotations/dataset_coco.json"),
+    ("dataset", str, "coco"), ("len_vis_input", int, 100), ("image_root", str, "/mnt/dat/COCO/images"), ("split", str, "val"),
+    ("drop_prob", float, 0.1), ("region_bbox_file", str, "coco_detection_vg_thresh0.2_feat_gvd_checkpoint_trainvaltest.h5"),
+    ("region_det_file_prefix", str, "feat_cls_1000/coco_detection_vg_100dets_gvd_checkpoint_trainval"), ("file_valid_jpgs", str, ""))
+_REFERENCE_SWITCHES = ("fp16", "amp", "do_lower_case", "new_segment_ids", "forbid_duplicate_ngrams", "enable_butd")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Write captions for the images of one split from a fine-tuned checkpoint.")
+    for name, kind, default in _REFERENCE_OPTIONS:
+        p.add_argument("--" + name, type=kind, default=default)
+    for name in _REFERENCE_SWITCHES:
+        p.add_argument("--" + name, action="store_true")
+    p.add_argument("--packed_features", default="", help="directory of a vlp_amd.data packed region store (write_packed / pack_from_h5); required")
+    p.add_argument("--vocab_file", default=None, help="WordPiece vocabulary, one token per line (default: <bert_model>/vocab.txt when --bert_model is a "
+                                                      "directory); without one, captions are written as token ids")
+    p.add_argument("--output_file", default=None, help="where the predictions go (default: next to the checkpoint, <checkpoint>-<split>-captions.json)")
+    p.add_argument("--num_hidden_layers", type=int, default=None, help="override the config's depth (plumbing tests)")
+    return p
+
+
+# ---- host-only pieces --------------------------------------------------------------------------------------------------
+def merge_word_pieces(pieces):
+    """WordPiece continuation pieces ('##ing') are glued onto the word in front of them; one that opens the caption stays as it is."""
+    words = []
+    for piece in pieces:
+        if words and piece.startswith("##"):
+            words[-1] += piece[2:]
+        else:
+            words.append(piece)
+    return words
+
+
+def parse_forbid_ignore_word(text):
+    """decode_img2txt.py:149-155: '|'-separated words; a bracketed word ([sep]) names a special token and is upper-cased."""
+    return [w.upper() if w.startswith("[") and w.endswith("]") else w for w in text.split("|")]
+
+
+class Vocab(object):
+    """The id <-> word-piece table of a BERT vocab.txt (one token per line, id = line number)."""
+
+    def __init__(self, path):
+        with open(path, "r", encoding="utf-8") as f:
+            self.tokens = [line.rstrip("\n") for line in f]
+        while self.tokens and self.tokens[-1] == "":
+            self.tokens.pop()
+        self.ids = {}
+        for i, t in enumerate(self.tokens):
+            self.ids.setdefault(t, i)
+
+    def __len__(self):
+        return len(self.tokens)
+
+    def to_ids(self, tokens):
+        missing = [t for t in tokens if t not in self.ids]
+        if missing:
+            raise KeyError("not in the vocabulary: %s" % ", ".join(missing))
+        return [self.ids[t] for t in tokens]
+
+
+def special_ids(vocab):
+    """(cls, unk, sep, mask, pad) ids: from the vocabulary, else the ids of vlp_amd.synthetic (those of the BERT cased vocabularies)."""
+    if vocab is None:
+        return synthetic.CLS_ID, synthetic.UNK_ID, synthetic.SEP_ID, synthetic.MASK_ID, synthetic.PAD_ID
+    return tuple(vocab.to_ids(["[CLS]", "[UNK]", "[SEP]", "[MASK]", "[PAD]"]))
+
+
+def forbid_ignore_set(text, vocab):
+    if not text:
+        return None
+    if vocab is None:
+        raise ValueError("--forbid_ignore_word names tokens: it needs a vocabulary (--vocab_file, or a --bert_model directory with vocab.txt)")
+    return set(vocab.to_ids(parse_forbid_ignore_word(text)))
+
+
+def select_images(img_dat, split, dataset, valid_jpgs=None):
+    """decode_img2txt.py:189-206: the images of `split` in file order -> [(image_id, store key)]; the store key is the file name's stem.
+    valid_jpgs only filters datasets other than coco / flickr30k, as in the reference."""
+    if dataset not in ("coco", "cc", "flickr30k"):
+        raise ValueError("--dataset must be coco, cc or flickr30k (got %r)" % (dataset,))
+    if dataset in ("coco", "flickr30k"):
+        valid_jpgs = None
+    out = []
+    for src in img_dat:
+        if src["split"] == split and (valid_jpgs is None or src["filename"] in valid_jpgs):
+            name = src["filename"]
+            if dataset == "coco":
+                imgid = int(name.split("_")[2][:-4])
+            elif dataset == "cc":
+                imgid = int(src["imgid"])
+            else:
+                imgid = int(name.split(".")[0])
+            out.append((imgid, os.path.splitext(os.path.basename(name))[0]))
+    return out
+
+
+def caption_of(w_ids, vocab, sep_id, pad_id):
+    """decode_img2txt.py:250-257: cut at the first [SEP] / [PAD], merge the word pieces; without a vocabulary the ids themselves."""
+    kept = []
+    for t in w_ids:
+        if t in (sep_id, pad_id):
+            break
+        kept.append(int(t))
+    if vocab is None:
+        return " ".join(str(t) for t in kept)
+    return " ".join(merge_word_pieces([vocab.tokens[t] if 0 <= t < len(vocab) else "[UNK]" for t in kept]))
+
+
+def output_path(args, ckpt, n_ckpts):
+    if not args.output_file:
+        return "%s-%s-captions.json" % (os.path.splitext(ckpt)[0], args.split)
+    if n_ckpts == 1:
+        return args.output_file
+    root, ext = os.path.splitext(args.output_file)
+    return "%s.%s%s" % (root, os.path.splitext(os.path.basename(ckpt))[0], ext)
+
+
+# ---- device side -------------------------------------------------------------------------------------------------------
+def decoder_inputs(B, Nv, max_tgt_length, new_segment_ids, cls_id, unk_id, sep_id, device):
+    """Preprocess4Seq2seqDecoder.__call__ (seq2seq_loader.py:390-429) for B images with max_a_len = Nv, built on the device:
+    input_ids [B, Nv+2], token_type_ids / position_ids [B, L], input_mask [B, L, L] with L = Nv + 2 + max_tgt_length."""
+    in_len, L = Nv + 2, Nv + 2 + max_tgt_length
+    input_ids = torch.full((B, in_len), unk_id, dtype=torch.long, device=device)
+    input_ids[:, 0] = cls_id
+    input_ids[:, in_len - 1] = sep_id
+    seg = torch.full((B, L), 5 if new_segment_ids else 1, dtype=torch.long, device=device)
+    seg[:, :in_len] = 4 if new_segment_ids else 0
+    pos = torch.arange(L, dtype=torch.long, device=device).unsqueeze(0).expand(B, L).contiguous()
+    mask = torch.zeros(L, L, dtype=torch.long, device=device)
+    mask[:, :in_len] = 1
+    mask[in_len:, in_len:] = torch.tril(torch.ones(max_tgt_length, max_tgt_length, dtype=torch.long, device=device))
+    return input_ids, seg, pos, mask.unsqueeze(0).expand(B, L, L).contiguous()
+
+
+def require_fp16(args):
+    if not args.fp16:
+        raise NotImplementedError(
+            "vlp_amd implements the reference's --fp16 path (fp16 storage, fp32 accumulate) and has no fp32 compute path.  This command line has "
+            "no --fp16%s.  Add --fp16." % (": --amp only engages together with --fp16 (decode_img2txt.py:138)" if args.amp else ""))
+
+
+def build_decoder(args, vocab, state, device):
+    require_fp16(args)
+    config = model_config(args)
+    cls_id, unk_id, sep_id, mask_id, pad_id = special_ids(vocab)
+    model = BertForSeq2SeqDecoder(config, mask_word_id=mask_id, num_labels=2, search_beam_size=args.beam_size, length_penalty=args.length_penalty,
+                                  eos_id=sep_id, forbid_duplicate_ngrams=args.forbid_duplicate_ngrams,
+                                  forbid_ignore_set=forbid_ignore_set(args.forbid_ignore_word, vocab), ngram_size=args.ngram_size, min_len=args.min_len,
+                                  enable_butd=args.enable_butd, len_vis_input=args.len_vis_input)
+    load_checkpoint_state(model, state)
+    model.half()
+    model.to(device)
+    return model.eval()
+
+
+def decode_images(model, store, keys, args, vocab, device):
+    """Captions of the store rows `keys`, in order."""
+    cls_id, unk_id, sep_id, mask_id, pad_id = special_ids(vocab)
+    Nv, bs = args.len_vis_input, args.batch_size
+    if store.nv != Nv:
+        raise RuntimeError("the packed store holds %d regions per image, --len_vis_input is %d" % (store.nv, Nv))
+    feat = torch.empty(bs, Nv, FEAT_DIM, dtype=torch.float16).pin_memory()
+    cls = torch.empty(bs, Nv, N_CLS, dtype=torch.float16).pin_memory()
+    bbox = torch.empty(bs, Nv, BOX_DIM, dtype=torch.float32).pin_memory()
+    input_ids, seg, pos, mask = decoder_inputs(bs, Nv, args.max_tgt_length, args.new_segment_ids, cls_id, unk_id, sep_id, device)
+    rows = store.rows(keys)
+    captions = []
+    with torch.no_grad():
+        for i in range(0, len(rows), bs):
+            chunk = rows[i:i + bs]
+            n = len(chunk)
+            chunk = chunk + [chunk[-1]] * (bs - n)                  # a short last batch runs at the full size
+            store.gather(chunk, feat.numpy(), cls.numpy(), bbox.numpy())
+            img = feat.to(device, non_blocking=True)
+            regions = RawRegions(bbox.to(device, non_blocking=True), cls.to(device, non_blocking=True))
+            out = model(img, regions, input_ids, seg, pos, mask, task_idx=None)
+            ids = (out["pred_seq"] if args.beam_size > 1 else out[0]).tolist()       # synchronises: the pinned buffers are free again
+            captions.extend(caption_of(w, vocab, sep_id, pad_id) for w in ids[:n])
+    return captions
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    require_fp16(args)
+    if args.enable_butd:
+        assert args.len_vis_input == 100
+    if not args.packed_features:
+        raise NotImplementedError("give --packed_features DIR (vlp_amd.data; the reference's h5 files are converted once with pack_from_h5)")
+    if not args.model_recover_path:
+        raise ValueError("--model_recover_path is required")
+    if not torch.cuda.is_available():
+        raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only; there is no CPU path")
+    device = torch.device("cuda")
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    torch.cuda.manual_seed_all(args.seed)
+
+    vocab_file = args.vocab_file
+    if vocab_file is None and os.path.isdir(args.bert_model) and os.path.exists(os.path.join(args.bert_model, "vocab.txt")):
+        vocab_file = os.path.join(args.bert_model, "vocab.txt")
+    vocab = Vocab(vocab_file) if vocab_file else None
+
+    with open(args.src_file, "r", encoding="utf-8") as f:
+        img_dat = json.load(f)["images"]
+    valid_jpgs = None
+    if args.file_valid_jpgs != "" and args.dataset not in ("coco", "flickr30k"):
+        with open(args.file_valid_jpgs) as f:
+            valid_jpgs = set(json.load(f))
+    images = select_images(img_dat, args.split, args.dataset, valid_jpgs)
+    store = PackedRegionStore(args.packed_features)
+
+    ckpts = sorted(glob.glob(args.model_recover_path.strip()))
+    if not ckpts:
+        raise FileNotFoundError("--model_recover_path %r matches no file" % (args.model_recover_path,))
+    results = {}
+    for ckpt in ckpts:
+        logger.info("***** Recover model: %s *****", ckpt)
+        model = build_decoder(args, vocab, torch.load(ckpt, map_location="cpu"), device)
+        captions = decode_images(model, store, [key for _, key in images], args, vocab, device)
+        predictions = [{"image_id": imgid, "caption": cap} for (imgid, _), cap in zip(images, captions)]
+        out = output_path(args, ckpt, len(ckpts))
+        with open(out, "w") as f:
+            json.dump(predictions, f)
+        logger.info("wrote %d captions to %s", len(predictions), out)
+        results[ckpt] = predictions
+        del model
+    return results
+
+
+if __name__ == "__main__":
+    logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s -   %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO)
+    main()

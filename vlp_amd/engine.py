@@ -936,7 +936,11 @@ class Engine(object):
             # beams: two caches per layer (select_beam_items permutes rows: gather from one into the other, then swap)
             ws.update(kvA=[h(R, Lcap, 2 * H) for _ in range(NL)], kvB=[h(R, Lcap, 2 * H) for _ in range(NL)],
                       kk_s=f(R, Kb), kk_i=i64(R, Kb), src_rows=i64(R), tot=f(Lcap, B, Kb), wids=i64(Lcap, B, Kb), ptrs=i64(Lcap, B, Kb),
-                      eos=f(Lcap, B, Kb))
+                      eos=f(Lcap, B, Kb),
+                      # device n-gram blocking: per hypothesis the words that would repeat an n-gram (vlp_ngram_candidates -> vlp_logsoftmax_topk_list)
+                      # (a hypothesis of frame s lists at most s + 1 <= Lcap - T0 + 1 words)
+                      cand_ids=torch.empty(R, Lcap - T0 + 1, device=dev, dtype=torch.int32), cand_cnt=torch.empty(R, device=dev, dtype=torch.int32),
+                      ngram_ignore={})
         self._ws[key] = ws
         return ws
 
@@ -1170,14 +1174,19 @@ class Engine(object):
         ws["calls"] += 1
         return out_ids[:, :n_steps].clone(), out_val[:, :n_steps].clone()
 
+    NGRAM_MAX_FRAMES = 256       # csrc/elementwise.hip: NGRAM_MAX_FRAMES frames per hypothesis (and <= TOPK_LIST_MAX = 1024 ids per list)
+
     def decode_beam(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, beam_size, eos_id,
-                    min_len=0, forbid_fn=None):
+                    min_len=0, forbid_fn=None, ngram=None):
         """Beam search frames (modeling.py:1255-1430) on the K/V-cache decoder.  The first step runs B sequences; its cache rows are
         replicated to the B*K beams (first_expand), afterwards every step decodes B*K sequences and the caches follow the back
         pointers (select_beam_items) -- only the generated positions; the prefix is identical for all beams of a sample and is kept,
         and streamed by the attention kernel, once per sample.
         `forbid_fn(step_ids [B,K] list, back_ptrs [B,K] list, first)` -> uint8 [B*K, V] numpy mask or None implements the host-side
         n-gram blocking (:1367-1430); when given, ids / pointers are copied to the host every step exactly as the reference does.
+        `ngram=(n, ignore_ids)` (n >= 2; ignore_ids: token ids or None) is the same blocking on the device: after frame s vlp_ngram_candidates
+        lists every hypothesis's forbidden words from the resident frames, step s+1 selects with vlp_logsoftmax_topk_list; nothing goes to
+        the host before the frames are returned and the token steps are captured / replayed like those of an unblocked search.
         Returns (total_scores, step_ids, back_ptrs) as [frames, B, K] tensors on the device."""
         self.pack()
         self.wait_params()
@@ -1203,11 +1212,34 @@ class Engine(object):
         ws["xids"][:, 1] = int(mask_word_id)
         bufs = (ws["kvA"], ws["kvB"])
         forbid = None
+        plan_tag = ()
+        if ngram is not None:
+            if forbid_fn is not None:
+                raise RuntimeError("vlp_amd: decode_beam takes forbid_fn (host blocking) or ngram (device blocking), not both")
+            ng_n, ign = int(ngram[0]), ngram[1]
+            if ng_n < 2:
+                raise RuntimeError("vlp_amd: device n-gram blocking needs ngram_size >= 2 (got %d)" % ng_n)
+            if n_steps > self.NGRAM_MAX_FRAMES:          # the kernels' limits, checked before anything is launched
+                raise RuntimeError("vlp_amd: device n-gram blocking handles at most %d generated tokens (vlp_ngram_candidates keeps a hypothesis in LDS), "
+                                   "this search asks for %d; shorten the target or use ngram_blocking='host'" % (self.NGRAM_MAX_FRAMES, n_steps))
+            ign = tuple(sorted(set(int(t) for t in (ign.tolist() if torch.is_tensor(ign) else ign)))) if ign is not None else ()
+            ng_ignore = None
+            if ign:                      # one device copy per distinct ignore list, owned by the workspace (the captured launches point at it)
+                ng_ignore = ws["ngram_ignore"].get(ign)
+                if ng_ignore is None:
+                    ng_ignore = ws["ngram_ignore"][ign] = torch.tensor(ign, device=dev, dtype=torch.long)
+            plan_tag = ("ngram", ng_n, ign)
 
         def frame(s, rows, first, forbid, block_eos):
-            K.logsoftmax_topk(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], forbid=forbid, eos_id=int(eos_id), block_eos=block_eos)
+            if ngram is not None and not first:
+                K.logsoftmax_topk_list(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], ws["cand_ids"], ws["cand_cnt"], eos_id=int(eos_id),
+                                       block_eos=block_eos)
+            else:
+                K.logsoftmax_topk(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], forbid=forbid, eos_id=int(eos_id), block_eos=block_eos)
             K.beam_select(ws["kk_s"], ws["kk_i"], None if first else tot[s - 1], None if first else eos[s - 1], tot[s], wids[s], ptrs[s], eos[s],
                           ws["src_rows"], ws["xids"][:, 0], B, Kb, first, int(eos_id))
+            if ngram is not None and s + 1 < n_steps:        # the next step's forbidden words (frame 0: s + 1 < n, every count becomes 0)
+                K.ngram_candidates(wids, ptrs, B, Kb, s, ng_n, ws["cand_ids"], ws["cand_cnt"], ignore_ids=ng_ignore)
 
         # step 0: B sequences.  first_expand (:1325-1332) is implicit: the prefix K|V of a sample stays in its per-sample cache and is
         # shared by its beams inside the attention kernel; the per-beam caches only ever hold generated positions
@@ -1235,7 +1267,7 @@ class Engine(object):
                 fm = forbid_fn(wids[s].tolist(), ptrs[s].tolist(), False)
                 forbid = None if fm is None else torch.from_numpy(fm).to(dev)
             else:
-                self._run_planned(ws, ("beam", s, int(eos_id), block_eos), step)
+                self._run_planned(ws, ("beam", s, int(eos_id), block_eos) + plan_tag, step)
         ws["calls"] += 1
         return tot[:n_steps].clone(), wids[:n_steps].clone(), ptrs[:n_steps].clone()
 

@@ -567,11 +567,14 @@ class BertForPreTrainingLossMask(PreTrainedBertModel):
 class BertForSeq2SeqDecoder(PreTrainedBertModel):
     """Incremental caption decoder (:1147-1494): same parameter tree as BertForPreTrainingLossMask (checkpoint compatible);
     greedy decoding (:1189-1253) and beam search (:1255-1494) run on the HIP engine with per-layer K/V caches
-    (Engine.decode_greedy / Engine.decode_beam); the host keeps only what the reference keeps on the host (n-gram blocking
-    over python lists, back-tracking of the frames).  sample_mode='sample' draws with the library's counter-based RNG; in train() mode with gradients enabled
+    (Engine.decode_greedy / Engine.decode_beam); the host keeps only the back-tracking of the frames (n-gram blocking runs on the
+    device; the reference's host loop over python lists remains as ngram_blocking="host").  sample_mode='sample' draws with the library's counter-based RNG; in train() mode with gradients enabled
     it also returns differentiable log-probabilities (SCST, run_img2txt_dist.py:506-507): a teacher-forced scoring pass of the sampled ids on
     the training engine (Engine.score_samples), without dropout."""
     tasks = "img2txt"
+    # forbid_duplicate_ngrams with ngram_size >= 2: "device" = Engine.decode_beam(ngram=...) (vlp_ngram_candidates / vlp_logsoftmax_topk_list, no
+    # host round trip, token steps replayed from captured graphs); "host" = the _ngram_blocker closure (A/B and fallback).  Same results.
+    ngram_blocking = "device"
 
     def __init__(self, config, mask_word_id=0, num_labels=2, search_beam_size=1, length_penalty=1.0, eos_id=0,
                  forbid_duplicate_ngrams=False, forbid_ignore_set=None, ngram_size=3, min_len=0, enable_butd=False, len_vis_input=49,
@@ -684,9 +687,16 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         (frames padded with zeros to the output length L), on the input device."""
         B, out_len = input_ids.shape[0], token_type_ids.shape[1]
         K = self.search_beam_size
-        forbid_fn = self._ngram_blocker(B, self.config.vocab_size) if self.forbid_duplicate_ngrams else None
+        forbid_fn = ngram = None
+        if self.forbid_duplicate_ngrams:
+            if self.ngram_blocking not in ("device", "host"):
+                raise ValueError("ngram_blocking must be 'device' or 'host', got %r" % (self.ngram_blocking,))
+            if self.ngram_blocking == "device" and self.ngram_size >= 2:
+                ngram = (self.ngram_size, self.forbid_ignore_set)
+            else:                    # ngram_size == 1 (the reference's seq[-0:] quirk) stays on the host
+                forbid_fn = self._ngram_blocker(B, self.config.vocab_size)
         tot, wids, ptrs = self.engine.decode_beam(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
-                                                  K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn)
+                                                  K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn, ngram=ngram)
         frames = tot.shape[0]
         dev = input_ids.device
         # frames stay on the device: [frames, B, K] -> [B, out_len, K], zero padded (three small launches; no per-sample host loop)

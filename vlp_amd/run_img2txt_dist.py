@@ -188,7 +188,7 @@ def model_config(args):
         config.max_position_embeddings = args.max_position_embeddings
     if args.num_hidden_layers:
         config.num_hidden_layers = args.num_hidden_layers
-    if args.label_smoothing:                  # the from_pretrained kwarg of the reference (:328, 351): the masked-LM loss only, not VQA's
+    if getattr(args, "label_smoothing", None):    # the from_pretrained kwarg of the reference (:328, 351): the masked-LM loss only, not VQA's
         config.label_smoothing = args.label_smoothing
     for key, default in (("relax_projection", 0), ("task_idx", None), ("fp32_embedding", False), ("label_smoothing", None)):
         if not hasattr(config, key):
