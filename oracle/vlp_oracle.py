@@ -133,20 +133,32 @@ def linear(x, w, b=None):
     return F.linear(x, w, b)
 
 
-def linear_add(x, w, b, res):
-    """Linear followed by a residual add (BertSelfOutput / BertOutput, modeling.py:314-316, 354-356; dropout p = 0)."""
+def _drop(t, mult):
+    """nn.Dropout as a given multiplier tensor (0 or 1/(1-p) per element, any shape with t's element count); None: not there at all."""
+    if mult is None:
+        return t
+    return t * mult.to(t.dtype).view(t.shape)
+
+
+def _no_site(site):
+    return None
+
+
+def linear_add(x, w, b, res, drop=None):
+    """Linear, dropout, residual add (BertSelfOutput / BertOutput, modeling.py:314-316, 354-356).  drop: the multiplier tensor of the
+    nn.Dropout between the Linear and the add (None: dropout p = 0); the fused branches apply it in fp32 in front of their one rounding."""
     if _res_exp(x):
         r32 = _res32[1] if (res is _res32[0]) else res.float()
         x, w = _kperm(x, w)
-        s32 = F.linear(x.float(), w.float(), b.float()) + r32
+        s32 = _drop(F.linear(x.float(), w.float(), b.float()), drop) + r32
         s16 = s32.half()
         if "residual_fp32_full" in _policy:
             _pre32[:] = [s16, s32]
         return s16
     if _moved("fused_sum", x):
         x, w = _kperm(x, w)
-        return (F.linear(x.float(), w.float(), b.float()) + res.float()).half()
-    return linear(x, w, b) + res
+        return (_drop(F.linear(x.float(), w.float(), b.float()), drop) + res.float()).half()
+    return _drop(linear(x, w, b), drop) + res
 
 
 def extended_attention_mask(attention_mask, dtype):
@@ -164,21 +176,21 @@ def extended_attention_mask(attention_mask, dtype):
 # ----------------------------------------------------------------------------------------------
 # model
 # ----------------------------------------------------------------------------------------------
-def vis_embed(p, vis_feats):
-    """modeling.py:1003-1007,1035: ReLU(Linear(2048,768)(ReLU(Linear(2048,2048)(x)))) (dropout p=0)."""
+def vis_embed(p, vis_feats, drop=None):
+    """modeling.py:1003-1007,1035: Dropout(ReLU(Linear(2048,768)(ReLU(Linear(2048,2048)(x))))); drop: the Dropout's multiplier (None: p = 0)."""
     h = torch.relu(linear(vis_feats, p["vis_embed.0.weight"], p["vis_embed.0.bias"]))
-    return torch.relu(linear(h, p["vis_embed.2.weight"], p["vis_embed.2.bias"]))
+    return _drop(torch.relu(linear(h, p["vis_embed.2.weight"], p["vis_embed.2.bias"])), drop)
 
 
-def vis_pe_embed(p, vis_pe):
+def vis_pe_embed(p, vis_pe, drop=None):
     """modeling.py:1016-1018,1036."""
-    return torch.relu(linear(vis_pe, p["vis_pe_embed.0.weight"], p["vis_pe_embed.0.bias"]))
+    return _drop(torch.relu(linear(vis_pe, p["vis_pe_embed.0.weight"], p["vis_pe_embed.0.bias"])), drop)
 
 
 def embeddings(p, vis_feats_h, vis_pe_h, input_ids, token_type_ids, len_vis_input, position_ids=None,
-               vis_input=True):
+               vis_input=True, drop=None):
     """modeling.py:217-241: rows 1..Nv of the word stream are the projected region features and rows
-    1..Nv of the position stream are the projected box/class encodings."""
+    1..Nv of the position stream are the projected box/class encodings.  drop: multiplier of the Dropout behind the LayerNorm (:240)."""
     B, L = input_ids.shape
     if position_ids is None:
         position_ids = torch.arange(L, dtype=torch.long, device=input_ids.device).unsqueeze(0).expand_as(input_ids)
@@ -194,11 +206,12 @@ def embeddings(p, vis_feats_h, vis_pe_h, input_ids, token_type_ids, len_vis_inpu
     else:
         pre = words + pos + typ
     out = layer_norm(pre, p["bert.embeddings.LayerNorm.weight"], p["bert.embeddings.LayerNorm.bias"])
-    return out, pre
+    return _drop(out, drop), pre
 
 
-def self_attention(p, pre, x, ext_mask, num_heads, history=None, cap=None):
-    """modeling.py:268-303.  `pre` = 'bert.encoder.layer.{i}.attention.self.'"""
+def self_attention(p, pre, x, ext_mask, num_heads, history=None, cap=None, drop=None):
+    """modeling.py:268-303.  `pre` = 'bert.encoder.layer.{i}.attention.self.'; drop: multiplier [B, heads, Lq, Lk] of the Dropout on the
+    attention probabilities (:296), None: p = 0."""
     B, Lq, H = x.shape
     d = H // num_heads
     kv_in = x if history is None else torch.cat((history, x), dim=1)
@@ -220,26 +233,31 @@ def self_attention(p, pre, x, ext_mask, num_heads, history=None, cap=None):
         sf = scores.float()
         e = torch.exp(sf - sf.max(dim=-1, keepdim=True)[0])
         probs = e / e.sum(dim=-1, keepdim=True)                    # (captured only)
-        ctx = (e.half().float().matmul(v.float()) / e.sum(dim=-1, keepdim=True)).half()
+        if drop is None:
+            ctx = (e.half().float().matmul(v.float()) / e.sum(dim=-1, keepdim=True)).half()
+        else:                                                      # the multiplier in fp32 in front of P~'s one rounding; the sum stays undropped
+            ctx = ((e * drop.float().view(e.shape)).half().float().matmul(v.float()) / e.sum(dim=-1, keepdim=True)).half()
     else:
         probs = torch.softmax(scores, dim=-1)
         if half:
             probs = probs.half()
-        ctx = probs.matmul(v)
+        ctx = _drop(probs, drop).matmul(v)
     ctx = ctx.permute(0, 2, 1, 3).contiguous().view(B, Lq, H)
     if cap is not None:
         cap["probs"] = probs
     return ctx
 
 
-def bert_layer(p, i, x, ext_mask, num_heads, history=None, cap=None):
-    """modeling.py:306-372 (BertSelfOutput, BertIntermediate, BertOutput, BertLayer)."""
+def bert_layer(p, i, x, ext_mask, num_heads, history=None, cap=None, dropout=None):
+    """modeling.py:306-372 (BertSelfOutput, BertIntermediate, BertOutput, BertLayer).  dropout: {site: multiplier} holding this layer's
+    ("attn", i), ("attn_out", i) and ("ffn_out", i), or None."""
     L = "bert.encoder.layer.%d." % i
-    ctx = self_attention(p, L + "attention.self.", x, ext_mask, num_heads, history, cap)
-    a = linear_add(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"], x)
+    site = _no_site if dropout is None else dropout.get
+    ctx = self_attention(p, L + "attention.self.", x, ext_mask, num_heads, history, cap, drop=site(("attn", i)))
+    a = linear_add(ctx, p[L + "attention.output.dense.weight"], p[L + "attention.output.dense.bias"], x, drop=site(("attn_out", i)))
     a = layer_norm(a, p[L + "attention.output.LayerNorm.weight"], p[L + "attention.output.LayerNorm.bias"])
     g = gelu(linear(a, p[L + "intermediate.dense.weight"], p[L + "intermediate.dense.bias"]))
-    o = linear_add(g, p[L + "output.dense.weight"], p[L + "output.dense.bias"], a)
+    o = linear_add(g, p[L + "output.dense.weight"], p[L + "output.dense.bias"], a, drop=site(("ffn_out", i)))
     o = layer_norm(o, p[L + "output.LayerNorm.weight"], p[L + "output.LayerNorm.bias"])
     if cap is not None:
         cap.update(ctx=ctx, attn_out=a, inter=g)
@@ -253,11 +271,11 @@ def num_layers_of(p):
     return n
 
 
-def encoder(p, x, ext_mask, num_heads, num_layers=None):
+def encoder(p, x, ext_mask, num_heads, num_layers=None, dropout=None):
     """modeling.py:382-402 (no-history path).  Returns the list of all layer outputs."""
     outs = []
     for i in range(num_layers if num_layers is not None else num_layers_of(p)):
-        x = bert_layer(p, i, x, ext_mask, num_heads)
+        x = bert_layer(p, i, x, ext_mask, num_heads, dropout=dropout)
         outs.append(x)
     return outs
 
@@ -314,8 +332,12 @@ def vis_pretext_loss(vf, vp, pooled, vis_masked_pos):
 
 
 def forward_pretraining_loss_mask(p, batch, num_heads=12, len_vis_input=100, tasks="img2txt",
-                                  drop_worst_ratio=0.0, vqa_inference=False, capture=False, mask_image_regions=False):
-    """modeling.py:1033-1143 (BertForPreTrainingLossMask.forward; dropout 0).  mask_image_regions=True: the rows of the projected
+                                  drop_worst_ratio=0.0, vqa_inference=False, capture=False, mask_image_regions=False, dropout=None):
+    """modeling.py:1033-1143 (BertForPreTrainingLossMask.forward).  dropout: None = dropout 0 (not one operation differs), or a mapping
+    {site: multiplier tensor} that stands for the reference's nn.Dropout modules of a train() forward: "vis" (:1007), "vispe" (:1018),
+    "emb" (:240), ("attn", i) (:296), ("attn_out", i) (:315), ("ffn_out", i) (:355); a missing site is not dropped.  The pretext loss
+    reads the dropped projections, as the reference's does; the VQA head, the pooler and the LM head have no dropout.
+    mask_image_regions=True: the rows of the projected
     region features / encodings named by batch.vis_masked_pos enter the encoder as zeros (:1049-1056) and the pretext loss
     (:1113-1131) is returned in `vis_pretext_loss` (a 0-dim tensor then, as in the reference).
 
@@ -323,16 +345,18 @@ def forward_pretraining_loss_mask(p, batch, num_heads=12, len_vis_input=100, tas
     3-tuple) plus the parity capture points `mlm_logits` / `vqa_logits` / `hidden` (list)."""
     dt = p["bert.embeddings.word_embeddings.weight"].dtype
     out = {}
-    vf = vis_embed(p, batch.img.to(dt))
-    vp = vis_pe_embed(p, batch.vis_pe.to(dt))
+    site = _no_site if dropout is None else dropout.get
+    vf = vis_embed(p, batch.img.to(dt), drop=site("vis"))
+    vp = vis_pe_embed(p, batch.vis_pe.to(dt), drop=site("vispe"))
+    emb_drop = site("emb")
     ext = extended_attention_mask(batch.input_mask, dt)
     if mask_image_regions and not vqa_inference:                   # :1049-1056 (the inference branch returns before it, :1039-1047)
         keep = torch.ones(vf.shape[0], vf.shape[1], 1, dtype=torch.bool, device=vf.device)
         keep.scatter_(1, (batch.vis_masked_pos - 1).unsqueeze(-1), False)
-        emb, emb_pre = embeddings(p, vf * keep, vp * keep, batch.input_ids, batch.segment_ids, len_vis_input)
+        emb, emb_pre = embeddings(p, vf * keep, vp * keep, batch.input_ids, batch.segment_ids, len_vis_input, drop=emb_drop)
     else:
-        emb, emb_pre = embeddings(p, vf, vp, batch.input_ids, batch.segment_ids, len_vis_input)
-    hs = encoder(p, emb, ext, num_heads)
+        emb, emb_pre = embeddings(p, vf, vp, batch.input_ids, batch.segment_ids, len_vis_input, drop=emb_drop)
+    hs = encoder(p, emb, ext, num_heads, dropout=dropout)
     seq = hs[-1]
     if capture:
         out.update(vis_feats=vf, vis_pe=vp, emb=emb, emb_pre=emb_pre, hidden=hs)
@@ -747,7 +771,7 @@ def init_params(vocab_size=28996, hidden=768, layers=12, inter=3072, max_pos=512
 
 def loss_and_grads(p, batch, **kw):
     """Forward + autograd backward of the summed loss (run_img2txt_dist.py:531,575).  `p` must hold
-    leaf tensors with requires_grad.  Returns (out dict, {key: grad or None})."""
+    leaf tensors with requires_grad; dropout={site: multiplier} goes to the forward.  Returns (out dict, {key: grad or None})."""
     out = forward_pretraining_loss_mask(p, batch, **kw)
     out["loss"].sum().backward()
     return out, {k: t.grad for k, t in p.items()}

@@ -5,39 +5,15 @@ import torch
 
 from vlp_amd import _lib as K
 
+from tests.dropout_ref import M32, _mix32, _mul64, drop_mult_ref as _drop_mult_ref      # noqa: F401
 from tests.hard_inputs import attn_mask, attn_ref, rel      # noqa: F401   (library-free: shared with the CPU tests)
 
 DEV = torch.device("cuda:0")
-M32 = 0xFFFFFFFF
 
 
-# ---- python mirror of csrc/common.h's dropout hash (uint32 arithmetic on int64 tensors) -----------------
-def _mix32(x):
-    x = x & M32
-    x = x ^ (x >> 15); x = ((x & 0xFFFFFF) * 0xd3833f + (x >> 7)) & M32
-    x = x ^ (x >> 13); x = ((x & 0xFFFFFF) * 0x7a6b35 + (x >> 9)) & M32
-    x = x ^ (x >> 16)
-    return x
-
-
-def _mul64(a, b):
-    return (a * b) & 0xFFFFFFFFFFFFFFFF
-
-
+# ---- python mirror of csrc/common.h's dropout hash: tests/dropout_ref.py (library-free); here with this module's device as the default ----
 def drop_mult_ref(p, seed, stream, rows, cols, device=DEV):
-    """[len(rows), len(cols)] multiplier tensor (0 or 1/(1-p)) for elements (row, col): one hash per column pair, the even column
-    takes the low 16 bits, the odd one the high 16 bits, dropped when that half is below round(p * 65536)."""
-    if p <= 0:
-        return torch.ones(len(rows), len(cols), device=device)
-    s = (_mul64(seed, 0x9E3779B97F4A7C15) + _mul64(stream, 0xD1B54A32D192ED03) + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
-    k0, k1 = s & M32, ((s >> 32) & M32) | 1
-    thresh = min(65535, max(1, int(p * 65536.0 + 0.5)))
-    rows = torch.as_tensor(rows, dtype=torch.int64, device=device)
-    cols = torch.as_tensor(cols, dtype=torch.int64, device=device)
-    rk = (_mix32((rows & M32) ^ k0) + _mix32(((rows >> 32) & M32) + k1)) & M32
-    h = _mix32((rk[:, None] + ((cols[None, :] >> 1) * 0x9E3779B9 & M32)) & M32)
-    half = torch.where((cols[None, :] & 1) == 1, h >> 16, h & 0xFFFF)
-    return torch.where(half < thresh, torch.zeros((), device=device), torch.full((), 1.0 / (1.0 - p), device=device))
+    return _drop_mult_ref(p, seed, stream, rows, cols, device)
 
 
 def h16(*shape, scale=1.0, gen=None):

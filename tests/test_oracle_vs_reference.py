@@ -78,6 +78,60 @@ def test_mask_image_regions_pretext_branch_vs_reference(tasks, monkeypatch):
 
 
 @needs_reference
+@pytest.mark.parametrize("mask_image_regions", [False, True])
+def test_dropout_hooks_vs_reference_train_mode(mask_image_regions, monkeypatch):
+    """Dropout ON: the UNMODIFIED reference in train() with drop_prob 0.1, every nn.Dropout.forward replaced by "multiply by the next
+    mask of a queue" (filled in the reference's call order: vis, vispe, emb, then attn / attn_out / ffn_out per layer), against the
+    oracle's dropout={site: multiplier} hooks fed the same masks (tests/dropout_ref.step_masks, an arbitrary seed).  Losses and every
+    parameter gradient, img2txt and the mask_image_regions branch (whose pretext loss reads the DROPPED projections, modeling.py:1113-1120).
+    Pins where each multiplier enters the oracle; the tolerances are those of the dropout-0 tests above."""
+    from tests.dropout_ref import site_order, step_masks
+    if mask_image_regions:
+        monkeypatch.setattr(torch.Tensor, "byte", lambda self: self.bool())       # (torch-version shim, see the pretext test above)
+    layers, B = 2, 4
+    model = ref_loader.build_reference_model(dict(vocab_size=1024, num_hidden_layers=layers), tasks="img2txt", seed=23, drop_prob=0.1).train()
+    b = S.make_batch(B, max_len_b=20, vocab_size=1024, tasks="img2txt", s2s_prob=0.5, seed=25, max_pred=3,
+                     vis_mask_prob=0.25 if mask_image_regions else 0.0)
+    L = b.input_ids.shape[1]
+    masks = step_masks(0x5EED + 41, 0.1, 0.1, B, L, 100, 768, 12, layers)
+    queue = [(site, masks[site]) for site in site_order(layers)]
+    seen = []
+
+    def from_queue(self, x):
+        site, m = queue.pop(0)
+        want = tuple(x.shape) if m.dim() == 4 else (x.shape[:-1].numel(), x.shape[-1])
+        assert tuple(m.shape) == want, (site, tuple(m.shape), tuple(x.shape))
+        seen.append(site)
+        return x * m.view(x.shape)
+    monkeypatch.setattr(torch.nn.Dropout, "forward", from_queue)
+    losses = model(b.img, b.vis_pe, b.input_ids, b.segment_ids, b.input_mask, b.lm_label_ids, b.ans_labels,
+                   b.is_next, masked_pos=b.masked_pos, masked_weights=b.masked_weights, task_idx=b.task_idx,
+                   vis_masked_pos=b.vis_masked_pos, mask_image_regions=mask_image_regions, drop_worst_ratio=0)
+    assert not queue and seen == site_order(layers)
+    (losses[0] + losses[1] + losses[2]).sum().backward()
+    p = O.params_from_state_dict(model.state_dict(), requires_grad=True)
+    out, grads = O.loss_and_grads(p, b, tasks="img2txt", drop_worst_ratio=0.0, mask_image_regions=mask_image_regions, dropout=masks)
+    if mask_image_regions:
+        assert float(losses[1]) > 0.5
+    for ref_l, k in zip(losses, ("mlm_loss", "vis_pretext_loss", "vqa_loss")):
+        assert tuple(ref_l.shape) == tuple(out[k].shape), k
+        assert float(ref_l.sum()) == pytest.approx(float(out[k].sum()), rel=1e-5, abs=1e-6)
+    # the masks matter: the same oracle without them gives another loss
+    with torch.no_grad():
+        plain = O.forward_pretraining_loss_mask(p, b, tasks="img2txt", mask_image_regions=mask_image_regions)
+    assert abs(float(plain["mlm_loss"]) - float(out["mlm_loss"])) > 1e-3 * float(out["mlm_loss"])
+    gscale = max(float(q.grad.norm()) for _, q in model.named_parameters() if q.grad is not None)
+    n_checked = 0
+    for n, q in model.named_parameters():
+        if q.grad is None:
+            assert grads[n] is None or float(grads[n].abs().max()) == 0.0, n
+        else:
+            assert float((q.grad - grads[n]).norm()) <= 1e-4 * float(q.grad.norm()) + 1e-6 * gscale, n
+            n_checked += 1
+    assert n_checked >= 40
+
+
+@needs_reference
 def test_vqa_inference_vs_reference():
     model = ref_loader.build_reference_model(dict(vocab_size=1024, num_hidden_layers=2), tasks="vqa2", seed=4).eval()
     b = S.make_batch(3, max_len_b=20, vocab_size=1024, tasks="vqa2", seed=6, max_pred=1)

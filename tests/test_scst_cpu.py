@@ -73,14 +73,15 @@ def forced_decode_logp(p, vf, vp, input_ids, token_type_ids, position_ids, am, s
     return torch.cat(out, dim=1)
 
 
-def layout_logp(p, vf, vp, input_ids, token_type_ids, position_ids, am, sample_ids, mask_id, num_heads=12, Nv=100):
-    """One training forward of the oracle (embeddings / encoder / lm_head) on the scoring layout: log-probs [B, T]."""
+def layout_logp(p, vf, vp, input_ids, token_type_ids, position_ids, am, sample_ids, mask_id, num_heads=12, Nv=100, dropout=None):
+    """One training forward of the oracle (embeddings / encoder / lm_head) on the scoring layout: log-probs [B, T].  dropout: {site:
+    multiplier} for the "emb" and per-layer sites of that forward (vf / vp arrive projected: the caller drops them), None: dropout 0."""
     out_len = token_type_ids.shape[1]
     ids, seg, pos, mask, mpos = layout_mirror(input_ids, sample_ids, token_type_ids[:, :out_len], position_ids[:, :out_len],
                                               am[:, :out_len, :out_len], mask_id)
     dt = p["bert.embeddings.word_embeddings.weight"].dtype
-    emb, _ = O.embeddings(p, vf, vp, ids, seg, Nv, position_ids=pos)
-    seq = O.encoder(p, emb, O.extended_attention_mask(mask, dt), num_heads)[-1]
+    emb, _ = O.embeddings(p, vf, vp, ids, seg, Nv, position_ids=pos, drop=None if dropout is None else dropout.get("emb"))
+    seq = O.encoder(p, emb, O.extended_attention_mask(mask, dt), num_heads, dropout=dropout)[-1]
     logits = O.lm_head(p, O.gather_seq_out_by_pos(seq, mpos))
     return torch.log_softmax(logits, dim=-1).gather(2, sample_ids.unsqueeze(2)).squeeze(2)
 
