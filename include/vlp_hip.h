@@ -32,6 +32,8 @@ extern "C" {
  * changed), so a binding written against version 5 keeps working and the version number stays 5. */
 /* + vlp_scst_layout, vlp_embed_bwd_pos, vlp_token_logprob_fwd / vlp_token_logprob_bwd (self-critical sequence training), each with its own
  * argument struct: purely additive as well. */
+/* + vlp_bce_sparse_loss_fwd / vlp_bce_sparse_loss_bwd, vlp_vqa_answer_rows (VQA 2.0 on real data: answer targets as (index, score) pairs):
+ * purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -641,6 +643,22 @@ int vlp_bce_loss_fwd(const void* logits, int64_t ld, const void* labels_f32, int
                      float* loss, void* stream);
 int vlp_bce_loss_bwd(const void* logits, int64_t ld, const void* labels_f32, int64_t ldl, int32_t B, int32_t N,
                      const float* grad_scale, void* dlogits, int64_t ldd, void* stream);
+/* The same two with the target given as what a VQA question has -- at most S <= 16 (answer index, score) pairs per row -- instead of a dense
+ * f32 [B, N] array:  y[b, n] = ans_score[b, s] where ans_idx[b, s] == n, else 0.  ans_idx i32 [B, S] / ans_score f32 [B, S], contiguous;
+ * ans_idx == -1 marks an empty slot; the caller guarantees that the indices of a row are distinct and every index is -1 or in [0, N)
+ * (seq2seq_loader.py:355 builds the dense vector from such pairs).  The kernels are the dense kernels instantiated with another source of y
+ * (the pairs of the rows a block works on sit in LDS): same element order, same expression, same summation order, so loss[0] and dlogits equal
+ * the dense entry points' on the densified target bit for bit.  No atomics. */
+int vlp_bce_sparse_loss_fwd(const void* logits, int64_t ld, const int32_t* ans_idx, const float* ans_score, int32_t S, int32_t B, int32_t N,
+                            float* loss, void* stream);
+int vlp_bce_sparse_loss_bwd(const void* logits, int64_t ld, const int32_t* ans_idx, const float* ans_score, int32_t S, int32_t B, int32_t N,
+                            const float* grad_scale, void* dlogits, int64_t ldd, void* stream);
+/* VQA answer choice (modeling.py:1046 `argmax(pred[:, 1:]) + 1`, eval_vqa2.py): per row of logits f16 [rows, ld] the FIRST maximum over
+ * columns [first_col, N): out_ids[r] = its absolute column, out_vals[r] = the maximum.  Columns < first_col and >= N (row padding) are never
+ * chosen.  With ans_idx / ans_score (as above) given, out_scores[r] = the score row r lists for out_ids[r], 0 if it lists none (the soft
+ * accuracy of the prediction); with ans_idx == NULL out_scores is not touched (it may be NULL).  One launch, no fp32 copy of the logits. */
+int vlp_vqa_answer_rows(const void* logits, int64_t ld, int32_t rows, int32_t N, int32_t first_col, const int32_t* ans_idx,
+                        const float* ans_score, int32_t S, int64_t* out_ids, float* out_vals, float* out_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizers

@@ -239,6 +239,9 @@ SYMBOLS = {
     "vlp_mlm_loss_ls_bwd": (C.c_int, [C.POINTER(MlmLossLsBwdArgs), vp]),
     "vlp_bce_loss_fwd": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp]),
     "vlp_bce_loss_bwd": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, i64, vp]),
+    "vlp_bce_sparse_loss_fwd": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp]),
+    "vlp_bce_sparse_loss_bwd": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp, vp, i64, vp]),
+    "vlp_vqa_answer_rows": (C.c_int, [vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]),
     "vlp_sumsq": (C.c_int, [vp, i64, vp, vp, vp]),
     "vlp_sumsq_acc": (C.c_int, [vp, i64, vp, vp, vp]),
     "vlp_fused_adam": (C.c_int, [C.POINTER(FusedAdamArgs), vp]),
@@ -805,6 +808,45 @@ def bce_loss_fwd(logits, ld, labels, ldl, B, N, loss257):
 def bce_loss_bwd(logits, ld, labels, ldl, B, N, grad_scale, dlogits, ldd):
     _req_cuda(logits, labels, grad_scale, dlogits)
     _check(load().vlp_bce_loss_bwd(ptr(logits), ld, ptr(labels), ldl, B, N, ptr(grad_scale), ptr(dlogits), ldd, stream_ptr()))
+
+
+def _req_answers(ans_idx, ans_score, B):
+    """The [B, S] (answer index, score) pairs of vlp_amd.input_prep.SparseAnswers as the kernels read them."""
+    _req_cuda(ans_idx, ans_score)
+    if ans_idx.dtype != torch.int32 or ans_score.dtype != torch.float32 or ans_idx.dim() != 2 or ans_idx.shape != ans_score.shape \
+            or ans_idx.shape[0] != B or not (ans_idx.is_contiguous() and ans_score.is_contiguous()):
+        raise RuntimeError("vlp_amd: sparse answers must be contiguous idx int32 / score f32 [%d, S]" % B)
+    return ans_idx.shape[1]
+
+
+def bce_sparse_loss_fwd(logits, ld, ans_idx, ans_score, B, N, loss257):
+    """vlp_bce_loss_fwd with y given as [B, S] (answer index, score) pairs (idx -1 = empty slot) instead of the dense [B, N] target."""
+    _req_cuda(logits, loss257)
+    S = _req_answers(ans_idx, ans_score, B)
+    _check(load().vlp_bce_sparse_loss_fwd(ptr(logits), ld, ptr(ans_idx), ptr(ans_score), S, B, N, ptr(loss257), stream_ptr()))
+
+
+def bce_sparse_loss_bwd(logits, ld, ans_idx, ans_score, B, N, grad_scale, dlogits, ldd):
+    _req_cuda(logits, grad_scale, dlogits)
+    S = _req_answers(ans_idx, ans_score, B)
+    _check(load().vlp_bce_sparse_loss_bwd(ptr(logits), ld, ptr(ans_idx), ptr(ans_score), S, B, N, ptr(grad_scale), ptr(dlogits), ldd, stream_ptr()))
+
+
+def vqa_answer_rows(logits, ld, rows, N, first_col, out_ids, out_vals, ans_idx=None, ans_score=None, out_scores=None):
+    """Per row: first maximum over columns [first_col, N) -> out_ids (absolute column, int64 [rows]) / out_vals (f32 [rows]); with the
+    (ans_idx, ans_score) pairs given also out_scores[r] = the score the row lists for the chosen column, 0 if it lists none."""
+    _req_cuda(logits, out_ids, out_vals)
+    if out_ids.dtype != torch.int64 or out_vals.dtype != torch.float32 or out_ids.numel() < rows or out_vals.numel() < rows \
+            or not (out_ids.is_contiguous() and out_vals.is_contiguous()):
+        raise RuntimeError("vlp_amd: vqa_answer_rows needs contiguous out_ids int64 [rows] and out_vals f32 [rows]")
+    S = 0
+    if ans_idx is not None:
+        S = _req_answers(ans_idx, ans_score, rows)
+        _req_cuda(out_scores)
+        if out_scores.dtype != torch.float32 or out_scores.numel() < rows or not out_scores.is_contiguous():
+            raise RuntimeError("vlp_amd: vqa_answer_rows needs contiguous out_scores f32 [rows]")
+    _check(load().vlp_vqa_answer_rows(ptr(logits), ld, rows, N, first_col, ptr(ans_idx), ptr(ans_score) if ans_idx is not None else None, S,
+                                      ptr(out_ids), ptr(out_vals), ptr(out_scores) if ans_idx is not None else None, stream_ptr()))
 
 
 def sumsq(g16, n, out2, partial, accumulate=False):

@@ -693,6 +693,20 @@ extern "C" int vlp_kv_append(const void* qkv_new, int64_t ld, void* cache, int32
     return VLP_OK;
 }
 
+// block arg-max of 256 (value, index) candidates: largest value, smallest index on ties; the result is in sv[0] / si[0] for every thread
+DEVFN void argmax_block256(float best, int bi, float* sv, int* si) {
+    sv[threadIdx.x] = best;
+    si[threadIdx.x] = bi;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const float f = sv[threadIdx.x + o];
+            const int j = si[threadIdx.x + o];
+            if (f > sv[threadIdx.x] || (f == sv[threadIdx.x] && j < si[threadIdx.x])) { sv[threadIdx.x] = f; si[threadIdx.x] = j; }
+        }
+        __syncthreads();
+    }
+}
 // ids[r] = argmax_v logits[r, v] (first maximum), vals[r] = that logit   (torch.max(prediction_scores, -1), modeling.py:1228)
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const f16* logits, int64_t ld, int V, int64_t* ids, int64_t ids_stride, float* vals,
                                                           int64_t vals_stride) {
@@ -705,17 +719,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const f16* logits, int
         const float f = (float)x[v];
         if (f > best) { best = f; bi = v; }
     }
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const float f = sv[threadIdx.x + o];
-            const int j = si[threadIdx.x + o];
-            if (f > sv[threadIdx.x] || (f == sv[threadIdx.x] && j < si[threadIdx.x])) { sv[threadIdx.x] = f; si[threadIdx.x] = j; }
-        }
-        __syncthreads();
-    }
+    argmax_block256(best, bi, sv, si);
     if (threadIdx.x == 0) { ids[blockIdx.x * ids_stride] = si[0]; vals[blockIdx.x * vals_stride] = sv[0]; }
 }
 extern "C" int vlp_argmax_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, int64_t* ids, int64_t ids_stride, float* vals,
@@ -724,6 +728,42 @@ extern "C" int vlp_argmax_rows(const void* logits, int64_t ld, int32_t rows, int
     VLP_ENTER(logits, "vlp_argmax_rows");
     hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16*)logits, ld, V, ids, ids_stride, vals, vals_stride);
     VLP_CHECK_LAUNCH("vlp_argmax_rows");
+    return VLP_OK;
+}
+// VQA answer choice (modeling.py:1046 `argmax(pred[:, 1:]) + 1`): per row the first maximum over columns [first_col, N) as an ABSOLUTE column
+// index, the maximum itself, and -- with the row's (answer index, score) pairs given -- the score of the chosen answer (0 when no pair lists it).
+__global__ __launch_bounds__(256) void vqa_answer_rows_kernel(const f16* logits, int64_t ld, int N, int first_col, const int32_t* ans_idx,
+                                                              const float* ans_score, int S, int64_t* out_ids, float* out_vals, float* out_scores) {
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    const f16* x = logits + (int64_t)blockIdx.x * ld;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int v = first_col + threadIdx.x; v < N; v += 256) {
+        const float f = (float)x[v];
+        if (f > best) { best = f; bi = v; }
+    }
+    argmax_block256(best, bi, sv, si);
+    if (threadIdx.x == 0) {
+        // a row of -inf / NaN only leaves no candidate: answer first_col, as torch.max over an all -inf row gives index 0
+        const int id = si[0] == 0x7fffffff ? first_col : si[0];
+        out_ids[blockIdx.x] = id;
+        out_vals[blockIdx.x] = si[0] == 0x7fffffff ? (float)x[first_col] : sv[0];
+        if (ans_idx) {
+            float sc = 0.f;
+            for (int s = 0; s < S; ++s) sc = ans_idx[(int64_t)blockIdx.x * S + s] == id ? ans_score[(int64_t)blockIdx.x * S + s] : sc;
+            out_scores[blockIdx.x] = sc;
+        }
+    }
+}
+extern "C" int vlp_vqa_answer_rows(const void* logits, int64_t ld, int32_t rows, int32_t N, int32_t first_col, const int32_t* ans_idx,
+                                   const float* ans_score, int32_t S, int64_t* out_ids, float* out_vals, float* out_scores, void* stream) {
+    VLP_CHECK_ARG(logits && out_ids && out_vals && rows > 0 && first_col >= 0 && N > first_col && ld >= N, "vlp_vqa_answer_rows: bad args");
+    VLP_CHECK_ARG(!ans_idx || (ans_score && out_scores && S > 0 && S <= 16), "vlp_vqa_answer_rows: targets need ans_score, out_scores and 0 < S <= 16");
+    VLP_ENTER(logits, "vlp_vqa_answer_rows");
+    hipLaunchKernelGGL(vqa_answer_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16*)logits, ld, N, first_col, ans_idx, ans_score, S,
+                       out_ids, out_vals, out_scores);
+    VLP_CHECK_LAUNCH("vlp_vqa_answer_rows");
     return VLP_OK;
 }
 

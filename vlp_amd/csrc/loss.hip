@@ -383,15 +383,59 @@ extern "C" int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* 
 // ---------------------------------------------------------------------------------------------
 // BCE with logits.  loss = sum_{b,n} [max(x,0) - x*y + log(1 + exp(-|x|))] / (B*N) * N
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bce_fwd_kernel(const f16* x, int64_t ld, const float* y, int64_t ldl, int B, int N, float* part) {
+// Where y comes from is a template parameter (as the forbidden words of the top-k kernels are): SPARSE = false reads the dense f32 [B, ldl]
+// target, SPARSE = true reads the row's S (answer index, score) pairs -- y is the score of the pair whose index is the column, 0 when no
+// pair lists it (idx -1 = empty slot; the indices of a row are distinct, so at most one pair hits).  The pairs of the rows a block's current
+// 256-element tile touches sit in LDS.  Element -> thread assignment, the per-element expression and the summation order do not depend on
+// SPARSE, so both forms give the same bits for the same y.
+struct BceAnswers { const int32_t* idx; const float* score; int S; };
+// rows a tile of 256 consecutive elements of a [B, W] array can touch
+static inline int bce_tile_rows(int B, int64_t W) {
+    const int64_t r = 255 / W + 2;
+    return (int)(r < B ? r : B);
+}
+// the pairs of rows [b0, b0 + nr) -> LDS (contiguous in memory); visible to the block after its next __syncthreads()
+DEVFN void bce_pairs_load(const BceAnswers& sa, int64_t b0, int nr, int32_t* l_idx, float* l_sc) {
+    const int n = nr * sa.S;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        l_idx[j] = sa.idx[b0 * sa.S + j];
+        l_sc[j] = sa.score[b0 * sa.S + j];
+    }
+}
+DEVFN float bce_pairs_y(const int32_t* l_idx, const float* l_sc, int S, int r, int n) {
+    float yv = 0.f;
+    for (int s = 0; s < S; ++s) yv = l_idx[r * S + s] == n ? l_sc[r * S + s] : yv;
+    return yv;
+}
+template <bool SPARSE>
+__global__ __launch_bounds__(256) void bce_fwd_kernel(const f16* x, int64_t ld, const float* y, int64_t ldl, BceAnswers sa, int tile_rows, int B, int N,
+                                                      float* part) {
     __shared__ float sh[8];
+    extern __shared__ __attribute__((aligned(16))) char bce_smem[];
+    int32_t* l_idx = (int32_t*)bce_smem;
+    float* l_sc = (float*)(bce_smem + (size_t)tile_rows * sa.S * sizeof(int32_t));
     float s = 0.f;
     const int64_t total = (int64_t)B * N;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i / N;
-        const int n = (int)(i % N);
-        const float xv = (float)x[b * ld + n], yv = y[b * ldl + n];
-        s += fmaxf(xv, 0.f) - xv * yv + log1pf(__expf(-fabsf(xv)));
+    // block-uniform trip count (the tile's pairs are loaded between two barriers); thread t still walks base + t in ascending order
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        int64_t b0 = 0;
+        if constexpr (SPARSE) {
+            b0 = base / N;
+            const int64_t last = (base + blockDim.x - 1 < total ? base + blockDim.x - 1 : total - 1) / N;
+            __syncthreads();                                 // the previous tile's readers are done
+            bce_pairs_load(sa, b0, (int)(last - b0) + 1, l_idx, l_sc);
+            __syncthreads();
+        }
+        if (i < total) {
+            const int64_t b = i / N;
+            const int n = (int)(i % N);
+            const float xv = (float)x[b * ld + n];
+            float yv;
+            if constexpr (SPARSE) yv = bce_pairs_y(l_idx, l_sc, sa.S, (int)(b - b0), n);
+            else yv = y[b * ldl + n];
+            s += fmaxf(xv, 0.f) - xv * yv + log1pf(__expf(-fabsf(xv)));
+        }
     }
     s = block_reduce_sum(s, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -403,40 +447,88 @@ __global__ void bce_finish_kernel(const float* part, int n, float inv, float* lo
     s = block_reduce_sum(s, sh);
     if (threadIdx.x == 0) loss[0] = s * inv;
 }
+template <bool SPARSE>
+static int bce_fwd_launch(const char* who, const void* logits, int64_t ld, const float* labels, int64_t ldl, BceAnswers sa, int32_t B, int32_t N, float* loss,
+                          void* stream) {
+    // loss[1..257) is used as scratch: the caller passes a buffer of >= 257 floats
+    hipStream_t s = (hipStream_t)stream;
+    const int tile_rows = SPARSE ? bce_tile_rows(B, N) : 0;
+    const size_t lds = (size_t)tile_rows * sa.S * (sizeof(int32_t) + sizeof(float));
+    hipLaunchKernelGGL(bce_fwd_kernel<SPARSE>, dim3(256), dim3(256), lds, s, (const f16*)logits, ld, labels, ldl, sa, tile_rows, B, N, loss + 1);
+    VLP_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(256), 0, s, loss + 1, 256, 1.f / (float)B, loss);
+    VLP_CHECK_LAUNCH(who);
+    return VLP_OK;
+}
 extern "C" int vlp_bce_loss_fwd(const void* logits, int64_t ld, const void* labels, int64_t ldl, int32_t B, int32_t N, float* loss, void* stream) {
     VLP_CHECK_ARG(logits && labels && loss && B > 0 && N > 0 && ld >= N && ldl >= N, "vlp_bce_loss_fwd: bad args");
     VLP_ENTER(logits, "vlp_bce_loss_fwd");
-    // loss[1..257) is used as scratch: the caller passes a buffer of >= 257 floats
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bce_fwd_kernel, dim3(256), dim3(256), 0, s, (const f16*)logits, ld, (const float*)labels, ldl, B, N, loss + 1);
-    VLP_CHECK_LAUNCH("vlp_bce_loss_fwd");
-    hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(256), 0, s, loss + 1, 256, 1.f / (float)B, loss);
-    VLP_CHECK_LAUNCH("vlp_bce_loss_fwd(finish)");
-    return VLP_OK;
+    return bce_fwd_launch<false>("vlp_bce_loss_fwd", logits, ld, (const float*)labels, ldl, BceAnswers{nullptr, nullptr, 0}, B, N, loss, stream);
 }
-__global__ void bce_bwd_kernel(const f16* x, int64_t ld, const float* y, int64_t ldl, int B, int N, const float* gscale, f16* d, int64_t ldd) {
+#define BCE_SPARSE_MAX_S 16
+extern "C" int vlp_bce_sparse_loss_fwd(const void* logits, int64_t ld, const int32_t* ans_idx, const float* ans_score, int32_t S, int32_t B, int32_t N,
+                                       float* loss, void* stream) {
+    VLP_CHECK_ARG(logits && ans_idx && ans_score && loss && B > 0 && N > 0 && ld >= N && S > 0 && S <= BCE_SPARSE_MAX_S, "vlp_bce_sparse_loss_fwd: bad args");
+    VLP_ENTER(logits, "vlp_bce_sparse_loss_fwd");
+    return bce_fwd_launch<true>("vlp_bce_sparse_loss_fwd", logits, ld, nullptr, 0, BceAnswers{ans_idx, ans_score, S}, B, N, loss, stream);
+}
+template <bool SPARSE>
+__global__ __launch_bounds__(256) void bce_bwd_kernel(const f16* x, int64_t ld, const float* y, int64_t ldl, BceAnswers sa, int tile_rows, int B, int N,
+                                                      const float* gscale, f16* d, int64_t ldd) {
+    extern __shared__ __attribute__((aligned(16))) char bce_smem[];
+    int32_t* l_idx = (int32_t*)bce_smem;
+    float* l_sc = (float*)(bce_smem + (size_t)tile_rows * sa.S * sizeof(int32_t));
     const float c = gscale[0] / (float)B;
     const int64_t total = (int64_t)B * ldd;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i / ldd;
-        const int n = (int)(i % ldd);
-        float v = 0.f;
-        if (n < N) {
-            const float xv = (float)x[b * ld + n];
-            v = c * (1.f / (1.f + __expf(-xv)) - y[b * ldl + n]);
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        int64_t b0 = 0;
+        if constexpr (SPARSE) {
+            b0 = base / ldd;
+            const int64_t last = (base + blockDim.x - 1 < total ? base + blockDim.x - 1 : total - 1) / ldd;
+            __syncthreads();
+            bce_pairs_load(sa, b0, (int)(last - b0) + 1, l_idx, l_sc);
+            __syncthreads();
         }
-        d[i] = (f16)v;
+        if (i < total) {
+            const int64_t b = i / ldd;
+            const int n = (int)(i % ldd);
+            float v = 0.f;
+            if (n < N) {
+                const float xv = (float)x[b * ld + n];
+                float yv;
+                if constexpr (SPARSE) yv = bce_pairs_y(l_idx, l_sc, sa.S, (int)(b - b0), n);
+                else yv = y[b * ldl + n];
+                v = c * (1.f / (1.f + __expf(-xv)) - yv);
+            }
+            d[i] = (f16)v;
+        }
     }
+}
+template <bool SPARSE>
+static int bce_bwd_launch(const char* who, const void* logits, int64_t ld, const float* labels, int64_t ldl, BceAnswers sa, int32_t B, int32_t N,
+                          const float* grad_scale, void* dlogits, int64_t ldd, void* stream) {
+    const int64_t total = (int64_t)B * ldd;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    const int tile_rows = SPARSE ? bce_tile_rows(B, ldd) : 0;
+    const size_t lds = (size_t)tile_rows * sa.S * (sizeof(int32_t) + sizeof(float));
+    hipLaunchKernelGGL(bce_bwd_kernel<SPARSE>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, (const f16*)logits, ld, labels, ldl, sa, tile_rows, B, N,
+                       grad_scale, (f16*)dlogits, ldd);
+    VLP_CHECK_LAUNCH(who);
+    return VLP_OK;
 }
 extern "C" int vlp_bce_loss_bwd(const void* logits, int64_t ld, const void* labels, int64_t ldl, int32_t B, int32_t N, const float* grad_scale,
                                 void* dlogits, int64_t ldd, void* stream) {
     VLP_CHECK_ARG(logits && labels && grad_scale && dlogits && B > 0 && N > 0 && ld >= N && ldl >= N && ldd >= N, "vlp_bce_loss_bwd: bad args");
     VLP_ENTER(logits, "vlp_bce_loss_bwd");
-    const int64_t total = (int64_t)B * ldd;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(bce_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16*)logits, ld, (const float*)labels, ldl, B, N,
-                       grad_scale, (f16*)dlogits, ldd);
-    VLP_CHECK_LAUNCH("vlp_bce_loss_bwd");
-    return VLP_OK;
+    return bce_bwd_launch<false>("vlp_bce_loss_bwd", logits, ld, (const float*)labels, ldl, BceAnswers{nullptr, nullptr, 0}, B, N, grad_scale, dlogits, ldd,
+                                 stream);
+}
+extern "C" int vlp_bce_sparse_loss_bwd(const void* logits, int64_t ld, const int32_t* ans_idx, const float* ans_score, int32_t S, int32_t B, int32_t N,
+                                       const float* grad_scale, void* dlogits, int64_t ldd, void* stream) {
+    VLP_CHECK_ARG(logits && ans_idx && ans_score && grad_scale && dlogits && B > 0 && N > 0 && ld >= N && ldd >= N && S > 0 && S <= BCE_SPARSE_MAX_S,
+                  "vlp_bce_sparse_loss_bwd: bad args");
+    VLP_ENTER(logits, "vlp_bce_sparse_loss_bwd");
+    return bce_bwd_launch<true>("vlp_bce_sparse_loss_bwd", logits, ld, nullptr, 0, BceAnswers{ans_idx, ans_score, S}, B, N, grad_scale, dlogits, ldd, stream);
 }

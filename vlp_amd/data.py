@@ -15,6 +15,8 @@ by the last three characters of the image id, class probabilities, boxes), conve
     numpy releases the GIL for it, so the threads scale -- and one ndarray write per token field) and copying them to the GPU on a
     separate HIP stream, `depth` batches ahead; it yields the reference's 12-tuple (run_img2txt_dist.py:464) with the compact
     `MaskSpec` / `RawRegions` of vlp_amd.input_prep in the `input_mask` / `vis_pe` slots (the engine expands them on the device).
+    A VQA 2.0 example carries the question's answer indices as well; the prefetcher scores them on the host (SparseAnswers.from_answer_ids)
+    into two more pinned [B, 10] buffers and hands the batch's `ans_labels` out as a SparseAnswers (the loss kernels read the pairs).
     Every batch draws from its OWN `random.Random(batch_seed(seed, epoch, rank, step))`: its content is a pure function of those four
     numbers -- the same for 1 and K workers, independent of thread interleaving and of anything else that touches the global `random`.
 """
@@ -27,7 +29,7 @@ import threading
 import numpy as np
 import torch
 
-from .input_prep import MaskSpec, RawRegions, N_CLS
+from .input_prep import MaskSpec, RawRegions, SparseAnswers, N_CLS, N_ANSWERS, N_ANSWER_SLOTS
 
 FEAT_DIM, BOX_DIM = 2048, 6
 
@@ -229,8 +231,44 @@ def batch_seed(seed, epoch, rank, step):
     return x
 
 
+VQA_EXAMPLE_FORMAT = ("a VQA 2.0 example is [image id, question token ids, answer ids (<= %d indices into the %d-entry answer vocabulary, "
+                      "0 = unknown), question id]; a caption example is [image id, caption token ids]" % (N_ANSWER_SLOTS, N_ANSWERS))
+
+
+def examples_have_answers(examples):
+    """True for a list of VQA examples (4 fields), False for caption examples (2 fields); a file that mixes the two raises."""
+    kinds = set(len(e) for e in examples)
+    if kinds == {4}:
+        return True
+    if kinds == {2}:
+        return False
+    raise ValueError("token file: every example must have the same form, found examples with %s fields -- %s"
+                     % (" and ".join(str(k) for k in sorted(kinds)), VQA_EXAMPLE_FORMAT))
+
+
+def vqa_examples_from_imdb(imdb, tokenize, answer_index, store_key=None):
+    """The reference's VQA imdb array (entry 0 = header, then one dict per question with `image_name`, `feature_path`, `question_str`,
+    `question_id` and -- when the header says has_answer -- `answers`; seq2seq_loader.py:141-156, eval_vqa2.py:189-199) -> the token-file
+    list [[image id, question token ids, answer ids, question id], ...] in file order.  The project has no tokenizer and no answer
+    vocabulary: `tokenize(question_str)` -> token ids and `answer_index(answer_str)` -> index into the 3129-entry answer vocabulary (0 for
+    an unknown answer) come from the caller.  store_key(entry) -> the packed store's key of the question's image; default: `feature_path`
+    without its extension (the name the reference loads the features under).  Entries without answers (test splits) get an empty list."""
+    if store_key is None:
+        def store_key(entry):
+            return os.path.splitext(os.path.basename(entry["feature_path"]))[0]
+    out = []
+    for i in range(1, len(imdb)):
+        e = imdb[i]
+        answers = [int(answer_index(a)) for a in e.get("answers", [])]
+        if len(answers) > N_ANSWER_SLOTS:
+            raise ValueError("imdb entry %d has %d answers (at most %d)" % (i, len(answers), N_ANSWER_SLOTS))
+        out.append([store_key(e), [int(t) for t in tokenize(e["question_str"])], answers, e["question_id"]])
+    return out
+
+
 class BatchPrefetcher(object):
-    """Iterates device-resident batches.  `examples` is a list of (image id, caption token ids); every sample picks the s2s or the
+    """Iterates device-resident batches.  `examples` is a list of (image id, caption token ids), or of VQA examples (image id, question
+    token ids, answer ids, question id): then the 12th element of a batch is a SparseAnswers instead of the dummy [B, 1] zeros.  Every sample picks the s2s or the
     bidirectional preprocessor with probabilities (s2s_prob, 1 - s2s_prob) like Img2txtDataset.__getitem__ (:162-166).  `num_workers`
     threads (run_img2txt_dist.py:296-298 `--num_workers`) prepare up to `depth` batches ahead: host buffers are pinned and the H2D
     copies run on their own stream, so they overlap the training step; the consumer's stream waits on the copy event only.  Batches are
@@ -246,6 +284,7 @@ class BatchPrefetcher(object):
         balance_lengths (world > 1): every global batch of batch_size x world samples is dealt to the ranks by kept length
         (balanced_rank_split) instead of by index -- same sample SET per step as DistributedSampler, near-equal padding-free row counts."""
         self.store, self.examples, self.B = store, examples, batch_size
+        self.has_answers = examples_have_answers(examples)
         self.rank, self.world, self.epoch = rank, world, 0
         self.balance_lengths = bool(balance_lengths) and world > 1
         per_rank = -(-len(examples) // world)
@@ -274,6 +313,8 @@ class BatchPrefetcher(object):
                 "ids": pin(2, B, L, dt=torch.long), "pred": pin(3, B, P, dt=torch.long), "spec": pin(3, B, dt=torch.int32), "task": pin(B, dt=torch.long)}
         if self.n_vis_masked:
             host["vmp"] = pin(B, self.n_vis_masked, dt=torch.long)
+        if self.has_answers:
+            host["ans_idx"], host["ans_score"] = pin(B, N_ANSWER_SLOTS, dt=torch.int32), pin(B, N_ANSWER_SLOTS, dt=torch.float32)
         dev = {k: torch.empty_like(v, device=self.device) for k, v in host.items()}
         # numpy views of the host buffers, taken once (the fill writes whole arrays through them)
         views = {k: v.numpy() for k, v in host.items()}
@@ -294,9 +335,9 @@ class BatchPrefetcher(object):
         spec = np.empty((3, B), dtype=np.int32)
         task = np.empty((B,), dtype=np.int64)
         vmp = [None] * B
-        for j, (_, toks) in enumerate(batch_examples):
+        for j, ex in enumerate(batch_examples):
             proc = rng.choices(self.procs, weights=self.weights)[0]
-            t = proc(toks, rng)
+            t = proc(ex[1], rng)
             ids[j], seg[j], mid[j], mpos[j], mw[j] = t["input_ids"], t["segment_ids"], t["masked_ids"], t["masked_pos"], t["masked_weights"]
             spec[0, j], spec[1, j], spec[2, j] = t["len_a"] + 2, t["len_a"] + t["len_b"] + 3, int(t["is_s2s"])
             task[j] = t["task_idx"]
@@ -308,6 +349,8 @@ class BatchPrefetcher(object):
         hv["task"][...] = task
         if self.n_vis_masked:
             hv["vmp"][...] = np.asarray(vmp, dtype=np.int64)
+        if self.has_answers:                      # scored on the host straight into the pinned slots (no draw from rng)
+            SparseAnswers.from_answer_ids([ex[2] for ex in batch_examples], out=(hv["ans_idx"], hv["ans_score"]))
         lens_host = spec[1].tolist()              # second_end on the host: the padding-free step needs no device read-back
         if ev is None:
             for k in host:
@@ -328,7 +371,10 @@ class BatchPrefetcher(object):
         raw = RawRegions(d["bbox"], d["cls"])
         is_next = torch.full((B,), -1, dtype=torch.long, device=self.device)
         vis_masked_pos = d["vmp"] if self.n_vis_masked else torch.zeros(B, 0, dtype=torch.long, device=self.device)
-        ans = torch.zeros(B, 1, dtype=torch.float16, device=self.device)
+        if self.has_answers:
+            ans = SparseAnswers(d["ans_idx"], d["ans_score"], N_ANSWERS)      # from_answer_ids built them: the kernels' contract holds
+        else:
+            ans = torch.zeros(B, 1, dtype=torch.float16, device=self.device)
         # (input_ids, segment_ids, input_mask, lm_label_ids, masked_pos, masked_weights, is_next, task_idx, img, vis_masked_pos, vis_pe, ans)
         return (d["ids"][0], d["ids"][1], spec, d["pred"][0], d["pred"][1], d["pred"][2], is_next, d["task"], d["feat"], vis_masked_pos, raw, ans)
 

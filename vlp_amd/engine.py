@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as K
 from . import tuning
-from .input_prep import MaskSpec, RawRegions
+from .input_prep import MaskSpec, RawRegions, SparseAnswers
 
 ALIGN = 64            # elements; every parameter starts on a 128-byte boundary inside its flat buffer
 NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")    # run_img2txt_dist.py:395
@@ -871,10 +871,18 @@ class Engine(object):
         return ws["loss"][0:1]
 
     def vqa_loss(self, st, ans_labels):
-        """modeling.py:1140: BCEWithLogits(mean) * num_answers."""
+        """modeling.py:1140: BCEWithLogits(mean) * num_answers.  ans_labels: the dense [B, num_answers] target, or a SparseAnswers -- then the
+        kernels read the (index, score) pairs; the choice is recorded on st (task_labels) so that backward follows this forward."""
         ws = st.ws
-        st.task_labels = ans_labels.to(torch.float32).contiguous()
         NA = self._model().num_answers
+        if isinstance(ans_labels, SparseAnswers):
+            ans_labels.check(st.B, NA)
+            if not (ans_labels.idx.is_cuda and ans_labels.score.is_cuda):
+                raise RuntimeError("SparseAnswers must live on the GPU (there is no CPU path)")
+            st.task_labels = SparseAnswers(ans_labels.idx.contiguous(), ans_labels.score.contiguous(), ans_labels.verified_for)
+            K.bce_sparse_loss_fwd(ws["vq_logits"], ws["NAp"], st.task_labels.idx, st.task_labels.score, st.B, NA, ws["loss"])
+            return ws["loss"][0:1]
+        st.task_labels = ans_labels.to(torch.float32).contiguous()
         K.bce_loss_fwd(ws["vq_logits"], ws["NAp"], st.task_labels, st.task_labels.stride(0), st.B, NA, ws["loss"])
         return ws["loss"][0:1]
 
@@ -1403,7 +1411,10 @@ class Engine(object):
         # ---- heads ------------------------------------------------------------------------------------
         if task == "vqa2":
             NA, NAp = model.num_answers, ws["NAp"]
-            K.bce_loss_bwd(ws["vq_logits"], NAp, st.task_labels, st.task_labels.stride(0), B, NA, gscale, ws["vq_dlogits"], NAp)
+            if isinstance(st.task_labels, SparseAnswers):
+                K.bce_sparse_loss_bwd(ws["vq_logits"], NAp, st.task_labels.idx, st.task_labels.score, B, NA, gscale, ws["vq_dlogits"], NAp)
+            else:
+                K.bce_loss_bwd(ws["vq_logits"], NAp, st.task_labels, st.task_labels.stride(0), B, NA, gscale, ws["vq_dlogits"], NAp)
             self._tn(ws["vq_dlogits"], ws["vq_a1"], self.G("ans_classifier.2.weight"), B, NA, 2 * H, ws, beta, bias=self.G("ans_classifier.2.bias"))
             self._nt(ws["vq_dlogits"], sh["a2T"], ws["vq_dz1"], B, 2 * H, NAp, mul_src=ws["vq_a1"], mul_mode=K.MUL_RELU_MASK)
             self._tn(ws["vq_dz1"], ws["vq_e"], self.G("ans_classifier.0.weight"), B, 2 * H, H, ws, beta, bias=self.G("ans_classifier.0.bias"))

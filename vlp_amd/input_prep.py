@@ -8,9 +8,11 @@ int64 [L, L] attention mask -- 1.7 MB of fp32 + 223 KB of mask per sample that t
     img       f16 [B, 100, 2048]                      (as stored; BertForPreTrainingLossMask already accepts fp16 features)
     RawRegions(bbox f32 [B, 100, 6], cls_prob f16 [B, 100, 1601])     in place of `vis_pe`
     MaskSpec(second_st, second_end, is_s2s)  int32 [B]                  in place of `attention_mask`
+    SparseAnswers(idx int32 [B, 10], score f32 [B, 10])                 in place of the dense f32 [B, 3129] VQA `ans_labels`
 
 and the HIP engine builds the packed masks (vlp_mask_build) and the K-padded box/class encoding (vlp_vis_pe_prep) directly in the
-buffers its kernels read.  Both objects are accepted wherever the reference API takes `vis_pe` / `attention_mask`
+buffers its kernels read; the BCE loss kernels look a column's target up in the row's (index, score) pairs (vlp_bce_sparse_loss_fwd / _bwd).
+The objects are accepted wherever the reference API takes `vis_pe` / `attention_mask` / `ans_labels`
 (BertForPreTrainingLossMask.forward); the dense tensors keep working unchanged.
 """
 import collections
@@ -78,3 +80,95 @@ class MaskSpec(_MaskSpecBase):
         k = torch.arange(L, device=self.second_st.device).view(1, 1, L)
         tri = (k < st) | ((q >= st) & (q < en) & (k >= st) & (k <= q))
         return torch.where(s2s.bool(), tri, (k < en).expand(-1, L, -1)).to(torch.long)
+
+
+N_ANSWERS = 3129        # entries of the VQA 2.0 answer vocabulary, hard-coded in the reference (modeling.py:1029)
+N_ANSWER_SLOTS = 10     # a VQA 2.0 question has 10 human answers, hence at most 10 distinct ones
+MAX_ANSWER_SLOTS = 16   # what the kernels hold per row (vlp_bce_sparse_loss_fwd / _bwd, vlp_vqa_answer_rows)
+
+_SparseAnswersBase = collections.namedtuple("SparseAnswers", ["idx", "score", "verified_for"])
+_SparseAnswersBase.__new__.__defaults__ = (None,)
+
+
+class SparseAnswers(_SparseAnswersBase):
+    """The VQA soft target of one batch as (answer index, score) pairs in place of the dense f32 [B, num_answers] `ans_labels`
+    (seq2seq_loader.py:355 `ans_proc(...)['answers_scores']`): idx int32 [B, S], score f32 [B, S], S <= 16 (the loader uses 10);
+    idx == -1 marks an empty slot.  The dense target it stands for is y[b, idx[b, s]] = score[b, s], 0 elsewhere.
+    Contract the loss kernels rely on: the indices of a row are distinct, and every index is -1 or in [0, num_answers).
+    verified_for (optional, host int): the num_answers this instance is KNOWN to satisfy the contract for -- from_answer_ids sets it and
+    .to() carries it along, so check() costs the training path no device read-back."""
+    __slots__ = ()
+
+    @staticmethod
+    def answer_scores(answer_ids, unk_index=0):
+        """[(answer index, score)] of one question's answer indices, distinct answers in order of first appearance, the unknown index left out.
+        Pythia's VQAAnswerProcessor.compute_answers_scores, the soft VQA accuracy: for each distinct answer, the mean over the n leave-one-out
+        subsets of the n given answers of min(1, matches in the subset / 3) -- for n = 10 an answer given c = 1, 2, 3, >= 4 times scores
+        0.3, 0.6, 0.9, 1.0.  Pythia's source is not part of this project or of the reference checkout; the rule is written from its
+        published definition (as vlp_amd.scst.CiderD is from coco-caption's)."""
+        answer_ids = [int(a) for a in answer_ids]
+        n = len(answer_ids)
+        out = []
+        for a in answer_ids:
+            if a == unk_index or any(a == seen for seen, _ in out):
+                continue
+            c = answer_ids.count(a)
+            # subset j leaves answer j out: it holds c - 1 matches when answer j is `a`, else c
+            accs = [min(1.0, float(c - (1 if answer_ids[j] == a else 0)) / 3) for j in range(n)]
+            out.append((a, sum(accs) / len(accs)))
+        return out
+
+    @staticmethod
+    def from_answer_ids(answer_ids, unk_index=0, slots=N_ANSWER_SLOTS, num_answers=N_ANSWERS, out=None):
+        """answer_ids: per question the list of its (<= 10) indices into the answer vocabulary -> SparseAnswers on the host, scored by
+        answer_scores().  A row of unknown answers only has every slot empty.  out: optional (idx, score) numpy arrays [B, slots] to fill
+        (the loader's pinned buffers); the result then wraps them."""
+        import numpy as np
+        B = len(answer_ids)
+        if not 0 < slots <= MAX_ANSWER_SLOTS:
+            raise ValueError("SparseAnswers: slots must be in 1..%d" % MAX_ANSWER_SLOTS)
+        if out is None:
+            out = (np.empty((B, slots), dtype=np.int32), np.empty((B, slots), dtype=np.float32))
+        idx, score = out
+        idx[...] = -1
+        score[...] = 0.0
+        for b, answers in enumerate(answer_ids):
+            pairs = SparseAnswers.answer_scores(answers, unk_index)
+            if len(pairs) > slots:
+                raise ValueError("SparseAnswers: question %d has %d distinct answers, more than the %d slots" % (b, len(pairs), slots))
+            for s, (a, sc) in enumerate(pairs):
+                if not 0 <= a < num_answers:
+                    raise ValueError("SparseAnswers: answer index %d of question %d is outside [0, %d)" % (a, b, num_answers))
+                idx[b, s], score[b, s] = a, sc
+        return SparseAnswers(torch.from_numpy(idx), torch.from_numpy(score), num_answers)
+
+    def to(self, device, non_blocking=False):
+        return SparseAnswers(self.idx.to(device, non_blocking=non_blocking), self.score.to(device, non_blocking=non_blocking), self.verified_for)
+
+    @property
+    def shape(self):
+        return tuple(self.idx.shape)
+
+    def check(self, B, NA):
+        """Layout always; the kernels' contract (distinct indices per row, each -1 or in [0, NA)) from `verified_for` when the instance carries
+        it (the loader's always do: no device read-back), else by looking at the values (a read-back when they live on the GPU: only
+        instances assembled by hand from device tensors pay it)."""
+        S = self.idx.shape[1] if self.idx.dim() == 2 else 0
+        if self.idx.dtype != torch.int32 or self.score.dtype != torch.float32 or tuple(self.idx.shape) != (B, S) \
+                or tuple(self.score.shape) != (B, S) or not 0 < S <= MAX_ANSWER_SLOTS:
+            raise RuntimeError("SparseAnswers must be idx int32 / score f32 [%d, S] with 1 <= S <= %d" % (B, MAX_ANSWER_SLOTS))
+        if self.verified_for is not None and self.verified_for <= NA:
+            return
+        idx = self.idx.cpu().to(torch.long)
+        if bool(((idx < -1) | (idx >= NA)).any()):
+            raise RuntimeError("SparseAnswers: every answer index must be -1 (empty slot) or in [0, %d)" % NA)
+        srt = idx.sort(dim=1).values
+        if bool(((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any()):
+            raise RuntimeError("SparseAnswers: the answer indices of a row must be distinct")
+
+    def dense(self, num_answers):
+        """The f32 [B, num_answers] target this stands for (host/debug helper; the engine never builds it)."""
+        y = torch.zeros(self.idx.shape[0], num_answers, dtype=torch.float32, device=self.idx.device)
+        b, s = torch.nonzero(self.idx >= 0, as_tuple=True)
+        y[b, self.idx[b, s].to(torch.long)] = self.score[b, s]
+        return y

@@ -22,6 +22,7 @@ from torch import nn
 
 from . import _lib as K
 from .engine import Engine
+from .input_prep import MaskSpec, SparseAnswers
 from .loss import LabelSmoothingLoss
 
 logger = logging.getLogger(__name__)
@@ -562,6 +563,38 @@ class BertForPreTrainingLossMask(PreTrainedBertModel):
         self.last_mlm_logits = eng.mlm_logits(st)
         loss, pt_loss = live(raw, "img2txt")
         return loss.reshape(()), pt_loss, zero1                         # :1143 shapes ([], [1] | [], [1])
+
+    def answer(self, vis_feats, vis_pe, input_ids, token_type_ids=None, attention_mask=None, answers=None):
+        """VQA prediction (:1039-1047, eval_vqa2.py:237-244) for a batch of questions: (ans_idx int64 [B], ans_logit f32 [B], ans_score f32 [B]
+        or None).  ans_idx = argmax(logits[:, 1:]) + 1 (first maximum; index 0, the unknown answer, is never predicted), ans_logit its logit;
+        with `answers` (a SparseAnswers on the GPU: the questions' human answers) ans_score is the soft accuracy of each prediction -- the
+        score the question lists for it, 0 when it lists none.  One engine forward without dropout, then ONE vlp_vqa_answer_rows launch
+        (no fp32 copy of the logits, no read-back).  The forward is padding-free when attention_mask is a MaskSpec that carries the lengths
+        on the host: the packed step is defined for gradient-enabled forwards (Engine.VARLEN), so that is the forward taken then -- what it
+        adds (the transposed mask, the W^T shadows) runs on the side stream.  Sets last_vqa_logits."""
+        if self.tasks != "vqa2":
+            raise RuntimeError("answer() needs a model built with tasks='vqa2'")
+        eng = self.engine
+        if token_type_ids is None:
+            token_type_ids = torch.zeros_like(input_ids)
+        B, NA = input_ids.shape[0], self.num_answers
+        packed = isinstance(attention_mask, MaskSpec) and attention_mask.lens_host is not None
+        with torch.enable_grad() if packed else torch.no_grad():
+            st = eng.forward(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask, None, False, False, True)
+        self.last_vqa_logits = eng.vqa_logits(st)
+        dev = input_ids.device
+        ans_idx = torch.empty(B, dtype=torch.long, device=dev)
+        ans_logit = torch.empty(B, dtype=torch.float32, device=dev)
+        ans_score = None
+        if answers is not None:
+            if not isinstance(answers, SparseAnswers):
+                raise TypeError("answer(answers=...) takes a vlp_amd.input_prep.SparseAnswers")
+            answers.check(B, NA)
+            ans_score = torch.empty(B, dtype=torch.float32, device=dev)
+            K.vqa_answer_rows(st.ws["vq_logits"], st.ws["NAp"], B, NA, 1, ans_idx, ans_logit, answers.idx.contiguous(), answers.score.contiguous(), ans_score)
+        else:
+            K.vqa_answer_rows(st.ws["vq_logits"], st.ws["NAp"], B, NA, 1, ans_idx, ans_logit)
+        return ans_idx, ans_logit, ans_score
 
 
 class BertForSeq2SeqDecoder(PreTrainedBertModel):

@@ -123,7 +123,8 @@ def build_parser():
                    help="train on seeded synthetic batches (vlp_amd/synthetic.py) for this many steps per epoch")
     p.add_argument("--packed_features", default="", help="directory of a vlp_amd.data packed region store (write_packed / pack_from_h5)")
     p.add_argument("--token_file", default="", help="json list of [image id, [caption token ids]] (captions pre-tokenised with the "
-                                                     "reference's WordPiece vocabulary); used with --packed_features")
+                                                     "reference's WordPiece vocabulary), or for --tasks vqa2 of [image id, [question token ids], "
+                                                     "[answer ids], question id] (vlp_amd.data.vqa_examples_from_imdb); used with --packed_features")
     p.add_argument("--num_hidden_layers", type=int, default=None, help="override the config's depth (plumbing tests)")
     p.add_argument("--optim_format", default="vlp", choices=["vlp", "apex"],
                    help="layout of optim.N.bin: 'vlp' = the engine's flat buffers (+ dropout stream position: bit-exact resume), 'apex' = the "
@@ -338,10 +339,12 @@ def build_packed_loader(args, device):
     s2s / bidirectional preprocessors drawn per sample with --s2s_prob / --bi_prob.  With world_size > 1 the per-epoch order is
     DistributedSampler's (:295, 455): one global permutation per epoch (seeded by the epoch, the same on every rank), padded by
     wrapping around so that every rank gets ceil(N / W) samples, rank r taking every W-th element (vlp_amd.data.distributed_sampler_indices)."""
-    from .data import BatchPrefetcher, PackedRegionStore, TextPreprocessor
+    from .data import BatchPrefetcher, PackedRegionStore, TextPreprocessor, examples_have_answers, VQA_EXAMPLE_FORMAT
     store = PackedRegionStore(args.packed_features)
     with open(args.token_file) as f:
-        examples = [(e[0], e[1]) for e in json.load(f)]
+        examples = [tuple(e) if len(e) == 4 else (e[0], e[1]) for e in json.load(f)]
+    if args.tasks == "vqa2" and not examples_have_answers(examples):     # (a file that mixes the two forms raises in there)
+        raise ValueError("--tasks vqa2 needs answers, and --token_file %s has none: %s" % (args.token_file, VQA_EXAMPLE_FORMAT))
     kw = dict(max_pred=args.max_pred, mask_prob=args.mask_prob, vocab_size=KNOWN_VOCABS.get(args.bert_model, 28996), cls_id=synthetic.CLS_ID,
               sep_id=synthetic.SEP_ID, mask_id=synthetic.MASK_ID, unk_id=synthetic.UNK_ID, max_len=args.max_seq_length, max_len_b=args.max_len_b,
               len_vis_input=args.len_vis_input, new_segment_ids=args.new_segment_ids, trunc_seg=args.trunc_seg,
