@@ -34,6 +34,7 @@ extern "C" {
  * argument struct: purely additive as well. */
 /* + vlp_bce_sparse_loss_fwd / vlp_bce_sparse_loss_bwd, vlp_vqa_answer_rows (VQA 2.0 on real data: answer targets as (index, score) pairs):
  * purely additive as well. */
+/* + vlp_cider_d / vlp_cider_d_workspace_bytes (the SCST reward on the device): purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -635,6 +636,37 @@ typedef struct {
     int32_t rows, V;
 } vlp_token_logprob_bwd_args;
 int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* stream);
+
+/* CIDEr-D of id strings (SCST, the reward the reference computes on the host: scst_utils.py:36-63 with pycocoevalcap's Cider(df='corpus')).
+ * The specification is vlp_amd/scst.py CiderD.compute_score on the strings array_to_str makes:
+ *   - a string is the ids of a row up to AND INCLUDING the first 0, or all T ids without one; nothing behind the first 0 is read as text.
+ *     Ids are vocabulary indices, 0 <= id < 2^31;
+ *   - hypothesis row i (of mult*G) is scored against the references of group i % G; group g has R reference rows of which the first
+ *     ref_count[g] (clamped to 1..R; NULL = R) are valid, the others are never read as text;
+ *   - n-grams of order 1..4 are counted exactly (token comparison, no hashing).  df(g) = mult * the number of groups whose valid references
+ *     hold g; ref_len = log(mult*G); weight = tf * (ref_len - log(max(1, df))), also for a hypothesis n-gram that no reference holds; one
+ *     L2 norm per order; a string's length is its number of bigram occurrences;
+ *   - per reference and order sum_g min(h_g, r_g) * r_g, divided by the two norms when both are non-zero, times
+ *     exp(-(len_h - len_r)^2 / (2 sigma^2)); scores[i] = 10 * the mean over the orders, averaged over the group's valid references;
+ *   - reward (optional, mult == 2: rows [0, G) the samples, [G, 2G) the greedy captions) [g] = scores[g] - scores[G + g], one fp32
+ *     subtraction of the two stored scores.
+ * fp32 with the accurate logf / expf / sqrtf, every sum in a fixed order, no atomics: equal inputs give bit-equal outputs.  Two launches
+ * (counting, scoring), no host involvement, capturable.  Nothing is written outside scores[0, mult*G), reward[0, G) and the workspace.
+ * Accepted: 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult 1 or 2, hyp_ld / ref_ld >= T, ref_group_stride >= (R-1) * ref_ld + T (strides in
+ * elements), sigma > 0, a 16-byte aligned workspace of vlp_cider_d_workspace_bytes() bytes (0 for a refused shape).  Anything else -- a
+ * workspace that is too small included -- returns VLP_ERR_BAD_ARG before anything is launched. */
+typedef struct {
+    const int64_t* hyp; int64_t hyp_ld;                        /* [mult*G, T]; row i is scored against group i % G */
+    const int64_t* ref; int64_t ref_group_stride, ref_ld;      /* [G, R, T] */
+    const int32_t* ref_count;                                  /* [G], 1..R references of each group are valid; NULL = all R */
+    int32_t G, R, T, mult;                                     /* mult = hypotheses per group (SCST: 2 = sample, greedy) */
+    float sigma;                                               /* 6.0 */
+    float* scores;                                             /* [mult*G] out */
+    float* reward;                                             /* optional [G] out: scores[g] - scores[G+g]; needs mult == 2 */
+    void* workspace; int64_t workspace_bytes;
+} vlp_cider_d_args;
+int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
+int vlp_cider_d(const vlp_cider_d_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

@@ -1,6 +1,6 @@
 """Per-phase timing of one self-critical (--scst) training step on one MI355X -> profiles/scst_step.json.
 
-    python tools/scst_bench.py [--batches 16 64] [--steps 5] [--warmup 2] [--out profiles/scst_step.json]
+    python tools/scst_bench.py [--batches 16 64] [--steps 5] [--warmup 2] [--reward host|device] [--refs R] [--out profiles/scst_step.json]
 
 Every step is the entry script's own vlp_amd.run_img2txt_dist.scst_step (the model's sample_mode paths, the reward, RewardCriterion, the fp16
 optimizer) at L = 123 (COCO's --max_len_b 20), 12 layers, the bert-base-cased vocabulary, on a seeded synthetic batch.  scst_step reports the
@@ -10,10 +10,15 @@ forward into its two halves:
   sample_decode    the sampled decode of the train() forward (not graph-planned: its seed changes every step)
   score_fwd        Engine.score_samples: scoring layout + training forward + LM head + log-probs
   reward_host      caption cleaning, one device -> host copy, CIDEr-D of 2B captions on the host, the rewards back
+  reward_device    (--reward device, in place of reward_host) caption cleaning and the vlp_cider_d kernels; nothing leaves the device
   score_bwd        RewardCriterion and the backward of the scoring forward
   optimizer        FP16_Optimizer_State(FusedAdam).step()
 Each mark synchronises the device first (host wall clock), so phases do not overlap; their sum is a serialised step.  Nothing is asserted:
-this records what is measured."""
+this records what is measured.
+--refs R > 1 scores every sample against R references (a CaptionRefs: the sample's ground truth and R - 1 seeded synthetic captions of the
+same lengths) instead of its one ground truth.  The default --out is profiles/scst_step.json for the default mode (--reward host --refs 1)
+and profiles/scst_reward_device.json otherwise; a run ADDS its records to the runs of an existing --out file (each names its reward and
+refs), so the four modes of one session end up in one record."""
 import argparse
 import json
 import os
@@ -37,7 +42,21 @@ NOTE = ("every phase ends with a device synchronisation (host wall clock), so ph
         "(its seed changes every step)")
 
 
-def bench(B, steps, warmup, dev):
+def with_refs(batch, R, dev, seed=11):
+    """The batch with a CaptionRefs of R references per sample in its 12th slot: row 0 the sample's own ground-truth ids, rows 1..R-1 the
+    same rows with their words redrawn (same lengths, [SEP] and padding kept)."""
+    from vlp_amd.input_prep import CaptionRefs
+    gt = batch.input_ids[:, 102:]
+    g = torch.Generator().manual_seed(seed)
+    rows = [gt]
+    for _ in range(R - 1):
+        words = torch.randint(1000, 1200, gt.shape, generator=g).to(dev)
+        rows.append(torch.where((gt != 0) & (gt != S.SEP_ID), words, gt))
+    refs = CaptionRefs(torch.stack(rows, 1).contiguous(), torch.full((gt.shape[0],), R, dtype=torch.int32, device=dev))
+    return batch._replace(ans_labels=refs)
+
+
+def bench(B, steps, warmup, dev, reward="host", refs=1):
     cfg = BertConfig(28996, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, type_vocab_size=6)
     torch.manual_seed(0)
     m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=100).half().to(dev)
@@ -47,8 +66,11 @@ def bench(B, steps, warmup, dev):
               {"params": [q for n, q in named if any(x in n for x in nd)], "weight_decay": 0.0}]
     opt = FP16_Optimizer_State(FusedAdam(groups, lr=1e-6, bias_correction=False, max_grad_norm=1.0), dynamic_loss_scale=True)
     batch = S.batch_to(S.make_batch(B, max_len_b=20, len_vis_input=100, max_pred=0, mask_prob=0.0, seed=7), dev, half=True)
+    if refs > 1:
+        batch = with_refs(batch, refs, dev)
     crit = RewardCriterion()
-    times = {k: [] for k in PHASES}
+    phases = tuple("reward_device" if (k == "reward_host" and reward == "device") else k for k in PHASES)
+    times = {k: [] for k in phases}
     clock = {"t": 0.0, "rec": False}
 
     def mark(phase):
@@ -68,11 +90,11 @@ def bench(B, steps, warmup, dev):
     for it in range(warmup + steps):
         clock["rec"] = it >= warmup
         mark(None)                          # the step starts here
-        R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark)
+        R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark, reward_on=reward)
     L = batch.input_ids.shape[1]
     out = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v))} for k, v in times.items()}
-    out["step_ms_sum_of_medians"] = float(sum(out[k]["median_ms"] for k in PHASES))
-    out.update(B=B, L=L, T=L - 102, scoring_length=102 + 2 * (L - 102) - 1, layers=12, vocab=28996, steps=steps, warmup=warmup)
+    out["step_ms_sum_of_medians"] = float(sum(out[k]["median_ms"] for k in phases))
+    out.update(B=B, L=L, T=L - 102, scoring_length=102 + 2 * (L - 102) - 1, layers=12, vocab=28996, steps=steps, warmup=warmup, reward=reward, refs=refs)
     return out
 
 
@@ -81,13 +103,30 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scst_step.json"))
+    ap.add_argument("--reward", default="host", choices=["host", "device"], help="where scst_step computes the CIDEr-D reward")
+    ap.add_argument("--refs", type=int, default=1, help="references per sample (1 = the sample's ground truth, as the entry script's default)")
+    ap.add_argument("--out", default=None, help="default: profiles/scst_step.json for --reward host --refs 1, else profiles/scst_reward_device.json")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "scst_step.json" if (a.reward == "host" and a.refs == 1) else "scst_reward_device.json")
     dev = torch.device("cuda")
-    res = {"device": torch.cuda.get_device_name(0), "note": NOTE, "runs": [],
-           "tool": "tools/scst_bench.py --batches %s --steps %d --warmup %d" % (" ".join(map(str, a.batches)), a.steps, a.warmup)}
+    tool = "tools/scst_bench.py --batches %s --steps %d --warmup %d --reward %s --refs %d" % (" ".join(map(str, a.batches)), a.steps, a.warmup, a.reward,
+                                                                                             a.refs)
+    res = {"device": torch.cuda.get_device_name(0), "note": NOTE, "runs": []}
+    yardstick = os.path.realpath(a.out) == os.path.realpath(os.path.join(ROOT, "profiles", "scst_step.json"))
+    if yardstick:                                 # the single-mode record of the default path: always written afresh
+        res["tool"] = tool
+    else:
+        res["tools"] = []
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                old = json.load(f)
+            for k, v in old.items():              # earlier runs, and what tests/test_81_scst_reward_gpu.py's report() keeps under "test_81"
+                if k not in ("device", "note"):
+                    res[k] = v
+        res["tools"].append(tool)
     for B in a.batches:
-        r = bench(B, a.steps, a.warmup, dev)
+        r = bench(B, a.steps, a.warmup, dev, a.reward, a.refs)
         print(json.dumps(r, sort_keys=True), flush=True)
         res["runs"].append(r)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

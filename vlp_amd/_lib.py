@@ -143,6 +143,12 @@ class TransposeDesc(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("lds", i64), ("ldd", i64), ("rows", i32), ("cols", i32), ("rows_pad", i32), ("reserved", i32)]
 
 
+class CiderDArgs(C.Structure):
+    _fields_ = [("hyp", vp), ("hyp_ld", i64), ("ref", vp), ("ref_group_stride", i64), ("ref_ld", i64), ("ref_count", vp),
+                ("G", i32), ("R", i32), ("T", i32), ("mult", i32), ("sigma", f32), ("scores", vp), ("reward", vp),
+                ("workspace", vp), ("workspace_bytes", i64)]
+
+
 class MlmLossFwdArgs(C.Structure):
     _fields_ = [("logits", vp), ("ld_logits", i64), ("labels", vp), ("weights", vp), ("loss", vp), ("lse", vp), ("coef", vp),
                 ("row_loss", vp), ("B", i32), ("P", i32), ("V", i32), ("drop_worst_ratio", f32)]
@@ -233,6 +239,8 @@ SYMBOLS = {
     "vlp_vqa_mul_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "vlp_relu_dropout_bwd": (C.c_int, [vp, vp, vp, i64, i64, f32, u64, u32, vp]),
     "vlp_gelu_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
+    "vlp_cider_d_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "vlp_cider_d": (C.c_int, [C.POINTER(CiderDArgs), vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
     "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
@@ -669,6 +677,36 @@ def token_logprob_bwd(logits, ld, ids, lse, g, dlogits, ldd, rows, V):
     _req_cuda(logits, ids, lse, g, dlogits)
     a = TokenLogprobBwdArgs(ptr(logits), ld, ptr(ids), ptr(lse), ptr(g), ptr(dlogits), ldd, rows, V)
     _check(load().vlp_token_logprob_bwd(C.byref(a), stream_ptr()))
+
+
+def cider_d_workspace_bytes(G, R, T, mult):
+    """0 for a shape vlp_cider_d refuses."""
+    return int(load().vlp_cider_d_workspace_bytes(G, R, T, mult))
+
+
+def cider_d(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, workspace=None):
+    """CIDEr-D on the device (include/vlp_hip.h vlp_cider_d): hyp int64 [mult*G, T] (row i against group i % G), ref int64 [G, R, T],
+    ref_count int32 [G] or None (all R valid), scores f32 [mult*G], reward f32 [G] or None (scores[:G] - scores[G:], mult == 2).  Rows may be
+    strided, the ids of a row are contiguous.  workspace: the caller's uint8 device buffer of cider_d_workspace_bytes() (16-byte aligned);
+    None = a fresh allocation of this call (torch's caching allocator: no synchronisation, ordered on the current stream, fine under graph
+    capture).  Launches on the current stream."""
+    _req_cuda(hyp, ref, ref_count, scores, reward, workspace)
+    if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
+        raise RuntimeError("vlp_amd.cider_d: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
+    G, R, T = ref.shape
+    if hyp.shape[0] != mult * G or hyp.shape[1] != T:
+        raise RuntimeError("vlp_amd.cider_d: hyp must be [%d, %d]" % (mult * G, T))
+    if ref_count is not None and (ref_count.dtype != torch.int32 or not ref_count.is_contiguous() or ref_count.numel() != G):
+        raise RuntimeError("vlp_amd.cider_d: ref_count must be contiguous int32 [%d]" % G)
+    if scores.dtype != torch.float32 or not scores.is_contiguous() or scores.numel() < mult * G:
+        raise RuntimeError("vlp_amd.cider_d: scores must be contiguous f32 [%d]" % (mult * G))
+    if reward is not None and (reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() < G):
+        raise RuntimeError("vlp_amd.cider_d: reward must be contiguous f32 [%d]" % G)
+    if workspace is None:
+        workspace = torch.empty(max(cider_d_workspace_bytes(G, R, T, mult), 1), device=hyp.device, dtype=torch.uint8)
+    a = CiderDArgs(ptr(hyp), hyp.stride(0), ptr(ref), ref.stride(0), ref.stride(1), ptr(ref_count), G, R, T, mult, sigma, ptr(scores), ptr(reward),
+                   ptr(workspace), _nbytes(workspace))
+    _check(load().vlp_cider_d(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

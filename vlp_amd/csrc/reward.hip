@@ -1,0 +1,266 @@
+// CIDEr-D of id strings on the device (vlp_cider_d, include/vlp_hip.h): the reward of self-critical sequence training without the host.
+// The specification is vlp_amd/scst.py CiderD.compute_score on the strings array_to_str makes; this file restates it with exact integer
+// counting and fp32 arithmetic in a fixed order (no atomics: equal inputs give bit-equal outputs).
+//
+// An n-gram is never hashed: two n-grams are equal when their tokens are.  For a query position p and a reference position q the MATCH
+// LENGTH m(p, q) = the number of leading equal tokens of the two suffixes, capped at 4 and cut at either string's end, answers all four
+// orders at once -- the k-gram at p equals the k-gram at q exactly when m >= k.  Strings are staged as int32 with a sentinel past their
+// end (the query's is -1, a reference's -2, so two ends never match) and three sentinel columns behind every row: the inner loop is one
+// LDS read and a few compares per (p, q), with no bounds test.
+//
+//   cider_count_kernel   one block per string (the mult*G hypotheses, then the G*R references).  A worker = P consecutive lanes (P = the power
+//                        of two >= T), one lane per position of the block's string; the 256 / P workers share the groups of a tile of
+//                        references staged in LDS.  Per position and order: the number of groups whose valid references hold the
+//                        n-gram (-> df), its multiplicity in its own string (tf) and whether it is the first occurrence there.  From
+//                        them the string's four L2 norms; a hypothesis also keeps (df, tf, first) per position for the second pass.
+//   cider_score_kernel   one block per group, one wave per hypothesis, one lane per position: tf of the hypothesis' n-grams in each
+//                        valid reference of its group, the clipped dot products, norms, length penalty, mean; then the reward.
+#include "common.h"
+
+#define CD_THREADS 256
+#define CD_PAD 3                 // sentinel columns behind every staged row
+#define CD_HYP_END (-1)
+#define CD_REF_END (-2)
+#define CD_TILE_INTS 8192        // LDS budget of one reference tile (32 KiB)
+
+// (df groups, tf, first occurrence) of one (position, order): groups <= 1024, tf <= 64
+DEVFN int cd_pack(int groups, int tf, int first) { return groups | (tf << 11) | (first << 18); }
+
+DEVFN int cd_match(int a0, int a1, int a2, int a3, int b0, int b1, int b2, int b3) {
+    return a0 == b0 ? (a1 == b1 ? (a2 == b2 ? (a3 == b3 ? 4 : 3) : 2) : 1) : 0;
+}
+
+// The P lanes of a segment hold one row (lane p its id p, p < T): the row's string length -- up to and including the first 0, T without one.
+DEVFN int cd_row_len(bool is_zero, int seg, int P, int T) {
+    unsigned long long m = __ballot(is_zero);
+    m >>= seg * P;                                   // seg * P <= 63
+    if (P < 64) m &= (1ull << P) - 1ull;
+    return m ? (int)__builtin_ctzll(m) + 1 : T;
+}
+
+DEVFN int cd_ref_count(const int32_t* ref_count, int g, int R) {
+    if (!ref_count) return R;
+    const int c = ref_count[g];
+    return c < 1 ? 1 : (c > R ? R : c);
+}
+
+// Stage `rows` reference rows, starting at reference row row0 of the whole [G*R] list, into dst[rows][T + CD_PAD] (sentinel form).  Every
+// lane of the block calls this (the ballot needs whole waves); a row past its group's ref_count is all sentinels.  len_out (or NULL) gets
+// each row's length, 0 for an invalid row.
+DEVFN void cd_stage_refs(const vlp_cider_d_args& a, int row0, int rows, int* dst, int* len_out, int P, int nthreads) {
+    const int T = a.T, R = a.R, ldr = T + CD_PAD;
+    const int W = nthreads / P, worker = threadIdx.x / P, p = threadIdx.x % P, seg = (threadIdx.x & 63) / P;
+    for (int i0 = 0; i0 < rows; i0 += W) {
+        const int i = i0 + worker;
+        const bool live = i < rows && p < T;
+        int tok = CD_REF_END;
+        bool valid = false;
+        if (i < rows) {
+            const int row = row0 + i, g = row / R, r = row - g * R;
+            valid = r < cd_ref_count(a.ref_count, g, R);
+            if (live && valid) tok = (int)a.ref[(int64_t)g * a.ref_group_stride + (int64_t)r * a.ref_ld + p];
+        }
+        const int len = cd_row_len(live && valid && tok == 0, seg, P, T);
+        if (live) dst[i * ldr + p] = (valid && p < len) ? tok : CD_REF_END;
+        if (i < rows && p < CD_PAD) dst[i * ldr + T + p] = CD_REF_END;
+        if (len_out && i < rows && p == 0) len_out[i] = valid ? len : 0;
+    }
+}
+
+__global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_args a, int P, int tile_groups, int* info, float* norms) {
+    extern __shared__ __attribute__((aligned(16))) int cd_tile[];      // [tile_groups][R][T + CD_PAD]
+    __shared__ int qrow[64 + CD_PAD], srow[64 + CD_PAD];               // the block's string with the query's / a reference's sentinel
+    __shared__ int cnt[4][CD_THREADS];
+    const int T = a.T, R = a.R, G = a.G, ldr = T + CD_PAD, SH = a.mult * G;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int W = CD_THREADS / P, worker = tid / P, p = tid % P;
+    const bool is_hyp = s < SH;
+    const int64_t* src;
+    if (is_hyp) {
+        src = a.hyp + (int64_t)s * a.hyp_ld;
+    } else {
+        const int row = s - SH, g = row / R, r = row - g * R;
+        if (r >= cd_ref_count(a.ref_count, g, R)) return;              // not a reference of its group: nobody reads its norms (block-uniform)
+        src = a.ref + (int64_t)g * a.ref_group_stride + (int64_t)r * a.ref_ld;
+    }
+    if (tid < 64) {                                                    // wave 0: the block's own string
+        const int tok = tid < T ? (int)src[tid] : CD_HYP_END;
+        unsigned long long m = __ballot(tid < T && tok == 0);
+        const int len = m ? (int)__builtin_ctzll(m) + 1 : T;
+        if (tid < T) {
+            qrow[tid] = tid < len ? tok : CD_HYP_END;
+            srow[tid] = tid < len ? tok : CD_REF_END;
+        }
+        if (tid < CD_PAD) {
+            qrow[T + tid] = CD_HYP_END;
+            srow[T + tid] = CD_REF_END;
+        }
+    }
+    __syncthreads();
+    int a0 = CD_HYP_END, a1 = CD_HYP_END, a2 = CD_HYP_END, a3 = CD_HYP_END;
+    if (p < T) { a0 = qrow[p]; a1 = qrow[p + 1]; a2 = qrow[p + 2]; a3 = qrow[p + 3]; }
+
+    // groups whose valid references hold the k-gram at p
+    int c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+    for (int g0 = 0; g0 < G; g0 += tile_groups) {
+        const int ng = min(tile_groups, G - g0);
+        __syncthreads();                                               // the previous tile has been read
+        cd_stage_refs(a, g0 * R, ng * R, cd_tile, nullptr, P, CD_THREADS);
+        __syncthreads();
+        for (int gl = worker; gl < ng; gl += W) {
+            const int nr = cd_ref_count(a.ref_count, g0 + gl, R);
+            int best = 0;
+            for (int r = 0; r < nr; ++r) {
+                const int* row = cd_tile + (gl * R + r) * ldr;
+                int b0 = row[0], b1 = row[1], b2 = row[2];
+                for (int q = 0; q < T; ++q) {
+                    const int b3 = row[q + 3];
+                    best = max(best, cd_match(a0, a1, a2, a3, b0, b1, b2, b3));
+                    b0 = b1; b1 = b2; b2 = b3;
+                }
+            }
+            c1 += best >= 1; c2 += best >= 2; c3 += best >= 3; c4 += best >= 4;
+        }
+    }
+    cnt[0][tid] = c1; cnt[1][tid] = c2; cnt[2][tid] = c3; cnt[3][tid] = c4;
+    __syncthreads();
+    if (tid >= 64) return;
+
+    // wave 0, lane = position: multiplicity and first occurrence inside the own string, then weights and norms
+    int tf[4] = {0, 0, 0, 0}, first[4] = {1, 1, 1, 1}, groups[4] = {0, 0, 0, 0};
+    if (tid < T) {
+        int b0 = srow[0], b1 = srow[1], b2 = srow[2];
+        for (int q = 0; q < T; ++q) {
+            const int b3 = srow[q + 3];
+            const int m = cd_match(a0, a1, a2, a3, b0, b1, b2, b3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                tf[k] += m > k;
+                first[k] &= !(m > k && q < tid);
+            }
+            b0 = b1; b1 = b2; b2 = b3;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            for (int w = 0; w < W; ++w) groups[k] += cnt[k][w * P + tid];
+    }
+    const float ref_len = logf((float)SH);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v = 0.f;
+        if (tid < T && tf[k] > 0 && first[k]) v = (float)tf[k] * (ref_len - logf(fmaxf(1.f, (float)(a.mult * groups[k]))));
+        const float n2 = wave_sum(v * v);
+        if (tid == 0) norms[(int64_t)s * 4 + k] = sqrtf(n2);
+        if (is_hyp && tid < T) info[((int64_t)s * 4 + k) * T + tid] = cd_pack(groups[k], tf[k], tf[k] > 0 && first[k]);
+    }
+}
+
+__global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const float* norms) {
+    extern __shared__ __attribute__((aligned(16))) int cd_refs[];      // [R][T + CD_PAD]
+    __shared__ int ref_len_s[8];
+    __shared__ float sc[2];
+    const int T = a.T, R = a.R, G = a.G, ldr = T + CD_PAD, SH = a.mult * G;
+    const int g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, h = w * G + g;
+    cd_stage_refs(a, g * R, R, cd_refs, ref_len_s, 64, blockDim.x);
+
+    const int tok = lane < T ? (int)a.hyp[(int64_t)h * a.hyp_ld + lane] : CD_HYP_END;
+    const unsigned long long zm = __ballot(lane < T && tok == 0);
+    const int len = zm ? (int)__builtin_ctzll(zm) + 1 : T;
+    int av[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = __shfl(tok, (lane + j) & 63, 64);
+        av[j] = lane + j < len ? t : CD_HYP_END;
+    }
+    __syncthreads();
+
+    const float ref_len = logf((float)SH);
+    float idf[4], hv[4], nh[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
+    bool first[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int pk = lane < T ? info[((int64_t)h * 4 + k) * T + lane] : 0;
+        idf[k] = ref_len - logf(fmaxf(1.f, (float)(a.mult * (pk & 2047))));
+        hv[k] = (float)((pk >> 11) & 127) * idf[k];
+        first[k] = (pk >> 18) & 1;
+        nh[k] = norms[(int64_t)h * 4 + k];
+    }
+    const int nr = cd_ref_count(a.ref_count, g, R);
+    const float two_sigma2 = 2.f * a.sigma * a.sigma;
+    for (int r = 0; r < nr; ++r) {
+        const int* row = cd_refs + r * ldr;
+        int t[4] = {0, 0, 0, 0};
+        int b0 = row[0], b1 = row[1], b2 = row[2];
+        for (int q = 0; q < T; ++q) {
+            const int b3 = row[q + 3];
+            const int m = cd_match(av[0], av[1], av[2], av[3], b0, b1, b2, b3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] += m > k;
+            b0 = b1; b1 = b2; b2 = b3;
+        }
+        const float delta = (float)(max(len - 1, 0) - max(ref_len_s[r] - 1, 0));
+        const float penalty = expf(-(delta * delta) / two_sigma2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float rv = (float)t[k] * idf[k];
+            float val = wave_sum(first[k] ? fminf(hv[k], rv) * rv : 0.f);
+            const float nrk = norms[((int64_t)SH + (int64_t)g * R + r) * 4 + k];
+            if (nh[k] != 0.f && nrk != 0.f) val /= nh[k] * nrk;
+            acc[k] += val * penalty;
+        }
+    }
+    const float score = (acc[0] + acc[1] + acc[2] + acc[3]) / 4.f / (float)nr * 10.f;
+    if (lane == 0) {
+        a.scores[h] = score;
+        sc[w] = score;
+    }
+    if (a.reward) {                                                    // mult == 2 (checked by the entry): sample - greedy
+        __syncthreads();
+        if (threadIdx.x == 0) a.reward[g] = sc[0] - sc[1];
+    }
+}
+
+static int cd_pow2_at_least(int T) {
+    int P = 1;
+    while (P < T) P <<= 1;
+    return P;
+}
+
+static bool cd_shape_ok(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    return T >= 1 && T <= 64 && R >= 1 && R <= 8 && G >= 1 && G <= 1024 && (mult == 1 || mult == 2);
+}
+// workspace: int32 info[mult*G][4][T] (df groups, tf, first per hypothesis position and order), then f32 norms[mult*G + G*R][4]
+static int64_t cd_info_ints(int32_t G, int32_t T, int32_t mult) { return (int64_t)mult * G * 4 * T; }
+
+extern "C" int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    if (!cd_shape_ok(G, R, T, mult)) return 0;
+    const int64_t bytes = 4 * (cd_info_ints(G, T, mult) + 4 * ((int64_t)mult * G + (int64_t)G * R));
+    return (bytes + 255) / 256 * 256;
+}
+
+extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
+    VLP_CHECK_ARG(a, "vlp_cider_d: null args");
+    VLP_CHECK_ARG(cd_shape_ok(a->G, a->R, a->T, a->mult), "vlp_cider_d: needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult 1 or 2 (G %d, R %d, T %d, mult %d)",
+                  a->G, a->R, a->T, a->mult);
+    VLP_CHECK_ARG(a->hyp && a->ref && a->scores && a->workspace, "vlp_cider_d: null operand");
+    VLP_CHECK_ARG(!a->reward || a->mult == 2, "vlp_cider_d: reward = scores[g] - scores[G + g] needs mult == 2");
+    VLP_CHECK_ARG(a->hyp_ld >= a->T && a->ref_ld >= a->T && a->ref_group_stride >= (int64_t)(a->R - 1) * a->ref_ld + a->T, "vlp_cider_d: strides shorter than the rows");
+    VLP_CHECK_ARG(a->sigma > 0.f, "vlp_cider_d: sigma must be positive");
+    const int64_t need = vlp_cider_d_workspace_bytes(a->G, a->R, a->T, a->mult);
+    VLP_CHECK_ARG(a->workspace_bytes >= need && (uintptr_t)a->workspace % 16 == 0, "vlp_cider_d: workspace of %lld bytes, needs %lld (16-byte aligned)",
+                  (long long)a->workspace_bytes, (long long)need);
+    VLP_ENTER(a->ref, "vlp_cider_d");
+    const int SH = a->mult * a->G, SR = a->G * a->R, ldr = a->T + CD_PAD;
+    const int P = cd_pow2_at_least(a->T);
+    int tile_groups = CD_TILE_INTS / (a->R * ldr);                     // >= 15 at the largest accepted R, T
+    if (tile_groups > a->G) tile_groups = a->G;
+    int* info = (int*)a->workspace;
+    float* norms = (float*)(info + cd_info_ints(a->G, a->T, a->mult));
+    hipLaunchKernelGGL(cider_count_kernel, dim3(SH + SR), dim3(CD_THREADS), (size_t)tile_groups * a->R * ldr * sizeof(int), (hipStream_t)stream, *a, P,
+                       tile_groups, info, norms);
+    VLP_CHECK_LAUNCH("vlp_cider_d (count)");
+    hipLaunchKernelGGL(cider_score_kernel, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
+                       (const float*)norms);
+    VLP_CHECK_LAUNCH("vlp_cider_d (score)");
+    return VLP_OK;
+}

@@ -17,6 +17,8 @@ by the last three characters of the image id, class probabilities, boxes), conve
     `MaskSpec` / `RawRegions` of vlp_amd.input_prep in the `input_mask` / `vis_pe` slots (the engine expands them on the device).
     A VQA 2.0 example carries the question's answer indices as well; the prefetcher scores them on the host (SparseAnswers.from_answer_ids)
     into two more pinned [B, 10] buffers and hands the batch's `ans_labels` out as a SparseAnswers (the loss kernels read the pairs).
+    With `caption_refs=R` a caption batch's `ans_labels` slot carries a CaptionRefs instead: up to R captions of each image of the batch, in
+    the format of the batch's own ground-truth ids, for the multi-reference SCST reward (vlp_amd.scst).
     Every batch draws from its OWN `random.Random(batch_seed(seed, epoch, rank, step))`: its content is a pure function of those four
     numbers -- the same for 1 and K workers, independent of thread interleaving and of anything else that touches the global `random`.
 """
@@ -29,7 +31,7 @@ import threading
 import numpy as np
 import torch
 
-from .input_prep import MaskSpec, RawRegions, SparseAnswers, N_CLS, N_ANSWERS, N_ANSWER_SLOTS
+from .input_prep import CaptionRefs, MaskSpec, RawRegions, SparseAnswers, MAX_CAPTION_REFS, N_CLS, N_ANSWERS, N_ANSWER_SLOTS
 
 FEAT_DIM, BOX_DIM = 2048, 6
 
@@ -268,7 +270,8 @@ def vqa_examples_from_imdb(imdb, tokenize, answer_index, store_key=None):
 
 class BatchPrefetcher(object):
     """Iterates device-resident batches.  `examples` is a list of (image id, caption token ids), or of VQA examples (image id, question
-    token ids, answer ids, question id): then the 12th element of a batch is a SparseAnswers instead of the dummy [B, 1] zeros.  Every sample picks the s2s or the
+    token ids, answer ids, question id): then the 12th element of a batch is a SparseAnswers instead of the dummy [B, 1] zeros (a CaptionRefs
+    with caption_refs > 0).  Every sample picks the s2s or the
     bidirectional preprocessor with probabilities (s2s_prob, 1 - s2s_prob) like Img2txtDataset.__getitem__ (:162-166).  `num_workers`
     threads (run_img2txt_dist.py:296-298 `--num_workers`) prepare up to `depth` batches ahead: host buffers are pinned and the H2D
     copies run on their own stream, so they overlap the training step; the consumer's stream waits on the copy event only.  Batches are
@@ -276,15 +279,33 @@ class BatchPrefetcher(object):
     rank, step)) only: the same seed gives the same batches for any worker count (tests/test_data_cpu.py)."""
 
     def __init__(self, store, examples, batch_size, proc_s2s, proc_bi=None, s2s_prob=1.0, device=None, steps=None, depth=None, seed=0,
-                 vis_mask_prob=0.0, rank=0, world=1, num_workers=1, balance_lengths=False):
+                 vis_mask_prob=0.0, rank=0, world=1, num_workers=1, balance_lengths=False, caption_refs=0):
         """world > 1: `examples` is the WHOLE dataset on every rank and the per-epoch order is DistributedSampler's
         (distributed_sampler_indices; call set_epoch(e) before iterating epoch e like the reference does, :455).
         steps: batches per epoch; default ceil(samples of this rank / batch_size) = len(DataLoader) of the reference (drop_last=False,
         :296-298) -- the last batch is filled by wrapping around the epoch's order instead of being short (fixed shapes).
         balance_lengths (world > 1): every global batch of batch_size x world samples is dealt to the ranks by kept length
-        (balanced_rank_split) instead of by index -- same sample SET per step as DistributedSampler, near-equal padding-free row counts."""
+        (balanced_rank_split) instead of by index -- same sample SET per step as DistributedSampler, near-equal padding-free row counts.
+        caption_refs = R > 0 (caption examples only): the 12th element of a batch is a CaptionRefs(ids int64 [B, R, T], count int32 [B]),
+        T = max_len_b + 1, instead of the dummy [B, 1] zeros: the first R captions of each image, taken from the WHOLE `examples` list in
+        order of first appearance, each in the format of `input_ids[:, Nv + 2:]` -- its first max_len_b tokens, [SEP], then 0 (no 0 when
+        [SEP] lands in the last column).  The cut draws nothing from the batch's generator: every other field of every batch is what
+        caption_refs=0 gives for the same seed."""
         self.store, self.examples, self.B = store, examples, batch_size
         self.has_answers = examples_have_answers(examples)
+        self.caption_refs = int(caption_refs)
+        if self.caption_refs:
+            if self.has_answers:
+                raise ValueError("BatchPrefetcher: caption_refs needs caption examples, these are VQA examples")
+            if not 0 < self.caption_refs <= MAX_CAPTION_REFS:
+                raise ValueError("BatchPrefetcher: caption_refs must be in 0..%d" % MAX_CAPTION_REFS)
+            self.ref_T = proc_s2s.max_len_b + 1
+            self.refs_of = {}                     # image id -> its captions as reference rows (at most caption_refs, order of first appearance)
+            for ex in examples:
+                rows = self.refs_of.setdefault(ex[0], [])
+                if len(rows) < self.caption_refs:
+                    row = [int(t) for t in ex[1][:proc_s2s.max_len_b]] + [proc_s2s.sep_id]
+                    rows.append(row + [0] * (self.ref_T - len(row)))
         self.rank, self.world, self.epoch = rank, world, 0
         self.balance_lengths = bool(balance_lengths) and world > 1
         per_rank = -(-len(examples) // world)
@@ -315,6 +336,8 @@ class BatchPrefetcher(object):
             host["vmp"] = pin(B, self.n_vis_masked, dt=torch.long)
         if self.has_answers:
             host["ans_idx"], host["ans_score"] = pin(B, N_ANSWER_SLOTS, dt=torch.int32), pin(B, N_ANSWER_SLOTS, dt=torch.float32)
+        if self.caption_refs:
+            host["ref_ids"], host["ref_count"] = pin(B, self.caption_refs, self.ref_T, dt=torch.long), pin(B, dt=torch.int32)
         dev = {k: torch.empty_like(v, device=self.device) for k, v in host.items()}
         # numpy views of the host buffers, taken once (the fill writes whole arrays through them)
         views = {k: v.numpy() for k, v in host.items()}
@@ -351,6 +374,12 @@ class BatchPrefetcher(object):
             hv["vmp"][...] = np.asarray(vmp, dtype=np.int64)
         if self.has_answers:                      # scored on the host straight into the pinned slots (no draw from rng)
             SparseAnswers.from_answer_ids([ex[2] for ex in batch_examples], out=(hv["ans_idx"], hv["ans_score"]))
+        if self.caption_refs:                     # the image's captions, cut and padded at construction (no draw from rng)
+            hv["ref_ids"][...] = 0
+            for j, ex in enumerate(batch_examples):
+                rows = self.refs_of[ex[0]]
+                hv["ref_ids"][j, :len(rows)] = rows
+                hv["ref_count"][j] = len(rows)
         lens_host = spec[1].tolist()              # second_end on the host: the padding-free step needs no device read-back
         if ev is None:
             for k in host:
@@ -373,6 +402,8 @@ class BatchPrefetcher(object):
         vis_masked_pos = d["vmp"] if self.n_vis_masked else torch.zeros(B, 0, dtype=torch.long, device=self.device)
         if self.has_answers:
             ans = SparseAnswers(d["ans_idx"], d["ans_score"], N_ANSWERS)      # from_answer_ids built them: the kernels' contract holds
+        elif self.caption_refs:
+            ans = CaptionRefs(d["ref_ids"], d["ref_count"])
         else:
             ans = torch.zeros(B, 1, dtype=torch.float16, device=self.device)
         # (input_ids, segment_ids, input_mask, lm_label_ids, masked_pos, masked_weights, is_next, task_idx, img, vis_masked_pos, vis_pe, ans)

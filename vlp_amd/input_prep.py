@@ -172,3 +172,32 @@ class SparseAnswers(_SparseAnswersBase):
         b, s = torch.nonzero(self.idx >= 0, as_tuple=True)
         y[b, self.idx[b, s].to(torch.long)] = self.score[b, s]
         return y
+
+
+MAX_CAPTION_REFS = 8    # references per image vlp_cider_d accepts
+MAX_CAPTION_LEN = 64    # ids per reference row vlp_cider_d accepts
+
+
+class CaptionRefs(collections.namedtuple("CaptionRefs", ["ids", "count"])):
+    """The captions of each image of one batch as references of the SCST reward (vlp_cider_d, vlp_amd.scst): ids int64 [B, R, T] in the
+    format `gt_ids` has -- the caption's tokens, then [SEP], then 0 up to T (no 0 when [SEP] lands in the last column) -- and count
+    int32 [B], 1..R: the first count[b] rows of image b are its references, the others are never read as text.  The loader
+    (vlp_amd.data.BatchPrefetcher(caption_refs=R)) delivers one in place of the dummy `ans_labels` of a caption batch."""
+    __slots__ = ()
+
+    def to(self, device, non_blocking=False):
+        return CaptionRefs(self.ids.to(device, non_blocking=non_blocking), self.count.to(device, non_blocking=non_blocking))
+
+    @property
+    def shape(self):
+        return tuple(self.ids.shape)
+
+    def check(self, B, T):
+        """Layout only (no device read-back): the reward kernel clamps count to 1..R itself."""
+        R = self.ids.shape[1] if self.ids.dim() == 3 else 0
+        if self.ids.dtype != torch.int64 or tuple(self.ids.shape) != (B, R, T) or not 0 < R <= MAX_CAPTION_REFS or not 0 < T <= MAX_CAPTION_LEN:
+            raise RuntimeError("CaptionRefs.ids must be int64 [%d, R, %d] with 1 <= R <= %d and T <= %d" % (B, T, MAX_CAPTION_REFS, MAX_CAPTION_LEN))
+        if self.count.dtype != torch.int32 or tuple(self.count.shape) != (B,):
+            raise RuntimeError("CaptionRefs.count must be int32 [%d]" % B)
+        if self.ids.device != self.count.device:
+            raise RuntimeError("CaptionRefs.ids and .count must live on one device")

@@ -30,7 +30,7 @@ import torch
 
 from . import synthetic
 from .distributed import DistributedDataParallel as DDP
-from .input_prep import MaskSpec
+from .input_prep import CaptionRefs, MaskSpec
 from .modeling import BertConfig, BertForPreTrainingLossMask, BertForSeq2SeqDecoder, load_checkpoint_state
 from .optimization import BertAdam, warmup_linear           # noqa: F401  (re-exported like the reference imports them)
 from .optimization_fp16 import FP16_Optimizer_State, FusedAdam
@@ -142,6 +142,15 @@ def build_parser():
     p.add_argument("--shard_order", default="balanced", choices=["balanced", "reference"],
                    help="world_size > 1 with --packed_features: 'balanced' deals every global batch (DistributedSampler's sample set) to the ranks "
                         "by caption length so that padding-free row counts per rank match; 'reference' is DistributedSampler's index order bit for bit")
+    p.add_argument("--scst_reward", default="host", choices=["host", "device"],
+                   help="--scst: where the CIDEr-D reward is computed.  'host' is the reference's way (the cleaned ids are copied to the host and "
+                        "scored there, vlp_amd.scst.CiderD); 'device' scores them with the vlp_cider_d kernels: same reward to fp32 rounding, no "
+                        "host synchronisation between the sampled decode and the backward")
+    p.add_argument("--scst_refs", default="caption", choices=["caption", "image"],
+                   help="--scst: the references of the reward.  'caption' is the reference's recipe: the one caption the loader drew for the "
+                        "sample.  'image' scores against up to 5 captions of the sample's image (all of COCO's), which is how CIDEr is defined -- a "
+                        "deliberate departure from the reference's objective; needs --packed_features (the loader collects the captions per "
+                        "image id from --token_file)")
     return p
 
 
@@ -161,6 +170,8 @@ def derive_args(args):
     assert (not args.scst) or args.dataset == "coco", "scst support on coco only!"
     if args.scst:                                        # :201-204
         assert args.max_pred == 0 and args.mask_prob == 0, "no mask for scst!"
+    if args.scst_refs == "image" and not (args.scst and args.packed_features):
+        raise ValueError("--scst_refs image needs --scst and --packed_features (the captions of an image come from the packed loader)")
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -285,16 +296,19 @@ def train_step(model, optimizer, batch, lr_this_step, mask_image_regions=False, 
     return loss_tuple
 
 
-def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None):
+def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host"):
     """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
     train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
     baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
     called at the end of each phase: "greedy_decode", "sample_forward" (sampled decode + scoring forward), "reward_host", "backward" and,
-    unless accumulating, "optimizer" (tools/scst_bench.py times them)."""
+    unless accumulating, "optimizer" (tools/scst_bench.py times them).
+    reward_on="device" (--scst_reward device) computes the reward with vlp_amd.scst.self_critical_reward_device instead: nothing leaves the
+    device between the sampled decode and the backward, and the phase is marked "reward_device".  A batch whose 12th element is a CaptionRefs
+    (--scst_refs image) is scored against those references, on either side, instead of its own ground-truth ids."""
     if mark is None:
         def mark(phase):
             pass
-    from .scst import clean_captions, self_critical_reward
+    from .scst import clean_captions, self_critical_reward, self_critical_reward_device, self_critical_reward_refs
     (input_ids, segment_ids, input_mask, lm_label_ids, masked_pos, masked_weights, is_next, task_idx, img, vis_masked_pos, vis_pe,
      ans_labels) = batch
     L = input_ids.shape[1]
@@ -312,10 +326,18 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gt_ids = input_ids[:, len_vis_input + 2:]
-    reward, _ = self_critical_reward(greedy_res, gt_ids, gen_result, gt_ids.size(0))
-    reward = torch.from_numpy(reward).float().to(gen_result.device)
-    mean_reward = reward.mean()
-    mark("reward_host")
+    if reward_on == "device":
+        reward, _ = self_critical_reward_device(greedy_res, ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids, gen_result)
+        mean_reward = reward.mean()
+        mark("reward_device")
+    else:
+        if isinstance(ans_labels, CaptionRefs):
+            reward, _ = self_critical_reward_refs(greedy_res, ans_labels, gen_result)
+        else:
+            reward, _ = self_critical_reward(greedy_res, gt_ids, gen_result, gt_ids.size(0))
+        reward = torch.from_numpy(reward).float().to(gen_result.device)
+        mean_reward = reward.mean()
+        mark("reward_host")
     loss = rl_crit(sample_logprobs, gen_result, reward)
     bwd = loss / accum_steps if accum_steps > 1 else loss
     if hasattr(optimizer, "backward"):
@@ -352,7 +374,8 @@ def build_packed_loader(args, device):
     return BatchPrefetcher(store, examples, args.train_batch_size, TextPreprocessor(mode="s2s", **kw), TextPreprocessor(mode="bi", **kw),
                            s2s_prob=args.s2s_prob, device=device, seed=args.seed, vis_mask_prob=args.vis_mask_prob,
                            rank=max(args.global_rank, 0), world=max(args.world_size, 1), num_workers=args.num_workers,
-                           balance_lengths=(args.shard_order == "balanced" and not args.no_padding_free))
+                           balance_lengths=(args.shard_order == "balanced" and not args.no_padding_free),
+                           caption_refs=5 if args.scst_refs == "image" else 0)
 
 
 def synthetic_batches(args, device, steps, rank):
@@ -455,7 +478,7 @@ def main(argv=None):
             lr = args.learning_rate * warmup_linear(global_step / t_total, args.warmup_proportion)
             if args.scst:
                 loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
-                                         accum_steps=args.gradient_accumulation_steps)
+                                         accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward)
                 rewards.append(mean_r.detach())
             else:
                 lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,

@@ -15,6 +15,10 @@ Its parity with coco-caption's own file is not pinned by a test (that source is 
 
 The reward is computed where the reference computes it, on the host: one device -> host copy of the cleaned ids, numpy / python scoring of
 2B short id strings, and the [B, T] reward back.  Caption cleaning and the criterion are vectorised torch ops.
+
+self_critical_reward_device computes the same reward with the vlp_cider_d kernels (no host round trip), and together with
+self_critical_reward_refs accepts several references per sample (input_prep.CaptionRefs: all captions of the image, which is how CIDEr is
+defined; the reference's recipe scores against the one caption the loader drew).  CiderD stays the specification of both.
 """
 from collections import Counter, OrderedDict
 
@@ -144,3 +148,56 @@ class RewardCriterion(nn.Module):
         mask = (seq > 0).to(input.dtype)
         mask = torch.cat([torch.ones_like(mask[:, :1]), mask[:, :-1]], 1).contiguous().view(-1)
         return torch.sum(-input * reward * mask) / torch.sum(mask)
+
+
+def _refs_parts(refs, B):
+    """refs -> (ids [B, R, T], count [B] or None): a CaptionRefs as it is, the [B, T] ground-truth ids as one reference per sample."""
+    from .input_prep import CaptionRefs
+    if isinstance(refs, CaptionRefs):
+        return refs.ids[:B], refs.count[:B]
+    return refs[:B].unsqueeze(1), None
+
+
+def self_critical_reward_refs(greedy_res, refs, gen_result):
+    """self_critical_reward against one OR several references per sample, on the host with CiderD: `refs` is the [B, T] ground-truth ids
+    (then this is self_critical_reward itself) or a CaptionRefs (ids [B, R, T], count [B]: sample b is scored against the first count[b]
+    rows).  Returns (reward [B, T] float64 ndarray, scores [2B]).  The oracle of self_critical_reward_device, and the host path of
+    multi-reference training."""
+    def host(x):
+        return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    from .input_prep import CaptionRefs
+    B = len(gen_result)
+    if not isinstance(refs, CaptionRefs):
+        return self_critical_reward(greedy_res, refs, gen_result, B)
+    greedy_res, gen_result, ids, count = host(greedy_res), host(gen_result), host(refs.ids), host(refs.count)
+    R = ids.shape[1]
+    gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
+    res, gts = OrderedDict(), OrderedDict()
+    for i in range(B):
+        res[i], gts[i] = [array_to_str(gen_result[i].tolist())], gt_s[i]
+    for i in range(B):
+        res[B + i], gts[B + i] = [array_to_str(greedy_res[i].tolist())], gt_s[i]
+    _, scores = _scorer.compute_score(gts, res)
+    d = scores[:B] - scores[B:]
+    return np.repeat(d[:, np.newaxis], gen_result.shape[1], 1), scores
+
+
+def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, workspace=None):
+    """self_critical_reward_refs on the device (vlp_cider_d, csrc/reward.hip): id tensors [B, T] on the GPU, `refs` the [B, T] ground-truth
+    ids or a CaptionRefs with ids [B, R, T] of the same T.  Returns (reward f32 [B, T] -- the [B] differences expanded over the columns --,
+    scores f32 [2B]) as device tensors; scores_out (f32 [2B]) receives the scores when given; workspace: the caller's kernel scratch
+    (_lib.cider_d_workspace_bytes(B, R, T, 2) bytes, uint8), else allocated per call.  No device -> host transfer, no synchronisation: two
+    kernel launches on the current stream, capturable into a graph."""
+    from . import _lib as K
+    from .input_prep import CaptionRefs
+    B, T = gen_result.shape
+    if isinstance(refs, CaptionRefs):
+        refs.check(B, T)
+    ids, count = _refs_parts(refs, B)
+    if tuple(greedy_res.shape) != (B, T) or ids.shape[0] != B or ids.shape[2] != T:
+        raise RuntimeError("self_critical_reward_device: samples, greedy captions and references must share [B, T] = [%d, %d]" % (B, T))
+    hyp = torch.cat([gen_result, greedy_res], 0)
+    scores = scores_out if scores_out is not None else torch.empty(2 * B, dtype=torch.float32, device=hyp.device)
+    diff = torch.empty(B, dtype=torch.float32, device=hyp.device)
+    K.cider_d(hyp, ids, count, 2, scores, reward=diff, sigma=_scorer.sigma, workspace=workspace)
+    return diff.unsqueeze(1).expand(B, T), scores
