@@ -119,7 +119,7 @@ def layernorm_restatement_fp32(x, gamma, beta, eps=1e-5, two_pass=True):
 
 
 def ce_rows_restatement_fp32(logits, labels):
-    """fp32 max-subtracted log-sum-exp per row and row loss lse - logit[label] (the arithmetic of ce_row_kernel): (lse, row_loss)."""
+    """fp32 max-subtracted log-sum-exp per row and row loss lse - logit[label] (the arithmetic of row_lse_kernel with the CE policy): (lse, row_loss)."""
     x = logits.float()
     m = x.max(-1, keepdim=True).values
     lse = (m + torch.log(torch.exp(x - m).sum(-1, keepdim=True)))[:, 0]

@@ -609,6 +609,19 @@ def test_token_logprob_guarded(R, V, gen):
     G.assert_untouched(dl, written="rows", name="dlogits")
     for g, name in ((logits, "logits"), (ids, "ids"), (grow, "g"), (lse_in, "lse")):
         G.assert_untouched(g, name=name)
+    # The CE loss and the token log-prob are two policies of one forward and one backward kernel template (csrc/loss.hip): with labels = ids,
+    # weights 1, one position per sample and nothing dropped they agree bit for bit -- a - b == -(b - a) and (-c)(o - p) == c(p - o) exactly.
+    ones = vin(torch.ones(R, dtype=I64, device=DEV), fill=1)
+    loss, lse_ce, coef, row = vout(1), vout(R), vout(R), vout(R)
+    K.mlm_loss_fwd(logits.view, logits.ld, ids.vec, ones.vec, loss.vec, lse_ce.vec, coef.vec, row.vec, R, 1, V, drop_worst_ratio=0.0)
+    assert torch.equal(G.bits(lse_ce.vec), G.bits(lse.vec)), "lse: mlm_loss_fwd vs token_logprob_fwd"
+    assert torch.equal(row.vec, -logp.vec), "row_loss vs -logp"      # by value: one class gives +0 against -0
+    one = vin(torch.ones(1, device=DEV))
+    neg_coef = vin(-coef.vec)
+    dl_ce, dl_tok = gout(R, V, pad=24), gout(R, V, pad=24)
+    K.mlm_loss_bwd(logits.view, logits.ld, ids.vec, lse_in.vec, coef.vec, one.vec, dl_ce.view, dl_ce.ld, R, V)
+    K.token_logprob_bwd(logits.view, logits.ld, ids.vec, lse_in.vec, neg_coef.vec, dl_tok.view, dl_tok.ld, R, V)
+    assert torch.equal(dl_ce.full, dl_tok.full), "dlogits [R, ldd]: mlm_loss_bwd(coef) vs token_logprob_bwd(-coef)"
 
 
 @pytest.mark.parametrize("B,N", [(7, 3129), (1, 1001), (3, 17), (2, 8), (5, 1)])

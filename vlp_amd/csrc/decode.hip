@@ -22,7 +22,7 @@
 // tile are visited in the order n = 8 (i >> 2) + 4 tn + (i & 3), so a lane ends with ONE row m and 8 consecutive n: one 16-byte store.
 // LDS: k tiles of [rows][64 halfs] (128-byte rows), 16-byte-chunk XOR swizzle applied on the DMA source address (X: row & 7; W: bits
 // 1, 3, 4 of the row = lane >> 1 of its fragment read).
-#include "common.h"
+#include "vocab_row.h"
 
 #define DG_BM 64
 #define DG_BN 32
@@ -359,33 +359,11 @@ __global__ __launch_bounds__(1024) void argmax_rows2_kernel(const f16* logits, i
     __shared__ float sv[16];
     __shared__ int si[16];
     const f16* x = logits + (int64_t)blockIdx.x * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    const int nv = V >> 3;
-    for (int i = threadIdx.x; i < nv; i += 1024) {            // ascending v within a thread: `>` keeps the first maximum
-        const f16x8 q = ld8(x + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float f = (float)q[j];
-            if (f > best) { best = f; bi = i * 8 + j; }
-        }
-    }
-    for (int v = nv * 8 + threadIdx.x; v < V; v += 1024) {
-        const float f = (float)x[v];
-        if (f > best) { best = f; bi = v; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float f = __shfl_xor(best, o, 64);
-        const int j = __shfl_xor(bi, o, 64);
-        if (f > best || (f == best && j < bi)) { best = f; bi = j; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
+    float best;
+    int bi;
+    row_first_max<1024, true>(x, 0, V, best, bi);
+    argmax_block1024(best, bi, sv, si);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < 16; ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
         ids_a[blockIdx.x * sa] = bi;
         if (ids_b) ids_b[blockIdx.x * sb] = bi;
         vals[blockIdx.x * sv_] = best;

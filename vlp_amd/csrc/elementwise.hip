@@ -1,6 +1,6 @@
 // Memory-bound glue kernels of the VLP hot path for gfx950 (16-byte vector accesses where layout permits).
 #include <hip/hip_fp16.h>
-#include "common.h"
+#include "vocab_row.h"
 
 // =================================================================================================
 // Embedding splice, modeling.py:217-236
@@ -693,32 +693,15 @@ extern "C" int vlp_kv_append(const void* qkv_new, int64_t ld, void* cache, int32
     return VLP_OK;
 }
 
-// block arg-max of 256 (value, index) candidates: largest value, smallest index on ties; the result is in sv[0] / si[0] for every thread
-DEVFN void argmax_block256(float best, int bi, float* sv, int* si) {
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const float f = sv[threadIdx.x + o];
-            const int j = si[threadIdx.x + o];
-            if (f > sv[threadIdx.x] || (f == sv[threadIdx.x] && j < si[threadIdx.x])) { sv[threadIdx.x] = f; si[threadIdx.x] = j; }
-        }
-        __syncthreads();
-    }
-}
 // ids[r] = argmax_v logits[r, v] (first maximum), vals[r] = that logit   (torch.max(prediction_scores, -1), modeling.py:1228)
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const f16* logits, int64_t ld, int V, int64_t* ids, int64_t ids_stride, float* vals,
                                                           int64_t vals_stride) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const f16* x = logits + (int64_t)blockIdx.x * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int v = threadIdx.x; v < V; v += 256) {
-        const float f = (float)x[v];
-        if (f > best) { best = f; bi = v; }
-    }
+    float best;
+    int bi;
+    row_first_max<256, false>(x, 0, V, best, bi);
     argmax_block256(best, bi, sv, si);
     if (threadIdx.x == 0) { ids[blockIdx.x * ids_stride] = si[0]; vals[blockIdx.x * vals_stride] = sv[0]; }
 }
@@ -737,12 +720,9 @@ __global__ __launch_bounds__(256) void vqa_answer_rows_kernel(const f16* logits,
     __shared__ float sv[256];
     __shared__ int si[256];
     const f16* x = logits + (int64_t)blockIdx.x * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int v = first_col + threadIdx.x; v < N; v += 256) {
-        const float f = (float)x[v];
-        if (f > best) { best = f; bi = v; }
-    }
+    float best;
+    int bi;
+    row_first_max<256, false>(x, first_col, N, best, bi);
     argmax_block256(best, bi, sv, si);
     if (threadIdx.x == 0) {
         // a row of -inf / NaN only leaves no candidate: answer first_col, as torch.max over an all -inf row gives index 0
@@ -790,6 +770,9 @@ DEVFN bool topk_list_has(const int* lst, int n, int v) {
     for (int j = 0; j < n; ++j) hit |= lst[j] == v;
     return hit;
 }
+// (This kernel keeps its hand-written passes and LDS trees: on row_visit / block_reduce_max / argmax_block256 its loops compile to the same
+// instructions, yet a launch at 64 rows, K = 17 measured 486 us against 470 us -- and 467 us with the reduction words moved in LDS: a
+// code-placement effect that is not understood.  profiles/vocab_row_refactor_ab.txt)
 template <bool LIST>
 __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl, int eos_id,
                                                               int block_eos, float* out_scores, int64_t* out_ids) {
@@ -862,50 +845,24 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits,
 // 256-candidate block arg-max over the threads' heads.  Same results as the K+2-pass kernel above (value descending, index ascending).
 // Round 6: 1024 threads per row and 16-byte loads (the 256-thread form walked the row three times with 2-byte loads at a 512-byte stride: 113
 // dependent iterations per pass, 73 us per launch at 192 rows -- 5 % of a beam-3 token step); block reductions by wave shuffles + 16 LDS words.
-DEVFN void topk_better(float& bv, int& bi, float f, int j) {
-    if (f > bv || (f == bv && j < bi)) { bv = f; bi = j; }
-}
 template <int KMAX, bool LIST>
 __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl,
                                                                      int eos_id, int block_eos, float* out_scores, int64_t* out_ids) {
-    __shared__ float sv[16];
+    __shared__ float red[16], sv[16];
     __shared__ int si[16];
     __shared__ int lst[LIST ? TOPK_LIST_MAX : 1];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv_ = tid >> 6;
+    const int row = blockIdx.x, tid = threadIdx.x;
     const f16* x = logits + (int64_t)row * ld;
     const uint8_t* fb = (!LIST && forbid) ? forbid + (int64_t)row * V : nullptr;
     int ncand = 0;
     if constexpr (LIST) ncand = topk_list_load<1024>(tl, row, tid, lst);
-    const int nv = V >> 3;                               // whole 8-element vectors (rows are 16-byte aligned: ld % 8 == 0 is checked by the launcher)
+    // whole 8-element vectors: rows are 16-byte aligned (ld % 8 == 0 is checked by the launcher)
     float mx = -INFINITY;
-    for (int i = tid; i < nv; i += 1024) {
-        const f16x8 q = ld8(x + i * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)q[e]);
-    }
-    for (int v = nv * 8 + tid; v < V; v += 1024) mx = fmaxf(mx, (float)x[v]);
-    mx = wave_max(mx);
-    if (lane == 0) sv[wv_] = mx;
-    __syncthreads();
-    mx = sv[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) mx = fmaxf(mx, sv[k]);
-    __syncthreads();
+    row_visit<1024, true>(x, 0, V, [&](float f, int) { mx = fmaxf(mx, f); });
+    mx = block_reduce_max<1024>(mx, red);
     float sum = 0.f;
-    for (int i = tid; i < nv; i += 1024) {
-        const f16x8 q = ld8(x + i * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum += __expf((float)q[e] - mx);
-    }
-    for (int v = nv * 8 + tid; v < V; v += 1024) sum += __expf((float)x[v] - mx);
-    sum = wave_sum(sum);
-    if (lane == 0) sv[wv_] = sum;
-    __syncthreads();
-    sum = sv[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) sum += sv[k];
-    const float lse = mx + __logf(sum);
-    __syncthreads();
+    row_visit<1024, true>(x, 0, V, [&](float f, int) { sum += __expf(f - mx); });
+    const float lse = mx + __logf(block_reduce_sum<1024>(sum, red));
     float lv[KMAX];
     int lidx[KMAX];
 #pragma unroll
@@ -935,23 +892,11 @@ __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* 
             }
         }
     };
-    for (int i = tid; i < nv; i += 1024) {
-        const f16x8 q = ld8(x + i * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) offer((float)q[e], i * 8 + e);
-    }
-    for (int v = nv * 8 + tid; v < V; v += 1024) offer((float)x[v], v);
+    row_visit<1024, true>(x, 0, V, offer);
     for (int k = 0; k < K; ++k) {
         float bv = lv[0];
         int bi = lidx[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) topk_better(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
-        if (lane == 0) { sv[wv_] = bv; si[wv_] = bi; }
-        __syncthreads();
-        bv = sv[0];
-        bi = si[0];
-#pragma unroll
-        for (int j = 1; j < 16; ++j) topk_better(bv, bi, sv[j], si[j]);
+        argmax_block1024(bv, bi, sv, si);
         if (tid == 0) { out_scores[(int64_t)row * K + k] = bv; out_ids[(int64_t)row * K + k] = bi; }
         if (lidx[0] == bi) {                         // the winner pops its head
 #pragma unroll
@@ -1150,6 +1095,9 @@ extern "C" int vlp_kv_gather(const void* src, int64_t src_rows_per_batch, void* 
 
 // ids[r] ~ Categorical(softmax(logits[r, :V])) by the Gumbel-max trick on the counter hash (element = (row, v) of stream `stream`), and
 // logp[r] = log_softmax(logits[r])[ids[r]]   (sample_mode == 'sample', modeling.py:1229-1235)
+// (This kernel keeps its hand-written passes and LDS trees: on row_visit / block_reduce_max / argmax_block256 its loops compile to the same
+// instructions, yet a launch at 64 rows measured 37.5 us against 36.1 us, and 38.8 us with the reduction words moved in LDS: a code-placement
+// effect that is not understood.  profiles/vocab_row_refactor_ab.txt)
 __global__ __launch_bounds__(256) void sample_rows_kernel(const f16* logits, int64_t ld, int V, DropCtx rng, int64_t* ids, int64_t ids_stride, float* logp,
                                                           int64_t logp_stride) {
     __shared__ float sv[256];

@@ -3,63 +3,113 @@
 //              per-sample sum, drop-worst top-k, normalisation (modeling.py:1083-1111);
 //              with label smoothing the per-row KL of loss.py LabelSmoothingLoss instead of the CE (modeling.py:1104-1106);
 //   VQA:       BCEWithLogitsLoss(mean) * num_answers (modeling.py:1030, 1140).
-#include "common.h"
 #include "keep_count.h"
+#include "vocab_row.h"
 
 #define CE_THREADS 256
 
-DEVFN float block_reduce_sum(float v, float* sh) {
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    float r = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-    return r;
-}
-DEVFN float block_reduce_max(float v, float* sh) {
-    v = wave_max(v);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    float r = -INFINITY;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r = fmaxf(r, sh[i]);
-    return r;
-}
-
-// one block per row: lse[row] and row_loss[row] = lse - logit[label]
-__global__ __launch_bounds__(CE_THREADS) void ce_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                            float* __restrict__ lse, float* __restrict__ row_loss, int V) {
+// ---------------------------------------------------------------------------------------------
+// Vocabulary-row losses.  Forward: one block per row, a max pass and a sum-exp pass give lse[row] = m + log S; a policy says whether
+// A = sum (z - m) is accumulated as well (SUM_D) and what the row's second output is.  Backward: grid (chunks of the row, rows), every
+// 8-column chunk of [0, ldd) is written -- the policy's per-element expression below V, zeros in the pad columns [V, ldd) and on a row the
+// policy zeroes.  Labels are clamped to [0, V).
+// ---------------------------------------------------------------------------------------------
+template <typename Policy>
+__global__ __launch_bounds__(CE_THREADS) void row_lse_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                             float* __restrict__ lse, float* __restrict__ out, int V, Policy p) {
     __shared__ float sh[8];
     const int row = blockIdx.x;
     const f16* x = logits + (int64_t)row * ld;
-    const int v8 = V >> 3;
     float mx = -INFINITY;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)t[e]);
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) mx = fmaxf(mx, (float)x[i]);
-    mx = block_reduce_max(mx, sh);
-    float s = 0.f;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += __expf((float)t[e] - mx);
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) s += __expf((float)x[i] - mx);
-    s = block_reduce_sum(s, sh);
+    row_visit<CE_THREADS, true>(x, 0, V, [&](float z, int) { mx = fmaxf(mx, z); });
+    mx = block_reduce_max<CE_THREADS>(mx, sh);
+    float s = 0.f, a = 0.f;
+    row_visit<CE_THREADS, true>(x, 0, V, [&](float z, int) {
+        const float d = z - mx;
+        s += __expf(d);
+        if constexpr (Policy::SUM_D) a += d;
+    });
+    s = block_reduce_sum<CE_THREADS>(s, sh);
+    if constexpr (Policy::SUM_D) a = block_reduce_sum<CE_THREADS>(a, sh);
     if (threadIdx.x == 0) {
-        const float l = mx + __logf(s);
+        const float ls = __logf(s);
         int64_t lab = labels[row];
         lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
-        lse[row] = l;
-        row_loss[row] = l - (float)x[lab];
+        lse[row] = mx + ls;
+        out[row] = p.row_out(x, lab, V, mx, ls, a);
     }
 }
+// rc / rc_scale: the operands of the policy's row constant.  They are kernel arguments, not policy members, and rc_scale sits behind V: in the
+// other forms tried the compiler loaded the label, waited, and only then loaded the row constant and lse -- a second scalar round trip per block,
+// +0.9 us on the 30 us launch of vlp_token_logprob_bwd (profiles/vocab_row_refactor_ab.txt).
+template <typename Policy>
+__global__ __launch_bounds__(CE_THREADS) void dlogits_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                                 const float* __restrict__ lse, const float* __restrict__ rc,
+                                                                 f16* __restrict__ dl, int64_t ldd, int V, const float* __restrict__ rc_scale, Policy p) {
+    const int row = blockIdx.y;
+    const f16* x = logits + (int64_t)row * ld;
+    f16* d = dl + (int64_t)row * ldd;
+    const float c = p.row_const(rc, rc_scale, row);
+    const float l = lse[row];
+    int64_t lab = labels[row];
+    lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
+    const int n8 = (int)(ldd >> 3);
+    if (p.zero_row(lab)) {
+        f16x8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[e] = (f16)0.f;
+        for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) st8(d + ch * 8, z);
+        return;
+    }
+    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
+        const int v0 = ch * 8;
+        f16x8 o;
+        if (v0 + 8 <= V) {
+            f16x8 t = ld8(x + v0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (f16)p.elem(c, (float)t[e], l, v0 + e, lab);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int v = v0 + e;
+                o[e] = v < V ? (f16)p.elem(c, (float)x[v], l, v, lab) : (f16)0.f;
+            }
+        }
+        st8(d + v0, o);
+    }
+}
+// the layout and alignment checks and the launch geometry of the two templates, for all entry points
+template <typename Policy>
+static int row_lse_launch(const char* who, const char* layout_msg, const void* logits, int64_t ld, const int64_t* labels, float* lse, float* out, int rows,
+                          int V, Policy p, hipStream_t s) {
+    VLP_CHECK_ARG(ld % 8 == 0 && ld >= V && (uintptr_t)logits % 16 == 0, "%s", layout_msg);
+    hipLaunchKernelGGL(row_lse_kernel<Policy>, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)logits, ld, labels, lse, out, V, p);
+    VLP_CHECK_LAUNCH(who);
+    return VLP_OK;
+}
+template <typename Policy>
+static int dlogits_row_launch(const char* who, int min_V, const void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* rc,
+                              const float* rc_scale, void* dlogits, int64_t ldd, int rows, int V, Policy p, void* stream) {
+    VLP_CHECK_ARG(rows > 0 && V >= min_V && ld % 8 == 0 && ld >= V && ldd % 8 == 0 && ldd >= V, "%s: layout", who);
+    VLP_CHECK_ARG(((uintptr_t)logits | (uintptr_t)dlogits) % 16 == 0, "%s: alignment", who);
+    int bx = cdiv(ldd / 8, CE_THREADS);
+    if (bx > 16) bx = 16;
+    hipLaunchKernelGGL(dlogits_row_kernel<Policy>, dim3(bx, rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)logits, ld, labels, lse, rc,
+                       (f16*)dlogits, ldd, V, rc_scale, p);
+    VLP_CHECK_LAUNCH(who);
+    return VLP_OK;
+}
+
+// cross entropy: row_loss[row] = lse - logit[label];  d row_loss / d z[w] = p[w] - [w == label], times coef[row] * grad_scale
+struct CeRow {
+    static constexpr bool SUM_D = false;
+    DEVFN float row_out(const f16* x, int64_t lab, int, float mx, float ls, float) const { return (mx + ls) - (float)x[lab]; }
+};
+struct CeGrad {
+    DEVFN bool zero_row(int64_t) const { return false; }
+    DEVFN float row_const(const float* coef, const float* gscale, int row) const { return coef[row] * gscale[0]; }
+    DEVFN float elem(float c, float z, float l, int v, int64_t lab) const { return c * (__expf(z - l) - (v == lab ? 1.f : 0.f)); }
+};
 
 // single block: masking, per-sample sums, drop-worst selection by rank, normalisation (modeling.py:1083-1093)
 __global__ __launch_bounds__(1024) void mlm_finish_kernel(const float* __restrict__ row_loss, const int64_t* __restrict__ weights,
@@ -91,8 +141,8 @@ __global__ __launch_bounds__(1024) void mlm_finish_kernel(const float* __restric
         den_part += k * wsum[b];
         loss_part += k * sb;
     }
-    const float den = block_reduce_sum(den_part, red) + 1e-5f;
-    const float tot = block_reduce_sum(loss_part, red);
+    const float den = block_reduce_sum<1024>(den_part, red) + 1e-5f;
+    const float tot = block_reduce_sum<1024>(loss_part, red);
     if (threadIdx.x == 0) loss[0] = tot / den;
     __syncthreads();
     for (int i = threadIdx.x; i < B * P; i += blockDim.x) coef[i] = keep[i / P] * (float)weights[i] / den;
@@ -102,57 +152,21 @@ extern "C" int vlp_mlm_loss_fwd(const vlp_mlm_loss_fwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->labels && a->weights && a->loss && a->lse && a->coef && a->row_loss, "vlp_mlm_loss_fwd: null operand");
     VLP_ENTER(a->logits, "vlp_mlm_loss_fwd");
     VLP_CHECK_ARG(a->B > 0 && a->P > 0 && a->V > 0 && a->B <= 4096, "vlp_mlm_loss_fwd: bad shape (B <= 4096)");
-    VLP_CHECK_ARG(a->ld_logits % 8 == 0 && a->ld_logits >= a->V && (uintptr_t)a->logits % 16 == 0, "vlp_mlm_loss_fwd: logits layout");
     VLP_CHECK_ARG(a->drop_worst_ratio >= 0.f && a->drop_worst_ratio < 1.f, "vlp_mlm_loss_fwd: drop_worst_ratio");
     hipStream_t s = (hipStream_t)stream;
-    const int rows = a->B * a->P;
-    hipLaunchKernelGGL(ce_row_kernel, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)a->logits, a->ld_logits, a->labels, a->lse, a->row_loss, a->V);
-    VLP_CHECK_LAUNCH("vlp_mlm_loss_fwd(ce)");
+    const int rc = row_lse_launch("vlp_mlm_loss_fwd(ce)", "vlp_mlm_loss_fwd: logits layout", a->logits, a->ld_logits, a->labels, a->lse, a->row_loss,
+                                  a->B * a->P, a->V, CeRow{}, s);
+    if (rc != VLP_OK) return rc;
     const int keep_n = vlp_drop_worst_keep_count(a->B, a->drop_worst_ratio);
     hipLaunchKernelGGL(mlm_finish_kernel, dim3(1), dim3(1024), 3 * a->B * sizeof(float), s, a->row_loss, a->weights, a->loss, a->coef, a->B, a->P, keep_n);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_fwd(finish)");
     return VLP_OK;
 }
-
-__global__ __launch_bounds__(CE_THREADS) void ce_bwd_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                            const float* __restrict__ lse, const float* __restrict__ coef,
-                                                            const float* __restrict__ gscale, f16* __restrict__ dl, int64_t ldd, int V) {
-    const int row = blockIdx.y;
-    const f16* x = logits + (int64_t)row * ld;
-    f16* d = dl + (int64_t)row * ldd;
-    const float c = coef[row] * gscale[0];
-    const float l = lse[row];
-    int64_t lab = labels[row];
-    lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
-    const int n8 = (int)(ldd >> 3);
-    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
-        const int v0 = ch * 8;
-        f16x8 o;
-        if (v0 + 8 <= V) {
-            f16x8 t = ld8(x + v0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)(c * (__expf((float)t[e] - l) - ((v0 + e) == lab ? 1.f : 0.f)));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int v = v0 + e;
-                o[e] = v < V ? (f16)(c * (__expf((float)x[v] - l) - (v == lab ? 1.f : 0.f))) : (f16)0.f;
-            }
-        }
-        st8(d + v0, o);
-    }
-}
 extern "C" int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->labels && a->lse && a->coef && a->grad_scale && a->dlogits, "vlp_mlm_loss_bwd: null operand");
     VLP_ENTER(a->logits, "vlp_mlm_loss_bwd");
-    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->ld_logits % 8 == 0 && a->ld_dlogits % 8 == 0 && a->ld_dlogits >= a->V, "vlp_mlm_loss_bwd: layout");
-    VLP_CHECK_ARG(((uintptr_t)a->logits | (uintptr_t)a->dlogits) % 16 == 0, "vlp_mlm_loss_bwd: alignment");
-    int bx = cdiv(a->ld_dlogits / 8, CE_THREADS);
-    if (bx > 16) bx = 16;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits, a->labels,
-                       a->lse, a->coef, a->grad_scale, (f16*)a->dlogits, a->ld_dlogits, a->V);
-    VLP_CHECK_LAUNCH("vlp_mlm_loss_bwd");
-    return VLP_OK;
+    return dlogits_row_launch("vlp_mlm_loss_bwd", 1, a->logits, a->ld_logits, a->labels, a->lse, a->coef, a->grad_scale, a->dlogits, a->ld_dlogits, a->rows,
+                              a->V, CeGrad{}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -162,46 +176,12 @@ extern "C" int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream) {
 // With m = max, S = sum exp(z - m), A = sum_{w != ignore} (z_w - m) and logp_w = z_w - m - log S:
 //   sum_w q log q    = (V-2) s log s + c log c   (q_log_q: a constant of the buffer, passed in as the caller rounds it)
 //   sum_w q logp     = s (A - (V-1) log S - logp_t) + c logp_t
-// so the same two passes as ce_row_kernel give the row's KL without a third one.
+// so the two passes of row_lse_kernel give the row's KL without a third one.
 // ---------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(CE_THREADS) void ce_ls_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                               float* __restrict__ lse, float* __restrict__ row_loss, int V, float smooth,
-                                                               float confidence, float q_log_q, int ignore) {
-    __shared__ float sh[8];
-    const int row = blockIdx.x;
-    const f16* x = logits + (int64_t)row * ld;
-    const int v8 = V >> 3;
-    float mx = -INFINITY;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)t[e]);
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) mx = fmaxf(mx, (float)x[i]);
-    mx = block_reduce_max(mx, sh);
-    float s = 0.f, a = 0.f;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float d = (float)t[e] - mx;
-            s += __expf(d);
-            a += d;
-        }
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) {
-        const float d = (float)x[i] - mx;
-        s += __expf(d);
-        a += d;
-    }
-    s = block_reduce_sum(s, sh);
-    a = block_reduce_sum(a, sh);
-    if (threadIdx.x == 0) {
-        const float ls = __logf(s);
-        int64_t lab = labels[row];
-        lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
-        lse[row] = mx + ls;
+struct CeLsRow {
+    static constexpr bool SUM_D = true;
+    float smooth, confidence, q_log_q; int ignore;
+    DEVFN float row_out(const f16* x, int64_t lab, int V, float mx, float ls, float a) const {
         float r = 0.f;
         if (lab != ignore) {
             a -= (float)x[ignore] - mx;                                   // A runs over w != ignore
@@ -209,175 +189,72 @@ __global__ __launch_bounds__(CE_THREADS) void ce_ls_row_kernel(const f16* __rest
             const float sum_lp = a - (float)(V - 1) * ls;                 // sum_{w != ignore} logp[w]
             r = q_log_q - smooth * (sum_lp - lpt) - confidence * lpt;
         }
-        row_loss[row] = r;
+        return r;
     }
-}
+};
+// d row_loss / d z[w] = p[w] * sum(q) - q[w]; zero on a row whose label is `ignore`
+struct CeLsGrad {
+    float smooth, confidence, q_sum; int ignore;
+    DEVFN bool zero_row(int64_t lab) const { return lab == ignore; }
+    DEVFN float row_const(const float* coef, const float* gscale, int row) const { return coef[row] * gscale[0]; }
+    DEVFN float elem(float c, float z, float l, int v, int64_t lab) const {
+        const float q = v == lab ? confidence : (v == ignore ? 0.f : smooth);
+        return c * (__expf(z - l) * q_sum - q);
+    }
+};
 
 extern "C" int vlp_mlm_loss_ls_fwd(const vlp_mlm_loss_ls_fwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->labels && a->weights && a->loss && a->lse && a->coef && a->row_loss, "vlp_mlm_loss_ls_fwd: null operand");
     VLP_ENTER(a->logits, "vlp_mlm_loss_ls_fwd");
     VLP_CHECK_ARG(a->B > 0 && a->P > 0 && a->V > 2 && a->B <= 4096, "vlp_mlm_loss_ls_fwd: bad shape (B <= 4096, V > 2)");
-    VLP_CHECK_ARG(a->ld_logits % 8 == 0 && a->ld_logits >= a->V && (uintptr_t)a->logits % 16 == 0, "vlp_mlm_loss_ls_fwd: logits layout");
     VLP_CHECK_ARG(a->drop_worst_ratio >= 0.f && a->drop_worst_ratio < 1.f, "vlp_mlm_loss_ls_fwd: drop_worst_ratio");
     VLP_CHECK_ARG(a->smooth >= 0.f && a->confidence >= 0.f && a->q_sum > 0.f && a->ignore_index >= 0 && a->ignore_index < a->V,
                   "vlp_mlm_loss_ls_fwd: smoothing parameters");
     hipStream_t s = (hipStream_t)stream;
-    const int rows = a->B * a->P;
-    hipLaunchKernelGGL(ce_ls_row_kernel, dim3(rows), dim3(CE_THREADS), 0, s, (const f16*)a->logits, a->ld_logits, a->labels, a->lse, a->row_loss,
-                       a->V, a->smooth, a->confidence, a->q_log_q, a->ignore_index);
-    VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(row)");
+    const int rc = row_lse_launch("vlp_mlm_loss_ls_fwd(row)", "vlp_mlm_loss_ls_fwd: logits layout", a->logits, a->ld_logits, a->labels, a->lse, a->row_loss,
+                                  a->B * a->P, a->V, CeLsRow{a->smooth, a->confidence, a->q_log_q, a->ignore_index}, s);
+    if (rc != VLP_OK) return rc;
     const int keep_n = vlp_drop_worst_keep_count(a->B, a->drop_worst_ratio);
     hipLaunchKernelGGL(mlm_finish_kernel, dim3(1), dim3(1024), 3 * a->B * sizeof(float), s, a->row_loss, a->weights, a->loss, a->coef, a->B, a->P, keep_n);
     VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_fwd(finish)");
     return VLP_OK;
 }
-
-// d row_loss / d z[w] = p[w] * sum(q) - q[w]; zero on a row whose label is `ignore` and in the pad columns V..ldd
-__global__ __launch_bounds__(CE_THREADS) void ce_ls_bwd_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                               const float* __restrict__ lse, const float* __restrict__ coef,
-                                                               const float* __restrict__ gscale, f16* __restrict__ dl, int64_t ldd, int V,
-                                                               float smooth, float confidence, float q_sum, int ignore) {
-    const int row = blockIdx.y;
-    const f16* x = logits + (int64_t)row * ld;
-    f16* d = dl + (int64_t)row * ldd;
-    int64_t lab = labels[row];
-    lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
-    const int n8 = (int)(ldd >> 3);
-    if (lab == ignore) {
-        f16x8 z;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) z[e] = (f16)0.f;
-        for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) st8(d + ch * 8, z);
-        return;
-    }
-    const float c = coef[row] * gscale[0];
-    const float l = lse[row];
-    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
-        const int v0 = ch * 8;
-        f16x8 o;
-        if (v0 + 8 <= V) {
-            f16x8 t = ld8(x + v0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int v = v0 + e;
-                const float q = v == lab ? confidence : (v == ignore ? 0.f : smooth);
-                o[e] = (f16)(c * (__expf((float)t[e] - l) * q_sum - q));
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int v = v0 + e;
-                const float q = v == lab ? confidence : (v == ignore ? 0.f : smooth);
-                o[e] = v < V ? (f16)(c * (__expf((float)x[v] - l) * q_sum - q)) : (f16)0.f;
-            }
-        }
-        st8(d + v0, o);
-    }
-}
 extern "C" int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->labels && a->lse && a->coef && a->grad_scale && a->dlogits, "vlp_mlm_loss_ls_bwd: null operand");
     VLP_ENTER(a->logits, "vlp_mlm_loss_ls_bwd");
-    VLP_CHECK_ARG(a->rows > 0 && a->V > 2 && a->ld_logits % 8 == 0 && a->ld_dlogits % 8 == 0 && a->ld_dlogits >= a->V && a->ld_logits >= a->V,
-                  "vlp_mlm_loss_ls_bwd: layout");
-    VLP_CHECK_ARG(((uintptr_t)a->logits | (uintptr_t)a->dlogits) % 16 == 0, "vlp_mlm_loss_ls_bwd: alignment");
     VLP_CHECK_ARG(a->smooth >= 0.f && a->confidence >= 0.f && a->q_sum > 0.f && a->ignore_index >= 0 && a->ignore_index < a->V,
                   "vlp_mlm_loss_ls_bwd: smoothing parameters");
-    int bx = cdiv(a->ld_dlogits / 8, CE_THREADS);
-    if (bx > 16) bx = 16;
-    hipLaunchKernelGGL(ce_ls_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits, a->labels,
-                       a->lse, a->coef, a->grad_scale, (f16*)a->dlogits, a->ld_dlogits, a->V, a->smooth, a->confidence, a->q_sum, a->ignore_index);
-    VLP_CHECK_LAUNCH("vlp_mlm_loss_ls_bwd");
-    return VLP_OK;
+    return dlogits_row_launch("vlp_mlm_loss_ls_bwd", 3, a->logits, a->ld_logits, a->labels, a->lse, a->coef, a->grad_scale, a->dlogits, a->ld_dlogits,
+                              a->rows, a->V, CeLsGrad{a->smooth, a->confidence, a->q_sum, a->ignore_index}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Log-probability of one chosen token per row (SCST: the sampled caption's log-probs, modeling.py:1229-1235):
 //   logp[r] = logit[r, id[r]] - lse_r;  backward dlogits[r, v] = g[r] * ([v == id[r]] - exp(logit[r, v] - lse_r)).
-// The same two passes as ce_row_kernel / ce_bwd_kernel; g is a per-row upstream gradient of either sign (it carries the loss scale).
+// g is a per-row upstream gradient of either sign (it carries the loss scale).
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CE_THREADS) void token_logprob_row_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
-                                                                       float* __restrict__ logp, float* __restrict__ lse, int V) {
-    __shared__ float sh[8];
-    const int row = blockIdx.x;
-    const f16* x = logits + (int64_t)row * ld;
-    const int v8 = V >> 3;
-    float mx = -INFINITY;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mx = fmaxf(mx, (float)t[e]);
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) mx = fmaxf(mx, (float)x[i]);
-    mx = block_reduce_max(mx, sh);
-    float s = 0.f;
-    for (int c = threadIdx.x; c < v8; c += CE_THREADS) {
-        f16x8 t = ld8(x + c * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += __expf((float)t[e] - mx);
-    }
-    for (int i = v8 * 8 + threadIdx.x; i < V; i += CE_THREADS) s += __expf((float)x[i] - mx);
-    s = block_reduce_sum(s, sh);
-    if (threadIdx.x == 0) {
-        const float l = mx + __logf(s);
-        int64_t id = ids[row];
-        id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-        lse[row] = l;
-        logp[row] = (float)x[id] - l;
-    }
-}
+struct TokenLogpRow {
+    static constexpr bool SUM_D = false;
+    DEVFN float row_out(const f16* x, int64_t id, int, float mx, float ls, float) const { return (float)x[id] - (mx + ls); }
+};
+struct TokenLogpGrad {
+    DEVFN bool zero_row(int64_t) const { return false; }
+    DEVFN float row_const(const float* g, const float*, int row) const { return g[row]; }
+    DEVFN float elem(float c, float z, float l, int v, int64_t id) const { return c * ((v == id ? 1.f : 0.f) - __expf(z - l)); }
+};
 
 extern "C" int vlp_token_logprob_fwd(const vlp_token_logprob_fwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->ids && a->logp && a->lse, "vlp_token_logprob_fwd: null operand");
     VLP_ENTER(a->logits, "vlp_token_logprob_fwd");
-    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->ld_logits % 8 == 0 && a->ld_logits >= a->V && (uintptr_t)a->logits % 16 == 0,
-                  "vlp_token_logprob_fwd: layout");
-    hipLaunchKernelGGL(token_logprob_row_kernel, dim3(a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits,
-                       a->ids, a->logp, a->lse, a->V);
-    VLP_CHECK_LAUNCH("vlp_token_logprob_fwd");
-    return VLP_OK;
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 0, "vlp_token_logprob_fwd: layout");
+    return row_lse_launch("vlp_token_logprob_fwd", "vlp_token_logprob_fwd: layout", a->logits, a->ld_logits, a->ids, a->lse, a->logp, a->rows, a->V,
+                          TokenLogpRow{}, (hipStream_t)stream);
 }
-
-__global__ __launch_bounds__(CE_THREADS) void token_logprob_bwd_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
-                                                                       const float* __restrict__ lse, const float* __restrict__ g,
-                                                                       f16* __restrict__ dl, int64_t ldd, int V) {
-    const int row = blockIdx.y;
-    const f16* x = logits + (int64_t)row * ld;
-    f16* d = dl + (int64_t)row * ldd;
-    const float c = g[row];
-    const float l = lse[row];
-    int64_t id = ids[row];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    const int n8 = (int)(ldd >> 3);
-    for (int ch = blockIdx.x * CE_THREADS + threadIdx.x; ch < n8; ch += gridDim.x * CE_THREADS) {
-        const int v0 = ch * 8;
-        f16x8 o;
-        if (v0 + 8 <= V) {
-            f16x8 t = ld8(x + v0);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)(c * (((v0 + e) == id ? 1.f : 0.f) - __expf((float)t[e] - l)));
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int v = v0 + e;
-                o[e] = v < V ? (f16)(c * ((v == id ? 1.f : 0.f) - __expf((float)x[v] - l))) : (f16)0.f;
-            }
-        }
-        st8(d + v0, o);
-    }
-}
-
 extern "C" int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->logits && a->ids && a->lse && a->g && a->dlogits, "vlp_token_logprob_bwd: null operand");
     VLP_ENTER(a->logits, "vlp_token_logprob_bwd");
-    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->ld_logits % 8 == 0 && a->ld_logits >= a->V && a->ld_dlogits % 8 == 0 && a->ld_dlogits >= a->V,
-                  "vlp_token_logprob_bwd: layout");
-    VLP_CHECK_ARG(((uintptr_t)a->logits | (uintptr_t)a->dlogits) % 16 == 0, "vlp_token_logprob_bwd: alignment");
-    int bx = cdiv(a->ld_dlogits / 8, CE_THREADS);
-    if (bx > 16) bx = 16;
-    hipLaunchKernelGGL(token_logprob_bwd_kernel, dim3(bx, a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream, (const f16*)a->logits, a->ld_logits,
-                       a->ids, a->lse, a->g, (f16*)a->dlogits, a->ld_dlogits, a->V);
-    VLP_CHECK_LAUNCH("vlp_token_logprob_bwd");
-    return VLP_OK;
+    return dlogits_row_launch("vlp_token_logprob_bwd", 1, a->logits, a->ld_logits, a->ids, a->lse, a->g, nullptr, a->dlogits, a->ld_dlogits, a->rows, a->V,
+                              TokenLogpGrad{}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -437,14 +314,14 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const f16* x, int64_t ld, 
             s += fmaxf(xv, 0.f) - xv * yv + log1pf(__expf(-fabsf(xv)));
         }
     }
-    s = block_reduce_sum(s, sh);
+    s = block_reduce_sum<256>(s, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 __global__ void bce_finish_kernel(const float* part, int n, float inv, float* loss) {
     __shared__ float sh[8];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) s += part[i];
-    s = block_reduce_sum(s, sh);
+    s = block_reduce_sum<256>(s, sh);
     if (threadIdx.x == 0) loss[0] = s * inv;
 }
 template <bool SPARSE>
