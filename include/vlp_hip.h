@@ -279,6 +279,11 @@ int vlp_layernorm_bwd_reduce_batched(const float* parts, const void* const* dst,
  *   dA = dsim . V, dV = dsim^T . A.  Writes ONLY the masked rows of d_vis_h / d_vispe_h (through ReLU + dropout exactly as
  *   vlp_embed_bwd does for the other rows: y > 0 mask and the dropout multiplier of element (region row, col) of streams
  *   vis_stream / vispe_stream), and d_pooled_pre[b] = (sum_i dA_i) * (1 - pooled[b]^2) (backward of the pooler's tanh, :416).
+ * Precondition of vlp_pretext_fwd / vlp_pretext_bwd: the Pm positions of a row of vis_masked_pos are DISTINCT and within 1..Nv, as the
+ *   loader draws them without replacement (seq2seq_loader.py:267-269).  The loss takes the diagonal of `probs` as the target and
+ *   vlp_pretext_bwd writes one row of d_vis_h / d_vispe_h per position: with a duplicate two work items store the same row and the
+ *   diagonal is no longer the target, so duplicates are outside the contract and are not diagnosed.  A position outside 1..Nv is clamped
+ *   to the nearest region by the two pretext kernels and ignored by vlp_region_mask_build (which is indifferent to duplicates).
  */
 int vlp_region_mask_build(const int64_t* vis_masked_pos, int32_t B, int32_t Pm, int32_t Nv, uint8_t* out, void* stream);
 typedef struct {

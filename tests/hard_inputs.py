@@ -118,6 +118,35 @@ def layernorm_restatement_fp32(x, gamma, beta, eps=1e-5, two_pass=True):
     return (gamma.float() * ((xf - u) * rstd) + beta.float()).half(), u[:, 0], rstd[:, 0]
 
 
+def pretext_sim_window(A, V, H):
+    """The similarity matrix of vlp_pretext_fwd in fp64, and which of its entries may round to either neighbouring fp16 value in the kernel.
+    A, V: [..., Pm, H] fp16 values (A = vispe + pooled already rounded to fp16).  The kernel sums each H-long dot product in fp32 -- 8
+    fused multiply-adds per 8-column chunk, ceil(H / 512) chunks per lane, then a 6-level wave reduction: at most 8 ceil(H / 512) + 6
+    roundings of 2^-24, each against no more than sum |a_k v_k| -- and rounds the sum to fp16.  An entry whose fp64 value is farther than
+    that from every fp16 rounding boundary rounds the same way in both; the others are returned as `ambiguous`.  (sim fp64, ambiguous)."""
+    a, v = A.double(), V.double()
+    s64 = a @ v.transpose(-1, -2)
+    slack = (8 * ((H + 511) // 512) + 6) * 2.0 ** -24 * (a.abs() @ v.abs().transpose(-1, -2))
+    return s64, (s64 - slack).half() != (s64 + slack).half()
+
+
+def pretext_sim_restatement_fp32(A, V):
+    """sim[i][j] of pretext_fwd_kernel (csrc/pretext.hip) in its own summation order, fp32: lane l walks the 8-column chunks l, l + 64, ...
+    of the row with one fma per column (the product of two fp16 values is exact in fp32, so an fma is an fp32 add of it), a butterfly over
+    the 64 lanes adds the partial sums (both partners of a pair compute the same sum), and the result is rounded to fp16.  A, V: [Pm, H]."""
+    Pm, H = A.shape
+    nch = H // 8
+    prod = (A.float()[:, None, :] * V.float()[None, :, :]).view(Pm, Pm, nch, 8)
+    lanes = torch.zeros(Pm, Pm, 64)
+    for c in range(nch):
+        for t in range(8):
+            lanes[:, :, c % 64] = lanes[:, :, c % 64] + prod[:, :, c, t]
+    idx = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[:, :, idx ^ o]
+    return lanes[:, :, 0].half()
+
+
 def ce_rows_restatement_fp32(logits, labels):
     """fp32 max-subtracted log-sum-exp per row and row loss lse - logit[label] (the arithmetic of row_lse_kernel with the CE policy): (lse, row_loss)."""
     x = logits.float()

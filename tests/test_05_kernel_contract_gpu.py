@@ -126,6 +126,10 @@ def _nt_run(variant, M, N, Kd, epi, x, w, ops):
 
 @pytest.mark.parametrize("variant,M,N,Kd,epi", _nt_cases())
 def test_gemm_nt_ragged(variant, M, N, Kd, epi, gen):
+    """Every product variant at a ragged N.  The persistent k-stream kernel (gemm_nt_ps.hip, variants 256 / 264) is NOT run here: it needs
+    N % 128 == 0 and NT_N holds no multiple of 128, so a `variant = 264` case checks the launcher's fallback to a ring and nothing else.
+    Neither is the lean multiplier instantiation of variants 21 / 29 (N % 16 == 0).  The kernels themselves under guards:
+    tests/test_07_step_kernel_contract_gpu.py::test_gemm_nt_persistent_guarded and ::test_gemm_nt_lean_multiplier_guarded."""
     if not (LAB or variant in NT_PRODUCT):
         pytest.skip("investigation variant: needs a -DVLP_LAB_BUILD library")
     n8 = roundup8(N)
@@ -171,12 +175,16 @@ def test_gemm_nt_ragged(variant, M, N, Kd, epi, gen):
     for k, g in ops.items():
         G.assert_untouched(g, name=k)
     if variant in (77, 264):
-        # what the launcher does with a wave-pipelined / persistent variant at a ragged N (csrc/gemm_nt.hip): the persistent kernel (264)
-        # needs N % 128 == 0 and always runs on a ring here; the wave-pipelined kernel (77) carries a ragged N itself and leaves only the
-        # erf epilogues to a ring.  The launcher names what it ran, and either way the bits are the ring's (same ascending-k fp32 chains)
+        # what the launcher does with a wave-pipelined / persistent variant at a ragged N (csrc/gemm_nt.hip).  264: no N of this list is a
+        # multiple of 128, so the persistent kernel never runs here -- the launcher must fall back to a ring and say so; this is a test
+        # of the fallback, not of gemm_nt_ps.hip (see the docstring).  77: the wave-pipelined kernel carries a ragged N itself and leaves
+        # only the erf epilogues to a ring.  Either way the bits are the ring's (same ascending-k fp32 chains)
         ring = 29 if N > 1024 else 27
         erf = epi in ("gelu_preact", "mul_gelu_grad")
-        assert resolved == (ring if (variant == 264 or erf) else 77), resolved
+        if variant == 264:
+            assert N % 128 != 0 and resolved == ring, (N, resolved)
+        else:
+            assert resolved == (ring if erf else 77), resolved
         y2, pre2 = _nt_run(ring, M, N, Kd, epi, x, w, ops)
         assert K.gemm_nt_resolved_variant() == ring
         assert torch.equal(G.bits(y.view), G.bits(y2.view))
