@@ -35,6 +35,8 @@ extern "C" {
 /* + vlp_bce_sparse_loss_fwd / vlp_bce_sparse_loss_bwd, vlp_vqa_answer_rows (VQA 2.0 on real data: answer targets as (index, score) pairs):
  * purely additive as well. */
 /* + vlp_cider_d / vlp_cider_d_workspace_bytes (the SCST reward on the device): purely additive as well. */
+/* + vlp_cider_d_df / vlp_cider_d_df_workspace_bytes (the same reward with document frequencies from a resident table): purely additive as
+ * well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -672,6 +674,35 @@ typedef struct {
 } vlp_cider_d_args;
 int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
 int vlp_cider_d(const vlp_cider_d_args* a, void* stream);
+
+/* vlp_cider_d with the document frequencies of a resident table (vlp_amd/scst.py DocFreq: df over a whole training set, one document per
+ * image) instead of the call's own references.  The specification is CiderD(df=<DocFreq>).compute_score; everything of vlp_cider_d that is
+ * not restated here holds as it stands (strings, groups, ref_count, norms, bigram length, clipped products, zero-norm rule, Gaussian
+ * penalty, mean over orders and references, x 10, reward, accepted shapes and strides, two capturable launches, fixed summation order, no
+ * atomics, bit-equal repeats, nothing written outside scores, reward and the workspace):
+ *   - the key of an n-gram t0..t(k-1), k <= 4, is ((t0+1) << 48) | ((t1+1) << 32) | ((t2+1) << 16) | (t3+1), absent positions contributing
+ *     0; df_keys [df_n] holds the keys of the table strictly ascending AS UNSIGNED 64-bit integers, df_vals [df_n] their df (>= 1);
+ *   - df(g) = df_vals[i] where df_keys[i] is g's key, 0 when the table has no such key.  A token < 0 or >= 65535 inside a string makes
+ *     every n-gram that contains it a miss (df 0): no key is formed from such a token, so it cannot alias another n-gram;
+ *   - idf = logf((float)n_docs) - logf(fmaxf(1.f, (float)df)), in that order; weight = tf * idf, also for a miss (tf * logf(n_docs));
+ *   - there is no `mult` factor anywhere: mult only says how many hypotheses a group has (in vlp_cider_d it doubles df because the
+ *     reference sets are listed twice);
+ *   - the lookup is a lower-bound binary search over df_keys with unsigned 64-bit comparison, at most ceil(log2(df_n + 1)) probes, one
+ *     lane per (position, order) so that the probes of a string overlap.  The table is read only through vector loads; nothing is ever
+ *     written to it.
+ * Accepted beyond vlp_cider_d's conditions on `s`: df_n >= 0 (an empty table is legal and makes every df 0; the two arrays are then not
+ * read), 1 <= n_docs <= 2^24 (so that (float)n_docs is exact), df_keys non-null and 8-byte aligned and df_vals non-null and 4-byte aligned
+ * when df_n > 0, s.workspace of vlp_cider_d_df_workspace_bytes() bytes (0 for a refused shape; larger than vlp_cider_d's: idf is kept as a
+ * full-width fp32 per hypothesis position and order, table df reaches 2^24).  Anything else returns VLP_ERR_BAD_ARG before a launch. */
+typedef struct {
+    vlp_cider_d_args s;                                        /* strings, shapes, outputs and workspace, as for vlp_cider_d */
+    const uint64_t* df_keys;                                   /* [df_n] strictly ascending (unsigned) */
+    const int32_t* df_vals;                                    /* [df_n] 1 <= df <= n_docs */
+    int64_t df_n;
+    int64_t n_docs;                                            /* documents the table was counted over */
+} vlp_cider_d_df_args;
+int64_t vlp_cider_d_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
+int vlp_cider_d_df(const vlp_cider_d_df_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

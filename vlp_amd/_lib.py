@@ -149,6 +149,10 @@ class CiderDArgs(C.Structure):
                 ("workspace", vp), ("workspace_bytes", i64)]
 
 
+class CiderDDfArgs(C.Structure):
+    _fields_ = [("s", CiderDArgs), ("df_keys", vp), ("df_vals", vp), ("df_n", i64), ("n_docs", i64)]
+
+
 class MlmLossFwdArgs(C.Structure):
     _fields_ = [("logits", vp), ("ld_logits", i64), ("labels", vp), ("weights", vp), ("loss", vp), ("lse", vp), ("coef", vp),
                 ("row_loss", vp), ("B", i32), ("P", i32), ("V", i32), ("drop_worst_ratio", f32)]
@@ -241,6 +245,8 @@ SYMBOLS = {
     "vlp_gelu_bwd": (C.c_int, [vp, vp, vp, i64, vp]),
     "vlp_cider_d_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vlp_cider_d": (C.c_int, [C.POINTER(CiderDArgs), vp]),
+    "vlp_cider_d_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "vlp_cider_d_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
     "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
@@ -690,6 +696,12 @@ def cider_d(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, workspace
     strided, the ids of a row are contiguous.  workspace: the caller's uint8 device buffer of cider_d_workspace_bytes() (16-byte aligned);
     None = a fresh allocation of this call (torch's caching allocator: no synchronisation, ordered on the current stream, fine under graph
     capture).  Launches on the current stream."""
+    a = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, cider_d_workspace_bytes)
+    _check(load().vlp_cider_d(C.byref(a), stream_ptr()))
+
+
+def _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes):
+    """The operand checks and the argument struct cider_d and cider_d_df share."""
     _req_cuda(hyp, ref, ref_count, scores, reward, workspace)
     if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
         raise RuntimeError("vlp_amd.cider_d: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
@@ -703,10 +715,30 @@ def cider_d(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, workspace
     if reward is not None and (reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() < G):
         raise RuntimeError("vlp_amd.cider_d: reward must be contiguous f32 [%d]" % G)
     if workspace is None:
-        workspace = torch.empty(max(cider_d_workspace_bytes(G, R, T, mult), 1), device=hyp.device, dtype=torch.uint8)
+        workspace = torch.empty(max(workspace_bytes(G, R, T, mult), 1), device=hyp.device, dtype=torch.uint8)
     a = CiderDArgs(ptr(hyp), hyp.stride(0), ptr(ref), ref.stride(0), ref.stride(1), ptr(ref_count), G, R, T, mult, sigma, ptr(scores), ptr(reward),
                    ptr(workspace), _nbytes(workspace))
-    _check(load().vlp_cider_d(C.byref(a), stream_ptr()))
+    a._keep = workspace                      # a fresh allocation lives until the launch has been enqueued
+    return a
+
+
+def cider_d_df_workspace_bytes(G, R, T, mult):
+    """0 for a shape vlp_cider_d_df refuses."""
+    return int(load().vlp_cider_d_df_workspace_bytes(G, R, T, mult))
+
+
+def cider_d_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward=None, sigma=6.0, workspace=None):
+    """cider_d with document frequencies from a resident table (include/vlp_hip.h vlp_cider_d_df; vlp_amd.scst.DocFreq.to(device) makes the
+    two tensors): df_keys int64 [N] holding the table's uint64 keys bit for bit (ascending as unsigned), df_vals int32 [N], n_docs the
+    number of documents.  N = 0 is an empty table.  workspace: cider_d_df_workspace_bytes() bytes.  Everything else as cider_d."""
+    _req_cuda(df_keys, df_vals)
+    if (df_keys.dtype not in (torch.int64, torch.uint64) or df_vals.dtype != torch.int32 or df_keys.dim() != 1 or df_vals.dim() != 1
+            or not df_keys.is_contiguous() or not df_vals.is_contiguous() or df_keys.numel() != df_vals.numel()):
+        raise RuntimeError("vlp_amd.cider_d_df: df_keys int64 [N] (the uint64 keys' bits) and df_vals int32 [N], contiguous")
+    s = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, cider_d_df_workspace_bytes)
+    n = df_keys.numel()
+    a = CiderDDfArgs(s, ptr(df_keys) if n else None, ptr(df_vals) if n else None, n, int(n_docs))
+    _check(load().vlp_cider_d_df(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

@@ -12,7 +12,8 @@ modules, so that the import lines of vlp/run_img2txt_dist.py:23-30,405 and vlp/d
 `misc.data_parallel` (DataParallelImbalance, run_img2txt_dist.py:30) resolves to vlp_amd.data_parallel, and, when apex is not
 installed, an `apex.optimizers` module exposing `FusedAdam` is provided (run_img2txt_dist.py:406 imports it from there).  Likewise, when
 pycocoevalcap is not installed, `pycocoevalcap.cider.cider.Cider` resolves to vlp_amd.scst.CiderD, so that vlp/scst_utils.py
-(`Cider(df='corpus')`, :10-12) imports and scores unmodified.
+(`Cider(df='corpus')`, :10-12) imports and scores unmodified.  The shimmed `Cider` also takes a document-frequency table of a whole training set,
+`Cider(df=<vlp_amd.scst.DocFreq>)`, in place of coco-caption's `df=<pickle name>`; any other string still raises.
 The tokenizer (`pytorch_pretrained_bert.tokenization`) is NOT provided: it is CPU-side text processing outside the hot path; keep
 using the reference's file for it.  install() refuses to shadow an already imported package of that name unless force=True.
 """

@@ -15,6 +15,12 @@
 //                        them the string's four L2 norms; a hypothesis also keeps (df, tf, first) per position for the second pass.
 //   cider_score_kernel   one block per group, one wave per hypothesis, one lane per position: tf of the hypothesis' n-grams in each
 //                        valid reference of its group, the clipped dot products, norms, length penalty, mean; then the reward.
+//
+// vlp_cider_d_df takes df from a resident table (sorted uint64 keys, int32 df; vlp_amd/scst.py DocFreq) instead of the call's references.
+// Both kernels are the ones above with TABLE = true: the counting pass drops its loop over the groups -- every (position, order) of the
+// block's string gets a lane of its own that packs the n-gram's key and looks it up (a lower-bound binary search of dependent global loads:
+// 256 independent searches per block overlap) -- and hands the scoring pass idf as a full-width fp32 next to the packed (tf, first), since
+// table df does not fit cd_pack's 11 bits.
 #include "common.h"
 
 #define CD_THREADS 256
@@ -36,6 +42,27 @@ DEVFN int cd_row_len(bool is_zero, int seg, int P, int T) {
     m >>= seg * P;                                   // seg * P <= 63
     if (P < 64) m &= (1ull << P) - 1ull;
     return m ? (int)__builtin_ctzll(m) + 1 : T;
+}
+
+// df of one n-gram in the table: lower bound of `key` in keys[0, n) (ascending as unsigned), at most ceil(log2(n + 1)) probes -- the key at
+// the final bound is the last one probed there, so the equality test costs no further probe.  Plain per-lane vector loads; read only.
+struct cd_table {
+    const uint64_t* keys;
+    const int32_t* vals;
+    int64_t n;
+    float n_docs;                                    // exact: n_docs <= 2^24
+};
+
+DEVFN int cd_table_df(const cd_table& t, uint64_t key) {
+    int64_t lo = 0, hi = t.n;
+    uint64_t at_hi = 0;                              // keys[hi] once hi < n (key 0 never occurs)
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);   // lo <= mid < hi <= n
+        const uint64_t v = t.keys[mid];
+        if (v < key) lo = mid + 1;
+        else { hi = mid; at_hi = v; }
+    }
+    return at_hi == key ? t.vals[hi] : 0;
 }
 
 DEVFN int cd_ref_count(const int32_t* ref_count, int g, int R) {
@@ -67,7 +94,11 @@ DEVFN void cd_stage_refs(const vlp_cider_d_args& a, int row0, int rows, int* dst
     }
 }
 
-__global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_args a, int P, int tile_groups, int* info, float* norms) {
+// TABLE: df from `tab` (one lane per position and order: P is 64; tile_groups is unused, no dynamic LDS) and idf_out [mult*G][4][T] written
+// for the hypotheses; otherwise df from the call's own references as described above (tab and idf_out unused).
+template <bool TABLE>
+__global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_args a, int P, int tile_groups, int* info, float* norms, cd_table tab,
+                                                                 float* idf_out) {
     extern __shared__ __attribute__((aligned(16))) int cd_tile[];      // [tile_groups][R][T + CD_PAD]
     __shared__ int qrow[64 + CD_PAD], srow[64 + CD_PAD];               // the block's string with the query's / a reference's sentinel
     __shared__ int cnt[4][CD_THREADS];
@@ -100,6 +131,24 @@ __global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_arg
     int a0 = CD_HYP_END, a1 = CD_HYP_END, a2 = CD_HYP_END, a3 = CD_HYP_END;
     if (p < T) { a0 = qrow[p]; a1 = qrow[p + 1]; a2 = qrow[p + 2]; a3 = qrow[p + 3]; }
 
+    if constexpr (TABLE) {
+        // lane (order k = tid / 64, position tid % 64): the table df of the k+1-gram that starts there.  A sentinel (the string ends inside
+        // the n-gram) or an id outside [0, 65535) forms no key: df 0
+        const int k = worker, q = p;                                   // P is 64 here
+        int df = 0;
+        if (q < T) {
+            uint64_t key = 0;
+            bool ok = true;
+            for (int j = 0; j <= k; ++j) {
+                const int t = qrow[q + j];
+                ok = ok && t >= 0 && t < 65535;
+                key |= (uint64_t)(((unsigned)t + 1u) & 0xffffu) << (48 - 16 * j);   // (used only when every id is in range)
+            }
+            if (ok) df = cd_table_df(tab, key);
+        }
+        cnt[k][q] = df;
+        __syncthreads();
+    } else {
     // groups whose valid references hold the k-gram at p
     int c1 = 0, c2 = 0, c3 = 0, c4 = 0;
     for (int g0 = 0; g0 < G; g0 += tile_groups) {
@@ -124,6 +173,7 @@ __global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_arg
     }
     cnt[0][tid] = c1; cnt[1][tid] = c2; cnt[2][tid] = c3; cnt[3][tid] = c4;
     __syncthreads();
+    }
     if (tid >= 64) return;
 
     // wave 0, lane = position: multiplicity and first occurrence inside the own string, then weights and norms
@@ -141,21 +191,30 @@ __global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_arg
             b0 = b1; b1 = b2; b2 = b3;
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            for (int w = 0; w < W; ++w) groups[k] += cnt[k][w * P + tid];
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (TABLE) groups[k] = cnt[k][tid];              // the table's df itself
+            else
+                for (int w = 0; w < W; ++w) groups[k] += cnt[k][w * P + tid];
+        }
     }
-    const float ref_len = logf((float)SH);
+    const float ref_len = logf(TABLE ? tab.n_docs : (float)SH);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+        const float idf = ref_len - logf(fmaxf(1.f, (float)(TABLE ? groups[k] : a.mult * groups[k])));
         float v = 0.f;
-        if (tid < T && tf[k] > 0 && first[k]) v = (float)tf[k] * (ref_len - logf(fmaxf(1.f, (float)(a.mult * groups[k]))));
+        if (tid < T && tf[k] > 0 && first[k]) v = (float)tf[k] * idf;
         const float n2 = wave_sum(v * v);
         if (tid == 0) norms[(int64_t)s * 4 + k] = sqrtf(n2);
-        if (is_hyp && tid < T) info[((int64_t)s * 4 + k) * T + tid] = cd_pack(groups[k], tf[k], tf[k] > 0 && first[k]);
+        if (is_hyp && tid < T) {
+            info[((int64_t)s * 4 + k) * T + tid] = cd_pack(TABLE ? 0 : groups[k], tf[k], tf[k] > 0 && first[k]);
+            if constexpr (TABLE) idf_out[((int64_t)s * 4 + k) * T + tid] = idf;
+        }
     }
 }
 
-__global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const float* norms) {
+// TABLE: idf of each hypothesis position and order comes from idf_in (the counting pass wrote it), not from the packed group count.
+template <bool TABLE>
+__global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const float* norms, const float* idf_in) {
     extern __shared__ __attribute__((aligned(16))) int cd_refs[];      // [R][T + CD_PAD]
     __shared__ int ref_len_s[8];
     __shared__ float sc[2];
@@ -174,13 +233,14 @@ __global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const fl
     }
     __syncthreads();
 
-    const float ref_len = logf((float)SH);
+    const float ref_len = logf((float)SH);                             // (unused with TABLE)
     float idf[4], hv[4], nh[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
     bool first[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int pk = lane < T ? info[((int64_t)h * 4 + k) * T + lane] : 0;
-        idf[k] = ref_len - logf(fmaxf(1.f, (float)(a.mult * (pk & 2047))));
+        if constexpr (TABLE) idf[k] = lane < T ? idf_in[((int64_t)h * 4 + k) * T + lane] : 0.f;
+        else idf[k] = ref_len - logf(fmaxf(1.f, (float)(a.mult * (pk & 2047))));
         hv[k] = (float)((pk >> 11) & 127) * idf[k];
         first[k] = (pk >> 18) & 1;
         nh[k] = norms[(int64_t)h * 4 + k];
@@ -238,17 +298,22 @@ extern "C" int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, 
     return (bytes + 255) / 256 * 256;
 }
 
+// the operand checks both entry points share; `need` is the entry's own workspace size
+#define CD_CHECK_ARGS(a, who, need)                                                                                                              \
+    VLP_CHECK_ARG(cd_shape_ok((a)->G, (a)->R, (a)->T, (a)->mult), who ": needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult 1 or 2 (G %d, R %d, T %d, mult %d)", \
+                  (a)->G, (a)->R, (a)->T, (a)->mult);                                                                                            \
+    VLP_CHECK_ARG((a)->hyp && (a)->ref && (a)->scores && (a)->workspace, who ": null operand");                                                  \
+    VLP_CHECK_ARG(!(a)->reward || (a)->mult == 2, who ": reward = scores[g] - scores[G + g] needs mult == 2");                                   \
+    VLP_CHECK_ARG((a)->hyp_ld >= (a)->T && (a)->ref_ld >= (a)->T && (a)->ref_group_stride >= (int64_t)((a)->R - 1) * (a)->ref_ld + (a)->T,       \
+                  who ": strides shorter than the rows");                                                                                        \
+    VLP_CHECK_ARG((a)->sigma > 0.f, who ": sigma must be positive");                                                                             \
+    VLP_CHECK_ARG((a)->workspace_bytes >= (need) && (uintptr_t)(a)->workspace % 16 == 0, who ": workspace of %lld bytes, needs %lld (16-byte aligned)", \
+                  (long long)(a)->workspace_bytes, (long long)(need))
+
 extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
     VLP_CHECK_ARG(a, "vlp_cider_d: null args");
-    VLP_CHECK_ARG(cd_shape_ok(a->G, a->R, a->T, a->mult), "vlp_cider_d: needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult 1 or 2 (G %d, R %d, T %d, mult %d)",
-                  a->G, a->R, a->T, a->mult);
-    VLP_CHECK_ARG(a->hyp && a->ref && a->scores && a->workspace, "vlp_cider_d: null operand");
-    VLP_CHECK_ARG(!a->reward || a->mult == 2, "vlp_cider_d: reward = scores[g] - scores[G + g] needs mult == 2");
-    VLP_CHECK_ARG(a->hyp_ld >= a->T && a->ref_ld >= a->T && a->ref_group_stride >= (int64_t)(a->R - 1) * a->ref_ld + a->T, "vlp_cider_d: strides shorter than the rows");
-    VLP_CHECK_ARG(a->sigma > 0.f, "vlp_cider_d: sigma must be positive");
     const int64_t need = vlp_cider_d_workspace_bytes(a->G, a->R, a->T, a->mult);
-    VLP_CHECK_ARG(a->workspace_bytes >= need && (uintptr_t)a->workspace % 16 == 0, "vlp_cider_d: workspace of %lld bytes, needs %lld (16-byte aligned)",
-                  (long long)a->workspace_bytes, (long long)need);
+    CD_CHECK_ARGS(a, "vlp_cider_d", need);
     VLP_ENTER(a->ref, "vlp_cider_d");
     const int SH = a->mult * a->G, SR = a->G * a->R, ldr = a->T + CD_PAD;
     const int P = cd_pow2_at_least(a->T);
@@ -256,11 +321,41 @@ extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
     if (tile_groups > a->G) tile_groups = a->G;
     int* info = (int*)a->workspace;
     float* norms = (float*)(info + cd_info_ints(a->G, a->T, a->mult));
-    hipLaunchKernelGGL(cider_count_kernel, dim3(SH + SR), dim3(CD_THREADS), (size_t)tile_groups * a->R * ldr * sizeof(int), (hipStream_t)stream, *a, P,
-                       tile_groups, info, norms);
+    hipLaunchKernelGGL(cider_count_kernel<false>, dim3(SH + SR), dim3(CD_THREADS), (size_t)tile_groups * a->R * ldr * sizeof(int), (hipStream_t)stream, *a, P,
+                       tile_groups, info, norms, cd_table{}, (float*)nullptr);
     VLP_CHECK_LAUNCH("vlp_cider_d (count)");
-    hipLaunchKernelGGL(cider_score_kernel, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
-                       (const float*)norms);
+    hipLaunchKernelGGL(cider_score_kernel<false>, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
+                       (const float*)norms, (const float*)nullptr);
     VLP_CHECK_LAUNCH("vlp_cider_d (score)");
+    return VLP_OK;
+}
+
+// workspace: int32 info[mult*G][4][T] (tf, first), f32 idf[mult*G][4][T], then f32 norms[mult*G + G*R][4]
+extern "C" int64_t vlp_cider_d_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    if (!cd_shape_ok(G, R, T, mult)) return 0;
+    const int64_t bytes = 4 * (2 * cd_info_ints(G, T, mult) + 4 * ((int64_t)mult * G + (int64_t)G * R));
+    return (bytes + 255) / 256 * 256;
+}
+
+extern "C" int vlp_cider_d_df(const vlp_cider_d_df_args* d, void* stream) {
+    VLP_CHECK_ARG(d, "vlp_cider_d_df: null args");
+    const vlp_cider_d_args* a = &d->s;
+    const int64_t need = vlp_cider_d_df_workspace_bytes(a->G, a->R, a->T, a->mult);
+    CD_CHECK_ARGS(a, "vlp_cider_d_df", need);
+    VLP_CHECK_ARG(d->df_n >= 0 && d->n_docs >= 1 && d->n_docs <= (1 << 24), "vlp_cider_d_df: needs df_n >= 0 and 1 <= n_docs <= 2^24 (df_n %lld, n_docs %lld)",
+                  (long long)d->df_n, (long long)d->n_docs);
+    VLP_CHECK_ARG(d->df_n == 0 || (d->df_keys && d->df_vals && (uintptr_t)d->df_keys % 8 == 0 && (uintptr_t)d->df_vals % 4 == 0),
+                  "vlp_cider_d_df: a table of %lld keys needs non-null df_keys (8-byte aligned) and df_vals (4-byte aligned)", (long long)d->df_n);
+    VLP_ENTER(a->ref, "vlp_cider_d_df");
+    const int SH = a->mult * a->G, SR = a->G * a->R, ldr = a->T + CD_PAD;
+    int* info = (int*)a->workspace;
+    float* idf = (float*)(info + cd_info_ints(a->G, a->T, a->mult));
+    float* norms = idf + cd_info_ints(a->G, a->T, a->mult);
+    const cd_table tab = {d->df_keys, d->df_vals, d->df_n, (float)d->n_docs};
+    hipLaunchKernelGGL(cider_count_kernel<true>, dim3(SH + SR), dim3(CD_THREADS), 0, (hipStream_t)stream, *a, 64, 0, info, norms, tab, idf);
+    VLP_CHECK_LAUNCH("vlp_cider_d_df (count)");
+    hipLaunchKernelGGL(cider_score_kernel<true>, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
+                       (const float*)norms, (const float*)idf);
+    VLP_CHECK_LAUNCH("vlp_cider_d_df (score)");
     return VLP_OK;
 }

@@ -151,6 +151,13 @@ def build_parser():
                         "sample.  'image' scores against up to 5 captions of the sample's image (all of COCO's), which is how CIDEr is defined -- a "
                         "deliberate departure from the reference's objective; needs --packed_features (the loader collects the captions per "
                         "image id from --token_file)")
+    p.add_argument("--scst_df", default="batch", metavar="{batch,train,PATH}",
+                   help="--scst: the document frequencies of the CIDEr-D reward.  'batch' is the reference's Cider(df='corpus'): counted over the "
+                        "references of each step.  'train' counts them once at start-up over ALL captions of --token_file, one document per image "
+                        "(vlp_amd.scst.DocFreq; needs --packed_features and a caption --token_file; every rank builds the same table from the whole "
+                        "list); a PATH loads a table saved by `python -m vlp_amd.cider_df` (its --max_len_b and [SEP] id must be this run's).  A "
+                        "deliberate departure from the reference's objective, like --scst_refs image; works with either --scst_reward and either "
+                        "--scst_refs (with 'device' the table is uploaded once and stays resident)")
     return p
 
 
@@ -172,6 +179,14 @@ def derive_args(args):
         assert args.max_pred == 0 and args.mask_prob == 0, "no mask for scst!"
     if args.scst_refs == "image" and not (args.scst and args.packed_features):
         raise ValueError("--scst_refs image needs --scst and --packed_features (the captions of an image come from the packed loader)")
+    if args.scst_df != "batch":
+        if not args.scst:
+            raise ValueError("--scst_df %s needs --scst (it chooses the document frequencies of the SCST reward)" % args.scst_df)
+        if args.scst_df == "train" and not (args.packed_features and args.token_file):
+            raise ValueError("--scst_df train needs --packed_features and a caption --token_file (the table is counted over the captions of "
+                             "--token_file); or give the path of a table saved by `python -m vlp_amd.cider_df`")
+        if args.scst_df != "train" and not os.path.isfile(args.scst_df):
+            raise ValueError("--scst_df: 'batch', 'train' or the path of a saved table; there is no file %s" % args.scst_df)
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -296,7 +311,32 @@ def train_step(model, optimizer, batch, lr_this_step, mask_image_regions=False, 
     return loss_tuple
 
 
-def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host"):
+def read_examples(token_file):
+    """--token_file: the whole example list, (image id, [caption token ids]) or the 4-tuples of VQA."""
+    with open(token_file) as f:
+        return [tuple(e) if len(e) == 4 else (e[0], e[1]) for e in json.load(f)]
+
+
+def scst_doc_freq(args):
+    """--scst_df: None for 'batch'; the table counted over the WHOLE --token_file list for 'train' (not the rank's shard: every rank holds the
+    same table); a saved table for a path, refused when it was built for another caption format than this run's."""
+    from .data import examples_have_answers
+    from .scst import DocFreq
+    if args.scst_df == "batch":
+        return None
+    if args.scst_df == "train":
+        examples = read_examples(args.token_file)
+        if examples_have_answers(examples):
+            raise ValueError("--scst_df train needs a caption --token_file, and %s holds VQA examples" % args.token_file)
+        return DocFreq.from_examples(examples, args.max_len_b, synthetic.SEP_ID)
+    table = DocFreq.load(args.scst_df)
+    if (table.max_len_b, table.sep_id) != (args.max_len_b, synthetic.SEP_ID):
+        raise ValueError("--scst_df %s was built for --max_len_b %s and [SEP] id %s; this run has --max_len_b %d and [SEP] id %d: rebuild it with "
+                         "python -m vlp_amd.cider_df" % (args.scst_df, table.max_len_b, table.sep_id, args.max_len_b, synthetic.SEP_ID))
+    return table
+
+
+def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host", df=None):
     """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
     train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
     baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
@@ -304,7 +344,8 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     unless accumulating, "optimizer" (tools/scst_bench.py times them).
     reward_on="device" (--scst_reward device) computes the reward with vlp_amd.scst.self_critical_reward_device instead: nothing leaves the
     device between the sampled decode and the backward, and the phase is marked "reward_device".  A batch whose 12th element is a CaptionRefs
-    (--scst_refs image) is scored against those references, on either side, instead of its own ground-truth ids."""
+    (--scst_refs image) is scored against those references, on either side, instead of its own ground-truth ids.  df (--scst_df): a
+    vlp_amd.scst.DocFreq whose document frequencies the reward uses, on either side, instead of the step's own references'; None = those."""
     if mark is None:
         def mark(phase):
             pass
@@ -326,15 +367,16 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gt_ids = input_ids[:, len_vis_input + 2:]
+    kw = {} if df is None else {"df": df}
     if reward_on == "device":
-        reward, _ = self_critical_reward_device(greedy_res, ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids, gen_result)
+        reward, _ = self_critical_reward_device(greedy_res, ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids, gen_result, **kw)
         mean_reward = reward.mean()
         mark("reward_device")
     else:
         if isinstance(ans_labels, CaptionRefs):
-            reward, _ = self_critical_reward_refs(greedy_res, ans_labels, gen_result)
+            reward, _ = self_critical_reward_refs(greedy_res, ans_labels, gen_result, **kw)
         else:
-            reward, _ = self_critical_reward(greedy_res, gt_ids, gen_result, gt_ids.size(0))
+            reward, _ = self_critical_reward(greedy_res, gt_ids, gen_result, gt_ids.size(0), **kw)
         reward = torch.from_numpy(reward).float().to(gen_result.device)
         mean_reward = reward.mean()
         mark("reward_host")
@@ -363,8 +405,7 @@ def build_packed_loader(args, device):
     wrapping around so that every rank gets ceil(N / W) samples, rank r taking every W-th element (vlp_amd.data.distributed_sampler_indices)."""
     from .data import BatchPrefetcher, PackedRegionStore, TextPreprocessor, examples_have_answers, VQA_EXAMPLE_FORMAT
     store = PackedRegionStore(args.packed_features)
-    with open(args.token_file) as f:
-        examples = [tuple(e) if len(e) == 4 else (e[0], e[1]) for e in json.load(f)]
+    examples = read_examples(args.token_file)
     if args.tasks == "vqa2" and not examples_have_answers(examples):     # (a file that mixes the two forms raises in there)
         raise ValueError("--tasks vqa2 needs answers, and --token_file %s has none: %s" % (args.token_file, VQA_EXAMPLE_FORMAT))
     kw = dict(max_pred=args.max_pred, mask_prob=args.mask_prob, vocab_size=KNOWN_VOCABS.get(args.bert_model, 28996), cls_id=synthetic.CLS_ID,
@@ -435,10 +476,13 @@ def main(argv=None):
     if recover_step:
         logger.info("***** Recover model: %d *****", recover_step)
         args.model_recover_path = os.path.join(args.output_dir, "model.{0}.bin".format(recover_step))
-    rl_crit = None
+    rl_crit, scst_df = None, None
     if args.scst:
         from .scst import RewardCriterion
         rl_crit = RewardCriterion()
+        scst_df = scst_doc_freq(args)
+        if scst_df is not None:
+            logger.info("--scst_df %s: %d n-grams over %d images", args.scst_df, len(scst_df), scst_df.n_docs)
         if args.drop_prob > 0:
             logger.info("--scst: --drop_prob %g is inert: the sampled decode and the scoring pass both run without dropout (INTEGRATION.md)",
                         args.drop_prob)
@@ -478,7 +522,7 @@ def main(argv=None):
             lr = args.learning_rate * warmup_linear(global_step / t_total, args.warmup_proportion)
             if args.scst:
                 loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
-                                         accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward)
+                                         accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward, df=scst_df)
                 rewards.append(mean_r.detach())
             else:
                 lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,

@@ -19,7 +19,14 @@ The reward is computed where the reference computes it, on the host: one device 
 self_critical_reward_device computes the same reward with the vlp_cider_d kernels (no host round trip), and together with
 self_critical_reward_refs accepts several references per sample (input_prep.CaptionRefs: all captions of the image, which is how CIDEr is
 defined; the reference's recipe scores against the one caption the loader drew).  CiderD stays the specification of both.
+
+Document frequencies of a whole training set (coco-caption's `df=<file>` mode, the line scst_utils.py:17 reaches for): DocFreq is a table
+n-gram -> number of IMAGES whose captions hold it, built once from the example list (DocFreq.from_examples, `python -m vlp_amd.cider_df`)
+with every caption in the exact string form the reward sees.  CiderD(df=<DocFreq>) takes df from it and ref_len = log(n_docs); an n-gram the
+table does not hold has df 0.  The three self_critical_reward* functions pass a `df=` table through (None = the call's own references, the
+reference's behaviour); on the device the table is two resident arrays searched by the vlp_cider_d_df kernels.
 """
+import itertools
 from collections import Counter, OrderedDict
 
 import numpy as np
@@ -35,12 +42,151 @@ def _ngrams(words, n):
     return counts
 
 
+MAX_TOKEN_ID = 65534            # ids 0..65534 have keys; +1 keeps an absent position (0) apart from id 0
+MAX_DOCS = 1 << 24              # float32(n_docs) is exact on the device
+
+
+def pack_ngram(ids):
+    """The uint64 key of an n-gram of 1..4 ids, each in 0..65534: ((t0+1) << 48) | ((t1+1) << 32) | ((t2+1) << 16) | (t3+1), absent positions
+    contributing 0.  Distinct n-grams have distinct keys, key 0 never occurs.  A python int."""
+    if not 1 <= len(ids) <= 4:
+        raise ValueError("pack_ngram: an n-gram has 1..4 ids")
+    key = 0
+    for j, t in enumerate(ids):
+        if not 0 <= t <= MAX_TOKEN_ID:
+            raise ValueError("pack_ngram: id %d is outside 0..%d" % (t, MAX_TOKEN_ID))
+        key |= (int(t) + 1) << (48 - 16 * j)
+    return key
+
+
+class DocFreq(object):
+    """Document frequencies of a training set: keys uint64 [N] strictly ascending (pack_ngram), vals int32 [N] (1 <= df <= n_docs), n_docs the
+    number of documents (images).  max_len_b / sep_id record the caption format the table was built for (None when unknown)."""
+
+    def __init__(self, keys, vals, n_docs, max_len_b=None, sep_id=None):
+        keys, vals = np.ascontiguousarray(keys), np.ascontiguousarray(vals)
+        if keys.dtype != np.uint64 or vals.dtype != np.int32 or keys.ndim != 1 or keys.shape != vals.shape:
+            raise ValueError("DocFreq: keys must be uint64 [N] and vals int32 [N]")
+        n_docs = int(n_docs)
+        if not 1 <= n_docs <= MAX_DOCS:
+            raise ValueError("DocFreq: n_docs %d is outside 1..2**24 (float32(n_docs) must be exact on the device)" % n_docs)
+        if len(keys):
+            if keys[0] == 0:
+                raise ValueError("DocFreq: key 0 is no n-gram")
+            if (keys[1:] == keys[:-1]).any():
+                raise ValueError("DocFreq: duplicate keys")
+            if (keys[1:] < keys[:-1]).any():
+                raise ValueError("DocFreq: keys are not sorted (ascending as unsigned 64-bit integers)")
+            if int(vals.min()) < 1:
+                raise ValueError("DocFreq: a document frequency below 1")
+            if int(vals.max()) > n_docs:
+                raise ValueError("DocFreq: a document frequency above n_docs = %d" % n_docs)
+        self.keys, self.vals, self.n_docs = keys, vals, n_docs
+        self.max_len_b = None if max_len_b is None else int(max_len_b)
+        self.sep_id = None if sep_id is None else int(sep_id)
+        self._resident, self._scorer = {}, None
+
+    def __len__(self):
+        return len(self.keys)
+
+    @classmethod
+    def from_examples(cls, examples, max_len_b, sep_id, chunk=1 << 16):
+        """examples: the loader's list of (image id, [caption token ids], ...).  A document is one image: ALL its captions in the list, each
+        as the reference row BatchPrefetcher builds -- the first max_len_b tokens, [SEP], then 0 -- read like array_to_str reads it (up to and
+        including the first 0, so [SEP] and the trailing 0 are tokens of n-grams; a caption of max_len_b or more tokens has no 0).
+        df(g) = the number of images whose strings hold g.  Vectorised numpy per chunk of `chunk` images; no python loop per n-gram."""
+        max_len_b, sep_id = int(max_len_b), int(sep_id)
+        T = max_len_b + 1
+        if max_len_b < 0 or not 0 <= sep_id <= MAX_TOKEN_ID:
+            raise ValueError("DocFreq: needs max_len_b >= 0 and sep_id in 0..%d" % MAX_TOKEN_ID)
+        index = {}
+        img = np.fromiter((index.setdefault(ex[0], len(index)) for ex in examples), dtype=np.int64, count=len(examples))
+        if not index:
+            raise ValueError("DocFreq: no examples")
+        order = np.argsort(img, kind="stable")
+        img_sorted = img[order]
+        cols = np.arange(T)
+        parts_k, parts_v = [], []
+        lo = 0
+        while lo < len(order):
+            hi = int(np.searchsorted(img_sorted, img_sorted[lo] + chunk, side="left"))
+            caps = [examples[i][1][:max_len_b] for i in order[lo:hi]]
+            lens = np.fromiter((len(c) for c in caps), dtype=np.int64, count=len(caps))
+            flat = np.fromiter(itertools.chain.from_iterable(caps), dtype=np.int64, count=int(lens.sum()))
+            if len(flat) and (flat.min() < 0 or flat.max() > MAX_TOKEN_ID):
+                raise ValueError("DocFreq: a caption token id is outside 0..%d" % MAX_TOKEN_ID)
+            rows = np.zeros((len(caps), T + 3), dtype=np.uint64)                      # id + 1 (so the row's padding 0 is 1); 0 = past the row
+            text = rows[:, :T]
+            text[:] = 1
+            text[cols[None, :] < lens[:, None]] = (flat + 1).astype(np.uint64)
+            text[np.arange(len(caps)), lens] = sep_id + 1
+            is0 = text == 1
+            slen = np.where(is0.any(1), is0.argmax(1) + 1, T)                        # up to and including the first 0
+            docs = img_sorted[lo:hi]
+            key = np.zeros((len(caps), T), dtype=np.uint64)
+            pairs_k, pairs_d = [], []
+            for k in range(4):
+                key = key | (rows[:, k:k + T] << np.uint64(48 - 16 * k))
+                ok = cols[None, :] + (k + 1) <= slen[:, None]
+                pairs_k.append(key[ok])
+                pairs_d.append(np.broadcast_to(docs[:, None], ok.shape)[ok])
+            pk, pd = np.concatenate(pairs_k), np.concatenate(pairs_d)
+            o = np.lexsort((pk, pd))
+            pk, pd = pk[o], pd[o]
+            new = np.ones(len(pk), dtype=bool)
+            new[1:] = (pk[1:] != pk[:-1]) | (pd[1:] != pd[:-1])                       # an n-gram counts once per image
+            k_u, k_c = np.unique(pk[new], return_counts=True)
+            parts_k.append(k_u)
+            parts_v.append(k_c)
+            lo = hi
+        keys, inv = np.unique(np.concatenate(parts_k), return_inverse=True)
+        vals = np.bincount(inv, weights=np.concatenate(parts_v), minlength=len(keys)).astype(np.int32)
+        return cls(keys.astype(np.uint64), vals, len(index), max_len_b, sep_id)
+
+    def save(self, path):
+        """An .npz of keys, vals, n_docs, max_len_b and sep_id (-1 = unknown), nothing else."""
+        with open(path, "wb") as f:
+            np.savez(f, keys=self.keys, vals=self.vals, n_docs=np.int64(self.n_docs),
+                     max_len_b=np.int64(-1 if self.max_len_b is None else self.max_len_b), sep_id=np.int64(-1 if self.sep_id is None else self.sep_id))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            if sorted(z.files) != ["keys", "max_len_b", "n_docs", "sep_id", "vals"]:
+                raise ValueError("DocFreq.load: %s is not a table written by DocFreq.save (fields %s)" % (path, sorted(z.files)))
+            m, s = int(z["max_len_b"]), int(z["sep_id"])
+            return cls(z["keys"], z["vals"], int(z["n_docs"]), None if m < 0 else m, None if s < 0 else s)
+
+    def get(self, ngram, default=0.0):
+        """df of an n-gram given as a tuple of ids or of id strings (CiderD's words); `default` when the table does not hold it -- an id
+        outside 0..65534, or a word that is no id, has no key and is a miss."""
+        try:
+            key = pack_ngram([int(w) for w in ngram])
+        except ValueError:
+            return default
+        i = int(np.searchsorted(self.keys, np.uint64(key)))
+        return int(self.vals[i]) if i < len(self.keys) and int(self.keys[i]) == key else default
+
+    def to(self, device):
+        """(keys, vals) on `device`: keys as an int64 tensor holding the uint64 keys bit for bit, vals int32.  Uploaded once per device and
+        kept (the device reward reads the same two arrays every step)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._resident:
+            self._resident[device] = (torch.from_numpy(self.keys.view(np.int64)).to(device), torch.from_numpy(self.vals).to(device))
+        return self._resident[device]
+
+
 class CiderD(object):
-    """CIDEr-D with corpus document frequencies (df='corpus'); compute_score(gts, res) -> (mean score, per-key scores as np.ndarray)."""
+    """CIDEr-D; compute_score(gts, res) -> (mean score, per-key scores as np.ndarray).  df='corpus': document frequencies of the references of
+    each call, ref_len = log(number of reference sets).  df=<DocFreq>: document frequencies of that table (0 for an n-gram it does not hold),
+    ref_len = log(table.n_docs); everything else is the same."""
 
     def __init__(self, n=4, sigma=6.0, df="corpus"):
-        if df != "corpus":
-            raise NotImplementedError("CiderD: only df='corpus' (document frequencies of the references of each call) is implemented")
+        if not isinstance(df, DocFreq) and not (isinstance(df, str) and df == "corpus"):
+            raise NotImplementedError("CiderD: only df='corpus' (document frequencies of the references of each call) or a DocFreq table is "
+                                      "implemented")
         self.n, self.sigma, self.df = n, float(sigma), df
 
     def _vec(self, counts, df, ref_len):
@@ -78,11 +224,14 @@ class CiderD(object):
             assert type(ref) is list and len(ref) > 0
             ctest.append(_ngrams(hypo[0].split(), self.n))
             crefs.append([_ngrams(r.split(), self.n) for r in ref])
-        df = Counter()
-        for refs in crefs:
-            for g in set(g for r in refs for g in r):
-                df[g] += 1
-        ref_len = np.log(float(len(crefs)))
+        if isinstance(self.df, DocFreq):
+            df, ref_len = self.df, np.log(float(self.df.n_docs))
+        else:
+            df = Counter()
+            for refs in crefs:
+                for g in set(g for r in refs for g in r):
+                    df[g] += 1
+            ref_len = np.log(float(len(crefs)))
         scores = []
         for test, refs in zip(ctest, crefs):
             vh, nh, lh = self._vec(test, df, ref_len)
@@ -117,10 +266,22 @@ def clean_captions(raw, eos_id, pad_id=0):
 _scorer = CiderD(df="corpus")
 
 
-def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None):
+def _table_scorer(df):
+    """The scorer of a `df=` argument: None -> the module's df='corpus' scorer, a DocFreq -> its CiderD (made once per table)."""
+    if df is None:
+        return _scorer
+    if not isinstance(df, DocFreq):
+        raise TypeError("df must be None or a vlp_amd.scst.DocFreq")
+    if df._scorer is None:
+        df._scorer = CiderD(df=df)
+    return df._scorer
+
+
+def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None, df=None):
     """scst_utils.py:36-63: CIDEr-D of the B samples and the B greedy captions (2B hypotheses), each against its own ground truth (so the 2B
     reference sets are the ground truths twice); reward[b, :] = score(sample_b) - score(greedy_b) repeated over the T columns.  Arguments are
-    id tensors or arrays [B, T]; returns (reward [B, T] float64 ndarray, scores [2B])."""
+    id tensors or arrays [B, T]; returns (reward [B, T] float64 ndarray, scores [2B]).  df: a DocFreq whose document frequencies replace the
+    call's own (ignored when a scorer is given)."""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     greedy_res, gt_ids, gen_result = host(greedy_res), host(gt_ids), host(gen_result)
@@ -133,7 +294,7 @@ def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None
         res[i], gts[i] = [gen_s[i]], [gt_s[i]]
     for i in range(B):
         res[B + i], gts[B + i] = [gre_s[i]], [gt_s[i]]
-    _, scores = (scorer or _scorer).compute_score(gts, res)
+    _, scores = (scorer or _table_scorer(df)).compute_score(gts, res)
     d = scores[:B] - scores[B:]
     return np.repeat(d[:, np.newaxis], gen_result.shape[1], 1), scores
 
@@ -158,17 +319,17 @@ def _refs_parts(refs, B):
     return refs[:B].unsqueeze(1), None
 
 
-def self_critical_reward_refs(greedy_res, refs, gen_result):
+def self_critical_reward_refs(greedy_res, refs, gen_result, df=None):
     """self_critical_reward against one OR several references per sample, on the host with CiderD: `refs` is the [B, T] ground-truth ids
     (then this is self_critical_reward itself) or a CaptionRefs (ids [B, R, T], count [B]: sample b is scored against the first count[b]
     rows).  Returns (reward [B, T] float64 ndarray, scores [2B]).  The oracle of self_critical_reward_device, and the host path of
-    multi-reference training."""
+    multi-reference training.  df: a DocFreq whose document frequencies replace the call's own."""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     from .input_prep import CaptionRefs
     B = len(gen_result)
     if not isinstance(refs, CaptionRefs):
-        return self_critical_reward(greedy_res, refs, gen_result, B)
+        return self_critical_reward(greedy_res, refs, gen_result, B, df=df)
     greedy_res, gen_result, ids, count = host(greedy_res), host(gen_result), host(refs.ids), host(refs.count)
     R = ids.shape[1]
     gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
@@ -177,17 +338,19 @@ def self_critical_reward_refs(greedy_res, refs, gen_result):
         res[i], gts[i] = [array_to_str(gen_result[i].tolist())], gt_s[i]
     for i in range(B):
         res[B + i], gts[B + i] = [array_to_str(greedy_res[i].tolist())], gt_s[i]
-    _, scores = _scorer.compute_score(gts, res)
+    _, scores = _table_scorer(df).compute_score(gts, res)
     d = scores[:B] - scores[B:]
     return np.repeat(d[:, np.newaxis], gen_result.shape[1], 1), scores
 
 
-def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, workspace=None):
+def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, workspace=None, df=None):
     """self_critical_reward_refs on the device (vlp_cider_d, csrc/reward.hip): id tensors [B, T] on the GPU, `refs` the [B, T] ground-truth
     ids or a CaptionRefs with ids [B, R, T] of the same T.  Returns (reward f32 [B, T] -- the [B] differences expanded over the columns --,
     scores f32 [2B]) as device tensors; scores_out (f32 [2B]) receives the scores when given; workspace: the caller's kernel scratch
     (_lib.cider_d_workspace_bytes(B, R, T, 2) bytes, uint8), else allocated per call.  No device -> host transfer, no synchronisation: two
-    kernel launches on the current stream, capturable into a graph."""
+    kernel launches on the current stream, capturable into a graph.
+    df: a DocFreq -- the vlp_cider_d_df kernels score with its document frequencies (workspace: _lib.cider_d_df_workspace_bytes).  The table
+    is uploaded by the first call that uses it on a device (DocFreq.to) and stays resident; make that call before a graph capture."""
     from . import _lib as K
     from .input_prep import CaptionRefs
     B, T = gen_result.shape
@@ -199,5 +362,9 @@ def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, w
     hyp = torch.cat([gen_result, greedy_res], 0)
     scores = scores_out if scores_out is not None else torch.empty(2 * B, dtype=torch.float32, device=hyp.device)
     diff = torch.empty(B, dtype=torch.float32, device=hyp.device)
-    K.cider_d(hyp, ids, count, 2, scores, reward=diff, sigma=_scorer.sigma, workspace=workspace)
+    if df is None:
+        K.cider_d(hyp, ids, count, 2, scores, reward=diff, sigma=_scorer.sigma, workspace=workspace)
+    else:
+        keys, vals = df.to(hyp.device)
+        K.cider_d_df(hyp, ids, count, 2, scores, keys, vals, df.n_docs, reward=diff, sigma=_table_scorer(df).sigma, workspace=workspace)
     return diff.unsqueeze(1).expand(B, T), scores
