@@ -442,6 +442,41 @@ def test_layernorm_guarded(M, H, p, gen):
         G.assert_untouched(g, name=name)
 
 
+@pytest.mark.parametrize("M,H", [(4100, 768), (4100, 520)])
+def test_layernorm_bwd_rows_per_wave_guarded(M, H, gen):
+    """M = 4100 is the smallest M at which some waves of the backward walk two rows and the others one (4096 waves in the grid): the
+    next-row prefetch, its rotation into the current row (statistics and LOGICAL row index included) and the tail of the walk run here,
+    which no M <= 4096 reaches.  Packed rows (row_map with gaps: the masks are those of the logical rows), both dropouts, every leading
+    dimension different and > H, NaN behind row M; bounds of test_layernorm_guarded."""
+    rm = torch.arange(M, device=DEV)
+    rm = (rm + rm // 100).to(I32)
+    row_map = vin(rm, fill=0)
+    x = gin(h16(M, H, scale=2.0, gen=gen), pad=8)
+    gamma, beta = vin((1 + 0.1 * torch.randn(H, device=DEV, generator=gen)).half()), h16(H, scale=0.1, gen=gen)
+    dy = gin(h16(M, H, gen=gen), pad=24)
+    x64 = x.view.double().requires_grad_(True)
+    g64, b64 = gamma.vec.double().requires_grad_(True), beta.double().requires_grad_(True)
+    mult = drop_mult_ref(0.2, 3, 9, rm.tolist(), range(H)).double()
+    ref = O.layer_norm(x64, g64, b64) * mult
+    ref.backward(dy.view.double())
+    xd = x64.detach()
+    mean_in, rstd_in = vin(xd.mean(1).float()), vin((1.0 / torch.sqrt(xd.var(1, unbiased=False) + 1e-5)).float())
+    dx, dxd = gout(M, H, pad=16), gout(M, H, pad=32)
+    dg, db = vout(H, HALF), vout(H, HALF)
+    ws = nan_ws(K.layernorm_bwd_workspace_bytes(H))
+    K.layernorm_bwd(dy.view, x.view, gamma.vec, mean_in.vec, rstd_in.vec, dx.view, dg.vec, db.vec, M, H, ws, dx_drop=dxd.view,
+                    dy_drop=(0.2, 3, 9), out_drop=(0.1, 4, 2), row_map=row_map.vec)
+    check_out(dx, x64.grad, 2e-3, "logical", "dx")
+    check_out(dxd, x64.grad * drop_mult_ref(0.1, 4, 2, rm.tolist(), range(H)), 2e-3, "logical", "dx_drop")
+    for g, want, name in ((dg, g64.grad, "dgamma"), (db, b64.grad, "dbeta")):
+        G.assert_written(g, "logical", name)
+        G.assert_finite(g.vec, name)
+        assert rel(g.vec.float(), want) < 3e-3, name
+        G.assert_untouched(g, written="logical", name=name)
+    for g, name in ((x, "x"), (dy, "dy"), (gamma, "gamma"), (mean_in, "mean"), (rstd_in, "rstd"), (row_map, "row_map")):
+        G.assert_untouched(g, name=name)
+
+
 @pytest.mark.parametrize("M,H", [(5, 768), (257, 1032)])
 def test_layernorm_deferred_reduce_guarded(M, H, gen):
     """defer_reduce leaves dgamma / dbeta bit-untouched; the batched second stage writes exactly [H] of each, accumulating (beta = 1)."""

@@ -6,10 +6,18 @@
 // the dropout that follows the embedding LayerNorm (:240); backward replaces their autograd plus the
 // SumBackward of every broadcast bias add.
 #include "common.h"
+#include <climits>
 #include <cstdlib>
 
 #define LN_THREADS 256
 #define LN_WAVES 4
+
+// What the two forward kernels share: the row's dropout key (dropout element = (row, col); packed rows: the LOGICAL row) and the output
+// element from the row's statistics, the affine pair and the dropout multiplier m (1 when dropout is off).
+DEVFN uint32_t ln_fwd_rowkey(const DropCtx& drop, const int32_t* __restrict__ row_map, int row) {
+    return drop.thresh ? drop_rowkey(drop, row_map ? (uint64_t)(uint32_t)row_map[row] : (uint64_t)row) : 0u;
+}
+DEVFN f16 ln_fwd_out(float v, float mu, float rs, f16 gamma, f16 beta, float m) { return (f16)(((float)gamma * ((v - mu) * rs) + (float)beta) * m); }
 
 template <int NP>   // per-lane pieces of 4 halfs (piece k = columns 256k + 4*lane .. +3): H <= 256*NP; at H = 768 every lane holds 12 columns
 __global__ __launch_bounds__(LN_THREADS) void layernorm_fwd_kernel(
@@ -50,7 +58,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_fwd_kernel(
             if (rstd) rstd[row] = rs;
         }
         f16* yr = y + (int64_t)row * ldy;
-        const uint32_t rkey = drop.thresh ? drop_rowkey(drop, row_map ? (uint64_t)(uint32_t)row_map[row] : (uint64_t)row) : 0u;   // dropout element = (row, col)
+        const uint32_t rkey = ln_fwd_rowkey(drop, row_map, row);
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int c = 256 * k + 4 * lane;
@@ -59,7 +67,7 @@ __global__ __launch_bounds__(LN_THREADS) void layernorm_fwd_kernel(
                 float m4[4] = {1.f, 1.f, 1.f, 1.f};
                 if (drop.thresh) drop_mult4(drop, rkey, (uint32_t)c, m4);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (f16)(((float)gv[e] * ((v[k][e] - mu) * rs) + (float)bv[e]) * m4[e]);
+                for (int e = 0; e < 4; ++e) o[e] = ln_fwd_out(v[k][e], mu, rs, gv[e], bv[e], m4[e]);
                 st4_out<VLP_SS_LN>(yr + c, o);
             }
         }
@@ -107,7 +115,7 @@ __global__ __launch_bounds__(LN_THREADS, NC <= 3 ? 6 : 4) void layernorm_fwd_hw_
         }
         if (!live) continue;
         f16* yr = y + (int64_t)row * ldy;
-        const uint32_t rkey = drop.thresh ? drop_rowkey(drop, row_map ? (uint64_t)(uint32_t)row_map[row] : (uint64_t)row) : 0u;   // dropout element = (row, col)
+        const uint32_t rkey = ln_fwd_rowkey(drop, row_map, row);
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             const int c = 256 * k + 8 * hl;
@@ -116,7 +124,7 @@ __global__ __launch_bounds__(LN_THREADS, NC <= 3 ? 6 : 4) void layernorm_fwd_hw_
             if (drop.thresh) drop_mult8(drop, rkey, (uint32_t)c, m8);
             f16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (f16)(((float)gv[e] * ((v[k][e] - mu) * rs) + (float)bv[e]) * m8[e]);
+            for (int e = 0; e < 8; ++e) o[e] = ln_fwd_out(v[k][e], mu, rs, gv[e], bv[e], m8[e]);
             st8_out<VLP_SS_LN>(yr + c, o);
         }
     }
@@ -126,14 +134,16 @@ __global__ __launch_bounds__(LN_THREADS, NC <= 3 ? 6 : 4) void layernorm_fwd_hw_
 // is reduced and stored, so that reads and writes of different iterations overlap -- is SLOWER at every grid size: 12.4 us at one pair per
 // wave (7 spilled registers at the 80-register budget of 6 waves per SIMD), 13.0 / 13.5 / 15.4 / 17.1 us at 2 / 3 / 4 / 5.2 pairs per wave,
 // profiles/r04_layernorm_lab.txt.  One pair per wave with every wave resident at once stays the forward.)
+// The block caps are read once; the per-call decision is a local (the entry points may be driven from several host threads)
+static int env_blocks(const char* name, int dflt, int most) {
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : dflt;
+    return v < 1 || v > most ? dflt : v;
+}
+
 // one row per wave up to this many blocks (VLP_LN_BLOCKS overrides for A/B runs)
 static int ln_fwd_blocks(int M) {
-    static int cap = 0;
-    if (!cap) {
-        const char* e = getenv("VLP_LN_BLOCKS");
-        cap = e ? atoi(e) : 4096;
-        if (cap < 1) cap = 4096;
-    }
+    static const int cap = env_blocks("VLP_LN_BLOCKS", 4096, INT_MAX);
     const int blocks = cdiv(M, LN_WAVES);
     return blocks > cap ? cap : blocks;
 }
@@ -145,34 +155,24 @@ extern "C" int vlp_layernorm_fwd(const vlp_layernorm_fwd_args* a, void* stream) 
     VLP_CHECK_ARG(a->ldx % 8 == 0 && a->ldy % 8 == 0 && a->ldx >= a->H && a->ldy >= a->H, "vlp_layernorm_fwd: leading dims");
     VLP_CHECK_ARG(((uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->gamma | (uintptr_t)a->beta) % 16 == 0, "vlp_layernorm_fwd: alignment");
     DropCtx d = make_drop(a->dropout_p, a->seed, a->rng_stream);
-    const int blocks = ln_fwd_blocks(a->M);
+    const int blocks = ln_fwd_blocks(a->M), hblocks = ln_fwd_blocks((a->M + 1) / 2);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_LN_FWD(NP_)                                                                                                              \
-    hipLaunchKernelGGL(layernorm_fwd_kernel<NP_>, dim3(blocks), dim3(LN_THREADS), 0, s, (const f16*)a->x, a->ldx, (const f16*)a->gamma, \
+#define LAUNCH_LN_FWD(KERNEL_, BLOCKS_)                                                                                        \
+    hipLaunchKernelGGL(KERNEL_, dim3(BLOCKS_), dim3(LN_THREADS), 0, s, (const f16*)a->x, a->ldx, (const f16*)a->gamma,        \
                        (const f16*)a->beta, (f16*)a->y, a->ldy, a->mean, a->rstd, a->M, a->H, a->eps, d, a->row_map)
-    // VLP_LN_HALFWAVE=0: the one-row-per-wave kernel everywhere (A/B runs).  Read once; the per-call decision is a local (the entry
-    // points may be driven from several host threads)
-    static const int use_hw = [] { const char* e = getenv("VLP_LN_HALFWAVE"); return e ? atoi(e) : 1; }();
-    if (use_hw && a->H % 256 == 0 && a->H <= 2048) {
-        bool launched = true;
-        const int hblocks = ln_fwd_blocks((a->M + 1) / 2);
-#define LAUNCH_LN_HW(NC_)                                                                                                                  \
-    hipLaunchKernelGGL(layernorm_fwd_hw_kernel<NC_>, dim3(hblocks), dim3(LN_THREADS), 0, s, (const f16*)a->x, a->ldx, (const f16*)a->gamma, \
-                       (const f16*)a->beta, (f16*)a->y, a->ldy, a->mean, a->rstd, a->M, a->H, a->eps, d, a->row_map)
-        if (a->H == 768) LAUNCH_LN_HW(3);
-        else if (a->H == 256) LAUNCH_LN_HW(1);
-        else if (a->H == 512) LAUNCH_LN_HW(2);
-        else if (a->H == 1024) LAUNCH_LN_HW(4);
-        else if (a->H == 1536) LAUNCH_LN_HW(6);
-        else if (a->H == 2048) LAUNCH_LN_HW(8);
-        else launched = false;         // no half-wave instantiation for this H: the row-per-wave kernel below
-#undef LAUNCH_LN_HW
-        if (launched) { VLP_CHECK_LAUNCH("vlp_layernorm_fwd"); return VLP_OK; }
+    switch (a->H) {                     // the H with a half-wave instantiation; every other H: one row per wave
+        case 256: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<1>, hblocks); break;
+        case 512: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<2>, hblocks); break;
+        case 768: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<3>, hblocks); break;
+        case 1024: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<4>, hblocks); break;
+        case 1536: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<6>, hblocks); break;
+        case 2048: LAUNCH_LN_FWD(layernorm_fwd_hw_kernel<8>, hblocks); break;
+        default:
+            if (a->H <= 768) LAUNCH_LN_FWD(layernorm_fwd_kernel<3>, blocks);
+            else if (a->H <= 1024) LAUNCH_LN_FWD(layernorm_fwd_kernel<4>, blocks);
+            else if (a->H <= 2048) LAUNCH_LN_FWD(layernorm_fwd_kernel<8>, blocks);
+            else LAUNCH_LN_FWD(layernorm_fwd_kernel<16>, blocks);
     }
-    if (a->H <= 768) LAUNCH_LN_FWD(3);
-    else if (a->H <= 1024) LAUNCH_LN_FWD(4);
-    else if (a->H <= 2048) LAUNCH_LN_FWD(8);
-    else LAUNCH_LN_FWD(16);
 #undef LAUNCH_LN_FWD
     VLP_CHECK_LAUNCH("vlp_layernorm_fwd");
     return VLP_OK;
@@ -188,115 +188,24 @@ extern "C" int vlp_layernorm_fwd(const vlp_layernorm_fwd_args* a, void* stream) 
 // the second pass): 168 VGPRs + spills, 3 waves per SIMD, no next-row prefetch -- 20.9 us against 14.5 us for this kernel (tools/ln_lab.py).
 // A third row in flight (prefetch two rows ahead, 128 VGPRs): 17.4 us -- a wave only sees 2.6 rows, the extra requests just queue up front.
 // ---------------------------------------------------------------------------------------------
-#ifndef LNB_WAVES      // block geometry of the backward kernel; overridable for A/B builds (tools/build_variant_lib.sh)
-#define LNB_WAVES 8
-#endif
+#define LNB_WAVES 8      // block geometry of the backward kernel
 #define LNB_THREADS (64 * LNB_WAVES)
 #define LNB_BLOCKS (4096 / LNB_WAVES)
-#ifndef LNB_MINW
-#define LNB_MINW 4
-#endif
 
-template <int NP>
-__global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? LNB_MINW : (NP == 4 ? 3 : 2)) void layernorm_bwd_kernel(
-    const f16* __restrict__ dy, int64_t lddy, const f16* __restrict__ x, int64_t ldx, const f16* __restrict__ gamma,
-    const float* __restrict__ mean, const float* __restrict__ rstd, f16* __restrict__ dx, int64_t lddx,
-    f16* __restrict__ dxd, int64_t lddxd, float* __restrict__ part, int M, int H, DropCtx dyd, DropCtx outd, const int32_t* __restrict__ row_map) {
+// block-level reduction of the 8 waves' column sums through LDS, one partial row [2H] per block.  sums(k, 0 / 1) = the lane's dgamma / dbeta
+// sums of piece k as a value: handed over as references to the kernel's arrays they pass a generic pointer, and the H = 768 kernels
+// allocate up to 10 more VGPRs.
+template <int NP, bool EXACT, typename Sums>
+DEVFN void lnb_block_partials(Sums sums, float* __restrict__ part, int H) {
+    extern __shared__ float lnb_sh[];      // [LNB_WAVES][2H]
     const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * LNB_WAVES + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * LNB_WAVES;
-    const float invH = 1.f / (float)H;
-    float g[NP][4], dg[NP][4], db[NP][4];
+    float* sg = lnb_sh + (threadIdx.x >> 6) * 2 * H;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
         const int c = 256 * k + 4 * lane;
-        f16x4 gv = (f16x4){0, 0, 0, 0};
-        if (c < H) gv = ld4(gamma + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { g[k][e] = (float)gv[e]; dg[k][e] = 0.f; db[k][e] = 0.f; }
-    }
-    // software pipeline: the raw vectors (and statistics) of the NEXT row are requested before the current row is
-    // reduced, so two rows of HBM traffic are in flight per wave
-    f16x4 xc[NP], dc[NP], xn[NP], dn[NP];
-    float mu_c = 0.f, rs_c = 0.f, mu_n = 0.f, rs_n = 0.f;
-    auto fetch = [&](int row, f16x4 (&X)[NP], f16x4 (&D)[NP], float& m_, float& r_) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int c = 256 * k + 4 * lane;
-            if (c < H) {
-                X[k] = ld4(x + (int64_t)row * ldx + c);
-                D[k] = ld4(dy + (int64_t)row * lddy + c);
-            }
-        }
-        m_ = mean[row];
-        r_ = rstd[row];
-    };
-    if (wave < M) fetch(wave, xc, dc, mu_c, rs_c);
-    for (int row = wave; row < M; row += nwaves) {
-        if (row + nwaves < M) fetch(row + nwaves, xn, dn, mu_n, rs_n);
-        const float mu = mu_c, rs = rs_c;
-        const uint64_t drow = ((dyd.thresh | outd.thresh) && row_map) ? (uint64_t)(uint32_t)row_map[row] : (uint64_t)row;     // packed rows: logical index
-        const uint32_t rk_dy = dyd.thresh ? drop_rowkey(dyd, drow) : 0u;
-        const uint32_t rk_out = outd.thresh ? drop_rowkey(outd, drow) : 0u;
-        float xh[NP][4], d[NP][4];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int c = 256 * k + 4 * lane;
-            if (c < H) {
-                const f16x4 xv = xc[k], dv = dc[k];
-                float m4[4] = {1.f, 1.f, 1.f, 1.f};
-                if (dyd.thresh) drop_mult4(dyd, rk_dy, (uint32_t)c, m4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float dd = (float)dv[e] * m4[e];
-                    xh[k][e] = ((float)xv[e] - mu) * rs;
-                    dg[k][e] += dd * xh[k][e];
-                    db[k][e] += dd;
-                    d[k][e] = dd * g[k][e];
-                    s1 += d[k][e];
-                    s2 += d[k][e] * xh[k][e];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { xh[k][e] = 0.f; d[k][e] = 0.f; }
-            }
-        }
-        s1 = wave_sum(s1) * invH;
-        s2 = wave_sum(s2) * invH;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int c = 256 * k + 4 * lane;
-            if (c < H) {
-                f16x4 o, od;
-                float m4[4] = {1.f, 1.f, 1.f, 1.f};
-                if (dxd) drop_mult4(outd, rk_out, (uint32_t)c, m4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float t = rs * (d[k][e] - s1 - xh[k][e] * s2);
-                    o[e] = (f16)t;
-                    od[e] = (f16)(t * m4[e]);
-                }
-                st4_out<VLP_SS_LN>(dx + (int64_t)row * lddx + c, o);
-                if (dxd) st4_out<VLP_SS_LN>(dxd + (int64_t)row * lddxd + c, od);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NP; ++k) { xc[k] = xn[k]; dc[k] = dn[k]; }
-        mu_c = mu_n;
-        rs_c = rs_n;
-    }
-    // block-level reduction of the 8 waves' column partials through LDS, one partial row per block
-    extern __shared__ float lnb_sh[];      // [LNB_WAVES][2H]
-    {
-        float* sg = lnb_sh + (threadIdx.x >> 6) * 2 * H;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int c = 256 * k + 4 * lane;
-            if (c < H) {
-                *reinterpret_cast<f32x4*>(sg + c) = (f32x4){dg[k][0], dg[k][1], dg[k][2], dg[k][3]};
-                *reinterpret_cast<f32x4*>(sg + H + c) = (f32x4){db[k][0], db[k][1], db[k][2], db[k][3]};
-            }
+        if (EXACT || c < H) {
+            *reinterpret_cast<f32x4*>(sg + c) = sums(k, 0);
+            *reinterpret_cast<f32x4*>(sg + H + c) = sums(k, 1);
         }
     }
     __syncthreads();
@@ -309,37 +218,47 @@ __global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? LNB_MINW : (NP == 4 ? 3 : 2)
     }
 }
 
-// Round 6: the SAME arithmetic for H == 256 NP (every LayerNorm of the model: 768) with a loop body the compiler can count.  In the kernel above
-// the next row's loads sit under lane-dependent (c < H) and row-dependent (row + nwaves < M, row_map != 0, dxd != 0) branches, so hipcc's waitcnt pass
-// cannot know how many requests are in flight at the join and puts `s_waitcnt vmcnt(0)` in front of the current row's arithmetic (seen in the ISA:
-// three of them per iteration): the "prefetch" was waited for in the iteration that issued it -- one row in flight per wave, not two.  Here every
-// iteration issues exactly the same loads (the next row is clamped to M - 1 instead of skipped; the optional operands are template switches), so the
-// waits are counted and a wave really keeps two rows of HBM traffic in flight.
-template <int NP, bool HAS_DXD, bool HAS_MAP>
-__global__ __launch_bounds__(LNB_THREADS, LNB_MINW) void layernorm_bwd_full_kernel(
+// EXACT: H == 256 NP at compile time (every LayerNorm of the model: 768), no column predicates; otherwise H <= 256 NP and a lane skips the
+// pieces at c >= H.  HAS_DXD: the dropped twin dx_drop = dx * mask(out_drop) is written too; HAS_MAP: packed rows, the dropout masks are
+// those of the logical row row_map[row].
+// Round 6: a loop body the compiler can count.  In the rounds 2 - 5 kernel the next row's loads sat under row-dependent (row + nwaves < M,
+// row_map != 0, dxd != 0) branches as well as the lane-dependent (c < H) one, so hipcc's waitcnt pass could not know how many requests are in
+// flight at the join and put `s_waitcnt vmcnt(0)` in front of the current row's arithmetic (seen in the ISA: three of them per iteration): the
+// "prefetch" was waited for in the iteration that issued it -- one row in flight per wave, not two.  Here every iteration issues exactly the
+// same loads (the next row is clamped to M - 1 instead of skipped; the optional operands are template switches), so with EXACT the waits are
+// counted and a wave really keeps two rows of HBM traffic in flight.
+template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP>
+__global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? 4 : (NP == 4 ? 3 : 2)) void layernorm_bwd_kernel(
     const f16* __restrict__ dy, int64_t lddy, const f16* __restrict__ x, int64_t ldx, const f16* __restrict__ gamma,
     const float* __restrict__ mean, const float* __restrict__ rstd, f16* __restrict__ dx, int64_t lddx,
-    f16* __restrict__ dxd, int64_t lddxd, float* __restrict__ part, int M, DropCtx dyd, DropCtx outd, const int32_t* __restrict__ row_map) {
-    constexpr int H = 256 * NP;
+    f16* __restrict__ dxd, int64_t lddxd, float* __restrict__ part, int M, int H_, DropCtx dyd, DropCtx outd, const int32_t* __restrict__ row_map) {
+    const int H = EXACT ? 256 * NP : H_;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * LNB_WAVES + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * LNB_WAVES;
-    constexpr float invH = 1.f / (float)H;
+    const float invH = 1.f / (float)H;
     float g[NP][4], dg[NP][4], db[NP][4];
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-        const f16x4 gv = ld4(gamma + 256 * k + 4 * lane);
+        const int c = 256 * k + 4 * lane;
+        f16x4 gv = (f16x4){0, 0, 0, 0};
+        if (EXACT || c < H) gv = ld4(gamma + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { g[k][e] = (float)gv[e]; dg[k][e] = 0.f; db[k][e] = 0.f; }
     }
+    // software pipeline: the raw vectors (statistics, logical row) of the NEXT row are requested before the current row is
+    // reduced, so two rows of HBM traffic are in flight per wave
     f16x4 xc[NP], dc[NP], xn[NP], dn[NP];
     float mu_c, rs_c, mu_n, rs_n;
     int map_c = 0, map_n = 0;
     auto fetch = [&](int row, f16x4 (&X)[NP], f16x4 (&D)[NP], float& m_, float& r_, int& mp_) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            X[k] = ld4(x + (int64_t)row * ldx + 256 * k + 4 * lane);
-            D[k] = ld4(dy + (int64_t)row * lddy + 256 * k + 4 * lane);
+            const int c = 256 * k + 4 * lane;
+            if (EXACT || c < H) {
+                X[k] = ld4(x + (int64_t)row * ldx + c);
+                D[k] = ld4(dy + (int64_t)row * lddy + c);
+            }
         }
         m_ = mean[row];
         r_ = rstd[row];
@@ -361,17 +280,22 @@ __global__ __launch_bounds__(LNB_THREADS, LNB_MINW) void layernorm_bwd_full_kern
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int c = 256 * k + 4 * lane;
-            float m4[4] = {1.f, 1.f, 1.f, 1.f};
-            if (dyd.thresh) drop_mult4(dyd, rk_dy, (uint32_t)c, m4);
+            if (EXACT || c < H) {
+                float m4[4] = {1.f, 1.f, 1.f, 1.f};
+                if (dyd.thresh) drop_mult4(dyd, rk_dy, (uint32_t)c, m4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float dd = (float)dc[k][e] * m4[e];
-                xh[k][e] = ((float)xc[k][e] - mu) * rs;
-                dg[k][e] += dd * xh[k][e];
-                db[k][e] += dd;
-                d[k][e] = dd * g[k][e];
-                s1 += d[k][e];
-                s2 += d[k][e] * xh[k][e];
+                for (int e = 0; e < 4; ++e) {
+                    const float dd = (float)dc[k][e] * m4[e];
+                    xh[k][e] = ((float)xc[k][e] - mu) * rs;
+                    dg[k][e] += dd * xh[k][e];
+                    db[k][e] += dd;
+                    d[k][e] = dd * g[k][e];
+                    s1 += d[k][e];
+                    s2 += d[k][e] * xh[k][e];
+                }
+            } else {       // (defined values in the pieces a lane skips: left undefined they cost the column-predicated kernels registers, NP = 8 spills)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { xh[k][e] = 0.f; d[k][e] = 0.f; }
             }
         }
         s1 = wave_sum(s1) * invH;
@@ -379,17 +303,19 @@ __global__ __launch_bounds__(LNB_THREADS, LNB_MINW) void layernorm_bwd_full_kern
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int c = 256 * k + 4 * lane;
-            f16x4 o, od;
-            float m4[4] = {1.f, 1.f, 1.f, 1.f};
-            if (HAS_DXD) drop_mult4(outd, rk_out, (uint32_t)c, m4);
+            if (EXACT || c < H) {
+                f16x4 o, od;
+                float m4[4] = {1.f, 1.f, 1.f, 1.f};
+                if (HAS_DXD) drop_mult4(outd, rk_out, (uint32_t)c, m4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float t = rs * (d[k][e] - s1 - xh[k][e] * s2);
-                o[e] = (f16)t;
-                od[e] = (f16)(t * m4[e]);
+                for (int e = 0; e < 4; ++e) {
+                    const float t = rs * (d[k][e] - s1 - xh[k][e] * s2);
+                    o[e] = (f16)t;
+                    od[e] = (f16)(t * m4[e]);
+                }
+                st4_out<VLP_SS_LN>(dx + (int64_t)row * lddx + c, o);
+                if (HAS_DXD) st4_out<VLP_SS_LN>(dxd + (int64_t)row * lddxd + c, od);
             }
-            st4_out<VLP_SS_LN>(dx + (int64_t)row * lddx + c, o);
-            if (HAS_DXD) st4_out<VLP_SS_LN>(dxd + (int64_t)row * lddxd + c, od);
         }
 #pragma unroll
         for (int k = 0; k < NP; ++k) { xc[k] = xn[k]; dc[k] = dn[k]; }
@@ -397,53 +323,47 @@ __global__ __launch_bounds__(LNB_THREADS, LNB_MINW) void layernorm_bwd_full_kern
         rs_c = rs_n;
         map_c = map_n;
     }
-    extern __shared__ float lnb_sh[];      // [LNB_WAVES][2H]
-    {
-        float* sg = lnb_sh + (threadIdx.x >> 6) * 2 * H;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int c = 256 * k + 4 * lane;
-            *reinterpret_cast<f32x4*>(sg + c) = (f32x4){dg[k][0], dg[k][1], dg[k][2], dg[k][3]};
-            *reinterpret_cast<f32x4*>(sg + H + c) = (f32x4){db[k][0], db[k][1], db[k][2], db[k][3]};
-        }
-    }
-    __syncthreads();
-    float* dst = part + (int64_t)blockIdx.x * 2 * H;
-    for (int i = threadIdx.x; i < 2 * H; i += LNB_THREADS) {
-        float t = 0.f;
-#pragma unroll
-        for (int w = 0; w < LNB_WAVES; ++w) t += lnb_sh[w * 2 * H + i];
-        dst[i] = t;
-    }
+    lnb_block_partials<NP, EXACT>([&](int k, int b) { return b ? (f32x4){db[k][0], db[k][1], db[k][2], db[k][3]} : (f32x4){dg[k][0], dg[k][1], dg[k][2], dg[k][3]}; },
+                                  part, H);
 }
 
-// out[0..H) = dgamma, out[H..2H) = dbeta from part[nparts][2H].  Block = 64 columns x 16 partial-groups.
-__global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __restrict__ part, int nparts, int H, f16* dgamma, f16* dbeta, int beta) {
+// Second stage of the backward and of colsum: dst(i) (+)= sum of column i over the nparts partial rows of width W.  Block = 64 columns x 16
+// partial-groups; a group adds its rows p = pg, pg + 16, .. in ascending order, then the 16 LDS words are added in ascending order:
+// every caller has this summation order (test_layernorm_bwd_deferred_batched_reduce compares two of them bit for bit).
+template <typename DstOf>
+DEVFN void reduce_partial_rows(const float* __restrict__ part, int nparts, int W, int beta, DstOf dst_of) {
     __shared__ float sh[16][64];
     const int cl = threadIdx.x & 63, pg = threadIdx.x >> 6;
     const int i = blockIdx.x * 64 + cl;
     float s = 0.f;
-    if (i < 2 * H)
-        for (int p = pg; p < nparts; p += 16) s += part[(int64_t)p * 2 * H + i];
+    if (i < W)
+        for (int p = pg; p < nparts; p += 16) s += part[(int64_t)p * W + i];
     sh[pg][cl] = s;
     __syncthreads();
-    if (pg == 0 && i < 2 * H) {
+    if (pg == 0 && i < W) {
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += sh[k][cl];
-        f16* dst = i < H ? dgamma + i : dbeta + (i - H);
+        f16* dst = dst_of(i);
         *dst = (f16)(beta ? (float)*dst + t : t);
     }
 }
 
+// out[0..H) = dgamma, out[H..2H) = dbeta from part[nparts][2H]
+__global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __restrict__ part, int nparts, int H, f16* dgamma, f16* dbeta, int beta) {
+    reduce_partial_rows(part, nparts, 2 * H, beta, [&](int i) { return i < H ? dgamma + i : dbeta + (i - H); });
+}
+
+// blockIdx.y = LayerNorm index: ln_bwd_reduce_kernel on slot y
+__global__ __launch_bounds__(1024) void ln_bwd_reduce_batched_kernel(const float* __restrict__ parts, int64_t slot_stride, f16* const* __restrict__ dst,
+                                                                     int nparts, int H, int beta) {
+    reduce_partial_rows(parts + (int64_t)blockIdx.y * slot_stride, nparts, 2 * H, beta,
+                        [&](int i) { return i < H ? dst[2 * blockIdx.y] + i : dst[2 * blockIdx.y + 1] + (i - H); });
+}
+
 // row-walking blocks of a backward launch (= partial rows in the workspace); VLP_LNB_BLOCKS lowers it for A/B runs
 static int lnb_blocks(int M) {
-    static int cap = 0;
-    if (!cap) {
-        const char* e = getenv("VLP_LNB_BLOCKS");
-        cap = e ? atoi(e) : LNB_BLOCKS;
-        if (cap < 1 || cap > LNB_BLOCKS) cap = LNB_BLOCKS;
-    }
+    static const int cap = env_blocks("VLP_LNB_BLOCKS", LNB_BLOCKS, LNB_BLOCKS);
     const int blocks = cdiv(M, LNB_WAVES);
     if (blocks <= cap) return blocks;
     // every wave the SAME number of rows: with the cap alone a wave walks M / (cap * 8) = 2.6 rows at M = 10 688 -- 61 % of the waves do
@@ -457,6 +377,23 @@ extern "C" int64_t vlp_layernorm_bwd_workspace_bytes(int32_t H) {
     return (int64_t)LNB_BLOCKS * 2 * H * (int64_t)sizeof(float);
 }
 
+template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP>
+static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s) {
+    const auto kernel = layernorm_bwd_kernel<NP, EXACT, HAS_DXD, HAS_MAP>;
+    VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 256 * NP * 4));
+    const size_t lnb_smem = (size_t)LNB_WAVES * 2 * a->H * sizeof(float);   // <= 128 KiB at H = 2048
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x, a->ldx, (const f16*)a->gamma,
+                       a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, (float*)a->workspace, a->M, a->H, dyd, outd, a->row_map);
+}
+template <int NP, bool EXACT>
+static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s) {
+    const bool hd = a->dx_drop != nullptr, hm = a->row_map != nullptr && (dyd.thresh || outd.thresh);
+    if (hd && hm) launch_ln_bwd<NP, EXACT, true, true>(a, blocks, dyd, outd, s);
+    else if (hd) launch_ln_bwd<NP, EXACT, true, false>(a, blocks, dyd, outd, s);
+    else if (hm) launch_ln_bwd<NP, EXACT, false, true>(a, blocks, dyd, outd, s);
+    else launch_ln_bwd<NP, EXACT, false, false>(a, blocks, dyd, outd, s);
+}
+
 extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) {
     VLP_CHECK_ARG(a && a->dy && a->x && a->gamma && a->mean && a->rstd && a->dx && a->dgamma && a->dbeta, "vlp_layernorm_bwd: null operand");
     VLP_ENTER(a->dy, "vlp_layernorm_bwd");
@@ -466,65 +403,20 @@ extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) 
     if (a->dx_drop) VLP_CHECK_ARG(a->lddxd % 8 == 0 && (uintptr_t)a->dx_drop % 16 == 0 && a->out_drop_p > 0.f, "vlp_layernorm_bwd: dx_drop needs out_drop_p > 0");
     const int64_t need = vlp_layernorm_bwd_workspace_bytes(a->H);
     if (!a->workspace || a->workspace_bytes < need) return vlp_set_error(VLP_ERR_WORKSPACE, "vlp_layernorm_bwd: workspace %lld < %lld", (long long)a->workspace_bytes, (long long)need);
-    DropCtx dyd = make_drop(a->dy_drop_p, a->dy_seed, a->dy_stream);
-    DropCtx outd = make_drop(a->out_drop_p, a->out_seed, a->out_stream);
+    const DropCtx dyd = make_drop(a->dy_drop_p, a->dy_seed, a->dy_stream);
+    const DropCtx outd = make_drop(a->out_drop_p, a->out_seed, a->out_stream);
     const int blocks = lnb_blocks(a->M);
     hipStream_t s = (hipStream_t)stream;
-    float* part = (float*)a->workspace;
-    const size_t lnb_smem = (size_t)LNB_WAVES * 2 * a->H * sizeof(float);   // <= 128 KiB at H = 2048
-    VLP_ONCE_PER_DEVICE({
-        (void)hipFuncSetAttribute((const void*)layernorm_bwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 768 * 4);
-        (void)hipFuncSetAttribute((const void*)layernorm_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 1024 * 4);
-        (void)hipFuncSetAttribute((const void*)layernorm_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 2048 * 4);
-    });
-    // H = 768: the countable-loop form (VLP_LNB_FULL=0: the general kernel, A/B runs)
-    static const int full_on = [] { const char* e = getenv("VLP_LNB_FULL"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (full_on && a->H == 768) {
-        const bool hd = a->dx_drop != nullptr, hm = a->row_map != nullptr && (dyd.thresh || outd.thresh);
-#define LAUNCH_LNB_FULL(HD_, HM_)                                                                                                                       \
-    do {                                                                                                                                                \
-        VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)layernorm_bwd_full_kernel<3, HD_, HM_>, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 768 * 4)); \
-        hipLaunchKernelGGL((layernorm_bwd_full_kernel<3, HD_, HM_>), dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x,       \
-                           a->ldx, (const f16*)a->gamma, a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, part, a->M, dyd, outd, a->row_map);          \
-    } while (0)
-        if (hd && hm) LAUNCH_LNB_FULL(true, true); else if (hd) LAUNCH_LNB_FULL(true, false); else if (hm) LAUNCH_LNB_FULL(false, true); else LAUNCH_LNB_FULL(false, false);
-#undef LAUNCH_LNB_FULL
-    } else if (a->H <= 768)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<3>, dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x, a->ldx,
-                           (const f16*)a->gamma, a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, part, a->M, a->H, dyd, outd, a->row_map);
-    else if (a->H <= 1024)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<4>, dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x, a->ldx,
-                           (const f16*)a->gamma, a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, part, a->M, a->H, dyd, outd, a->row_map);
-    else
-        hipLaunchKernelGGL(layernorm_bwd_kernel<8>, dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x, a->ldx,
-                           (const f16*)a->gamma, a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, part, a->M, a->H, dyd, outd, a->row_map);
+    if (a->H == 768) launch_ln_bwd<3, true>(a, blocks, dyd, outd, s);
+    else if (a->H <= 768) launch_ln_bwd<3, false>(a, blocks, dyd, outd, s);
+    else if (a->H <= 1024) launch_ln_bwd<4, false>(a, blocks, dyd, outd, s);
+    else launch_ln_bwd<8, false>(a, blocks, dyd, outd, s);
     VLP_CHECK_LAUNCH("vlp_layernorm_bwd");
     if (a->defer_reduce) return VLP_OK;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * a->H, 64)), dim3(1024), 0, s, part, blocks, a->H, (f16*)a->dgamma,
+    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * a->H, 64)), dim3(1024), 0, s, (const float*)a->workspace, blocks, a->H, (f16*)a->dgamma,
                        (f16*)a->dbeta, a->beta);
     VLP_CHECK_LAUNCH("vlp_layernorm_bwd_reduce");
     return VLP_OK;
-}
-
-// blockIdx.y = LayerNorm index: same arithmetic (and summation order) as ln_bwd_reduce_kernel on slot y
-__global__ __launch_bounds__(1024) void ln_bwd_reduce_batched_kernel(const float* __restrict__ parts, int64_t slot_stride, f16* const* __restrict__ dst,
-                                                                     int nparts, int H, int beta) {
-    __shared__ float sh[16][64];
-    const float* part = parts + (int64_t)blockIdx.y * slot_stride;
-    const int cl = threadIdx.x & 63, pg = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + cl;
-    float s = 0.f;
-    if (i < 2 * H)
-        for (int p = pg; p < nparts; p += 16) s += part[(int64_t)p * 2 * H + i];
-    sh[pg][cl] = s;
-    __syncthreads();
-    if (pg == 0 && i < 2 * H) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sh[k][cl];
-        f16* d = i < H ? dst[2 * blockIdx.y] + i : dst[2 * blockIdx.y + 1] + (i - H);
-        *d = (f16)(beta ? (float)*d + t : t);
-    }
 }
 
 extern "C" int vlp_layernorm_bwd_reduce_batched(const float* parts, const void* const* dst, int32_t count, int32_t M, int32_t H, int32_t beta, void* stream) {
@@ -570,20 +462,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const f16* __restrict__ A, 
     if (col < N) part[(int64_t)blockIdx.y * N + col] = s;
 }
 __global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float* __restrict__ part, int nparts, int N, f16* out, int beta) {
-    __shared__ float sh[16][64];
-    const int cl = threadIdx.x & 63, pg = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + cl;
-    float s = 0.f;
-    if (i < N)
-        for (int p = pg; p < nparts; p += 16) s += part[(int64_t)p * N + i];
-    sh[pg][cl] = s;
-    __syncthreads();
-    if (pg == 0 && i < N) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += sh[k][cl];
-        out[i] = (f16)(beta ? (float)out[i] + t : t);
-    }
+    reduce_partial_rows(part, nparts, N, beta, [&](int i) { return out + i; });
 }
 
 extern "C" int64_t vlp_colsum_workspace_bytes(int32_t M, int32_t N) {
