@@ -37,6 +37,8 @@ extern "C" {
 /* + vlp_cider_d / vlp_cider_d_workspace_bytes (the SCST reward on the device): purely additive as well. */
 /* + vlp_cider_d_df / vlp_cider_d_df_workspace_bytes (the same reward with document frequencies from a resident table): purely additive as
  * well. */
+/* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
+ * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -107,6 +109,22 @@ int vlp_gemm_nt(const vlp_gemm_nt_args* a, void* stream);
  * epilogue, or with operands beyond 32-bit offsets, and a persistent variant outside its epilogues / shapes, run on the rings 27 / 29);
  * -1 before the first call. */
 int vlp_gemm_nt_resolved_variant(void);
+/* Listed-row launches (the backward of the last encoder layer of a masked-LM step: only the masked rows carry gradient).  `live` is a device
+ * int32 list of row indices, ascending and without duplicates, padded with -1 (vlp_live_rows_build): entry m >= 0 names the row of the big
+ * [rows, *] buffers that compact row m stands for; a pad entry contributes nothing and its output row is not written. */
+enum { VLP_ROWS_X = 1,    /* vlp_gemm_nt_rows: X row m is read at live[m];  vlp_gemm_tn_grouped_rows: A row m is read at live[m];
+                             vlp_layernorm_bwd_rows: dy row m is read at live[m] */
+       VLP_ROWS_MUL = 2,  /* mul_src row m is read at live[m] */
+       VLP_ROWS_RES = 4,  /* residual row m is read at live[m] */
+       VLP_ROWS_Y = 8     /* vlp_gemm_nt_rows: Y row m is written at live[m];  vlp_layernorm_bwd_rows: dx row m is written at live[m] */ };
+/* live[0..n) = the distinct rows base(b) + clamp(pos[b, j]) of pos [B, P] (base / clamp as in vlp_gather_rows) in ascending order, the rest
+ * of live[0..B*P) = -1; *count = n.  One workgroup; B*P <= 12288. */
+int vlp_live_rows_build(const int64_t* pos, int32_t B, int32_t P, int32_t L, const int32_t* row_off, int32_t* live, int32_t* count, void* stream);
+/* vlp_gemm_nt over the listed rows: a->M = entries of `live`; the operands named by `flags` (VLP_ROWS_*) are addressed at row live[m], the
+ * others at row m.  Epilogues: bias, VLP_MUL_PLAIN / VLP_MUL_RELU_MASK, dropout (drawn at the logical row: a->row_map[live[m]], or live[m]),
+ * residual.  One workgroup walks the whole K of its 128x128 tile in ascending order (the ring variant 17 of vlp_gemm_nt; no split-K), so a
+ * listed output row has the bits that variant gives the same row in an unlisted launch. */
+int vlp_gemm_nt_rows(const vlp_gemm_nt_args* a, const int32_t* live, int32_t flags, void* stream);
 /* Split-K form for skinny problems (incremental decoding, M = 128..640 rows: only N/128 output tiles): the k range is cut into `splits`
  * slices computed by separate workgroups into an fp32 workspace of vlp_gemm_nt_splitk_workspace_bytes(M, N, splits) bytes; a second
  * kernel sums the slices in a fixed order (deterministic) and applies the same fused epilogue.  `variant` is ignored. */
@@ -147,6 +165,10 @@ int vlp_gemm_tn(const vlp_gemm_tn_args* a, void* stream);
  * through the workspace (flags reset by a hipMemsetAsync ahead of the launch); without a workspace the launch runs in the plain form. */
 int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, void* stream);
 int64_t vlp_gemm_tn_grouped_workspace_bytes(int32_t tiles);
+/* The same launch with a row list per problem: live[i] (host array of `count` device pointers; NULL = problem i as in vlp_gemm_tn_grouped)
+ * lists the contraction rows of problem i, M = entries of the list.  B row m is read at live[i][m]; A row m at live[i][m] when flags[i]
+ * has VLP_ROWS_X, else at row m (compact dY).  Pad entries (-1) add nothing.  Rows are summed in list order. */
+int vlp_gemm_tn_grouped_rows(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* flags, int32_t count, void* stream);
 
 /* out[n] (+)= sum_m A[m,n]  -- bias gradients (autograd SumBackward of the broadcast bias add). */
 typedef struct {
@@ -265,6 +287,11 @@ typedef struct {
 } vlp_layernorm_bwd_args;
 int64_t vlp_layernorm_bwd_workspace_bytes(int32_t H);
 int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream);
+/* vlp_layernorm_bwd over the listed rows: a->M = entries of `live`; x / mean / rstd are read at row live[m], dy at live[m] with VLP_ROWS_X
+ * (else at row m), dx is written at row live[m] with VLP_ROWS_Y (else at row m), dx_drop at row m; both dropout masks are drawn at the
+ * logical row (a->row_map[live[m]], or live[m]).  The launch leaves as many partial rows in the workspace as vlp_layernorm_bwd with
+ * M = part_M does (exact zeros in those that saw no row), so a deferred vlp_layernorm_bwd_reduce_batched over M = part_M stays complete. */
+int vlp_layernorm_bwd_rows(const vlp_layernorm_bwd_args* a, const int32_t* live, int32_t flags, int32_t part_M, void* stream);
 /* Second stage of `count` deferred vlp_layernorm_bwd calls in ONE launch (the 25 LayerNorms of a 12-layer step otherwise cost 25
  * tiny reduce launches): slot i of `parts` (stride = vlp_layernorm_bwd_workspace_bytes(H) / 4 floats) holds the partials of
  * LayerNorm i (all with the same M, H); dst[2*i] / dst[2*i+1] (device array of pointers) are its dgamma / dbeta ([H] fp16). */

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("VLP_HIP_LIB") or os.path.join(_HERE, "libvlp_hip.so")
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_TANH, ACT_GELU_SAVE_GRAD = 0, 1, 2, 3, 4
 MUL_NONE, MUL_GELU_GRAD, MUL_RELU_MASK, MUL_PLAIN = 0, 1, 2, 3
+ROWS_X, ROWS_MUL, ROWS_RES, ROWS_Y = 1, 2, 4, 8      # VLP_ROWS_*: operands of a listed-row launch addressed at row live[m]
 
 vp, i64, i32, f32, u64, u32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_uint64, C.c_uint32
 
@@ -190,12 +191,14 @@ SYMBOLS = {
     "vlp_lab_build": (C.c_int, []),
     "vlp_debug_device_lookup_stats": (None, [vp, vp]),
     "vlp_gemm_nt": (C.c_int, [C.POINTER(GemmNtArgs), vp]),
+    "vlp_gemm_nt_rows": (C.c_int, [C.POINTER(GemmNtArgs), vp, i32, vp]),
     "vlp_gemm_nt_resolved_variant": (C.c_int, []),
     "vlp_gemm_nt_splitk_workspace_bytes": (C.c_int64, [i32, i32, i32]),
     "vlp_gemm_nt_splitk": (C.c_int, [C.POINTER(GemmNtArgs), i32, vp, i64, vp]),
     "vlp_gemm_tn_workspace_bytes": (i64, [i32, i32, i32]),
     "vlp_gemm_tn": (C.c_int, [C.POINTER(GemmTnArgs), vp]),
     "vlp_gemm_tn_grouped": (C.c_int, [C.POINTER(GemmTnArgs), i32, vp]),
+    "vlp_gemm_tn_grouped_rows": (C.c_int, [C.POINTER(GemmTnArgs), C.POINTER(vp), C.POINTER(i32), i32, vp]),
     "vlp_gemm_tn_grouped_workspace_bytes": (i64, [i32]),
     "vlp_colsum_workspace_bytes": (i64, [i32, i32]),
     "vlp_colsum": (C.c_int, [C.POINTER(ColsumArgs), vp]),
@@ -221,6 +224,7 @@ SYMBOLS = {
     "vlp_layernorm_fwd": (C.c_int, [C.POINTER(LayerNormFwdArgs), vp]),
     "vlp_layernorm_bwd_workspace_bytes": (i64, [i32]),
     "vlp_layernorm_bwd": (C.c_int, [C.POINTER(LayerNormBwdArgs), vp]),
+    "vlp_layernorm_bwd_rows": (C.c_int, [C.POINTER(LayerNormBwdArgs), vp, i32, i32, vp]),
     "vlp_layernorm_bwd_reduce_batched": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "vlp_embed_fwd": (C.c_int, [C.POINTER(EmbedFwdArgs), vp]),
     "vlp_embed_bwd": (C.c_int, [C.POINTER(EmbedBwdArgs), vp]),
@@ -236,6 +240,7 @@ SYMBOLS = {
     "vlp_transpose_batched": (C.c_int, [vp, vp, i32, i32, vp]),
     "vlp_gather_rows": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
     "vlp_scatter_add_rows": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
+    "vlp_live_rows_build": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
     "vlp_rowmap_build": (C.c_int, [vp, i32, i32, vp, vp]),
     "vlp_rows_unpack": (C.c_int, [vp, i64, vp, i32, vp, i64, i32, vp]),
     "vlp_rows_pack": (C.c_int, [vp, i64, vp, i32, vp, i64, i32, vp]),
@@ -388,6 +393,16 @@ def gemm_nt(x, w, y, M, N, K, ldx=None, ldw=None, ldy=None, bias=None, residual=
     _check(load().vlp_gemm_nt(C.byref(a), stream_ptr()))
 
 
+def gemm_nt_rows(x, w, y, live, flags, M, N, K, ldx=None, ldw=None, ldy=None, bias=None, residual=None, ldr=None, mul_src=None, ldm=None,
+                 mul_mode=MUL_NONE, alpha=1.0, dropout_p=0.0, seed=0, rng_stream=0, variant=0, row_map=None):
+    """gemm_nt over the M entries of the device row list `live` (int32, -1 = pad): the operands named by `flags` (ROWS_*) are addressed at
+    row live[m], the others at row m."""
+    _req_cuda(x, w, y, live, row_map)
+    a = _gemm_nt_args(x, w, y, M, N, K, ldx, ldw, ldy, bias, residual, ldr, None, None, mul_src, ldm, ACT_NONE, mul_mode, alpha, dropout_p, seed,
+                      rng_stream, variant, row_map)
+    _check(load().vlp_gemm_nt_rows(C.byref(a), ptr(live), flags, stream_ptr()))
+
+
 def gemm_nt_resolved_variant():
     """The variant this thread's last gemm_nt actually launched (after the launcher's fallbacks)."""
     return int(load().vlp_gemm_nt_resolved_variant())
@@ -434,6 +449,21 @@ def gemm_tn_grouped(problems, workspace=None):
         arr[i] = GemmTnArgs(ptr(a_), a_.stride(0), ptr(b_), b_.stride(0), ptr(c_), c_.stride(0), M, N, K, beta, ptr(w),
                             _nbytes(w), 0, 0, ptr(bias_out))
     _check(load().vlp_gemm_tn_grouped(arr, len(problems), stream_ptr()))
+
+
+def gemm_tn_grouped_rows(problems):
+    """problems: list of tuples (a, b, c, M, N, K, beta, bias_out, live, flags): gemm_tn_grouped with a row list per problem (live = None:
+    the problem as in gemm_tn_grouped); b is read at row live[m], a at live[m] with ROWS_X, else at row m."""
+    n = len(problems)
+    arr = (GemmTnArgs * n)()
+    lives = (vp * n)()
+    flags = (i32 * n)()
+    for i, (a_, b_, c_, M, N, K, beta, bias_out, live, fl) in enumerate(problems):
+        _req_cuda(a_, b_, c_, bias_out, live)
+        arr[i] = GemmTnArgs(ptr(a_), a_.stride(0), ptr(b_), b_.stride(0), ptr(c_), c_.stride(0), M, N, K, beta, None, 0, 0, 0, ptr(bias_out))
+        lives[i] = live.data_ptr() if live is not None else None
+        flags[i] = fl
+    _check(load().vlp_gemm_tn_grouped_rows(arr, lives, flags, n, stream_ptr()))
 
 
 def colsum_workspace_bytes(M, N):
@@ -605,6 +635,18 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, M, H, workspace, 
                          dy_drop[0], dy_drop[1], dy_drop[2], out_drop[0], out_drop[1], out_drop[2],
                          ptr(workspace), _nbytes(workspace), 1 if defer_reduce else 0, ptr(row_map))
     _check(load().vlp_layernorm_bwd(C.byref(a), stream_ptr()))
+
+
+def layernorm_bwd_rows(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, live, flags, M, H, workspace, part_M, beta=0, dx_drop=None,
+                       out_drop=(0.0, 0, 0), defer_reduce=False, row_map=None):
+    """layernorm_bwd over the M entries of the device row list `live`: x / mean / rstd at row live[m], dy with ROWS_X, dx with ROWS_Y; the
+    workspace gets the partial rows of an unlisted launch over part_M rows."""
+    _req_cuda(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, row_map, live)
+    a = LayerNormBwdArgs(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), dx.stride(0),
+                         ptr(dx_drop), dx_drop.stride(0) if dx_drop is not None else 0, ptr(dgamma), ptr(dbeta), M, H, beta,
+                         0.0, 0, 0, out_drop[0], out_drop[1], out_drop[2],
+                         ptr(workspace), _nbytes(workspace), 1 if defer_reduce else 0, ptr(row_map))
+    _check(load().vlp_layernorm_bwd_rows(C.byref(a), ptr(live), flags, part_M, stream_ptr()))
 
 
 def layernorm_bwd_reduce_batched(parts, dst_table, count, M, H, beta=0):
@@ -801,6 +843,12 @@ def gather_rows(src, lds, pos, out, ldo, B, P, L, H, row_off=None):
 def scatter_add_rows(src, lds, pos, dst, ldd, B, P, L, H, row_off=None):
     _req_cuda(src, pos, dst, row_off)
     _check(load().vlp_scatter_add_rows(ptr(src), lds, ptr(pos), ptr(dst), ldd, B, P, L, H, ptr(row_off), stream_ptr()))
+
+
+def live_rows_build(pos, B, P, L, live, count, row_off=None):
+    """live[0..n) = the distinct rows scatter_add_rows(pos) adds to, ascending; live[n..B*P) = -1; count[0] = n (device int32)."""
+    _req_cuda(pos, live, count, row_off)
+    _check(load().vlp_live_rows_build(ptr(pos), B, P, L, ptr(row_off), ptr(live), ptr(count), stream_ptr()))
 
 
 def rowmap_build(row_off, B, L, row_map):

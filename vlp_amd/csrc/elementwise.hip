@@ -484,6 +484,51 @@ extern "C" int vlp_scatter_add_rows(const void* src, int64_t lds, const int64_t*
     return VLP_OK;
 }
 
+// The rows scatter_add_rows_kernel adds to, once each and in ascending order: entry t is kept when no earlier entry names the same row, and its
+// place in the list is the number of kept entries with a smaller row (n^2 / 256 compares per thread; n = B * P is a few hundred).  One workgroup.
+__global__ __launch_bounds__(256) void live_rows_build_kernel(const int64_t* __restrict__ pos, int B, int P, int L, const int32_t* __restrict__ row_off,
+                                                              int32_t* __restrict__ live, int32_t* __restrict__ count) {
+    extern __shared__ int32_t lrb_rows[];      // [n] rows, then [n] keep flags
+    __shared__ int lrb_count;
+    const int n = B * P;
+    int32_t* keep = lrb_rows + n;
+    if (threadIdx.x == 0) lrb_count = 0;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        int nb;
+        const int64_t base = sample_base(row_off, t / P, L, nb);
+        int64_t ps = pos[t];
+        ps = ps < 0 ? 0 : (ps >= nb ? nb - 1 : ps);
+        lrb_rows[t] = (int32_t)(base + ps);
+        live[t] = -1;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        const int32_t r = lrb_rows[t];
+        int first = 1;
+        for (int j = 0; j < t; ++j) first &= (lrb_rows[j] != r);
+        keep[t] = first;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        if (!keep[t]) continue;
+        const int32_t r = lrb_rows[t];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += (keep[j] && lrb_rows[j] < r) ? 1 : 0;
+        live[rank] = r;          // (ranks of kept entries are distinct and < n: after the -1 fill above, ordered by the barrier)
+        atomicAdd(&lrb_count, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && count) *count = lrb_count;
+}
+extern "C" int vlp_live_rows_build(const int64_t* pos, int32_t B, int32_t P, int32_t L, const int32_t* row_off, int32_t* live, int32_t* count, void* stream) {
+    VLP_CHECK_ARG(pos && live && B > 0 && P > 0 && L > 0 && (int64_t)B * P <= 12288, "vlp_live_rows_build: bad args (B * P <= 12288)");
+    VLP_ENTER(pos, "vlp_live_rows_build");
+    VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)live_rows_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 12288 * 4));
+    hipLaunchKernelGGL(live_rows_build_kernel, dim3(1), dim3(256), (size_t)2 * B * P * sizeof(int32_t), (hipStream_t)stream, pos, B, P, L, row_off, live, count);
+    VLP_CHECK_LAUNCH("vlp_live_rows_build");
+    return VLP_OK;
+}
+
 __global__ void vqa_mul_fwd_kernel(const f16* h, f16* out, int B, int L, int Nv, int H, const int32_t* row_off) {
     const int64_t total = (int64_t)B * H;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {

@@ -49,8 +49,11 @@ DEVFN int swz_w(int r) { return (((r >> 4) & 3) << 1) | ((r >> 1) & 1); }
 //      times mulsrc, nothing else; N % 16 == 0): the lane's eight multiplier vectors are requested TOGETHER before the first one is used.  In the
 //      shared epilogue each 8-wide vector sits behind its own run-time branches -- load, full vmcnt wait, multiply, store, eight times in a row per
 //      lane: the stored-derivative multiply cost 14 us on a 59 us GEMM (10 688 x 768 x 3072).  Same arithmetic, same bits.
-template <int VARIANT, int BM_T, int BN_T, bool SG, int NSR = 0, int EPI = 0>
-__global__ __launch_bounds__((BM_T / 64) * (BN_T / 64) * 64, (VARIANT == 3 ? (BN_T == 256 ? 4 : BM_T / 128) : ((VARIANT == 2 || BN_T == 256) ? 4 : 2))) void gemm_nt_kernel(GemmNtParams p) {
+// ROWS: listed-row launch (vlp_gemm_nt_rows, gemm_nt_rows_kernel below): live[m] is the row of the operands chosen by live_flags (VLP_ROWS_*),
+//       < 0 skips output row m.  The k loop and the epilogue arithmetic are the ROWS = false ones: an output row has the bits the same variant
+//       gives it in an unlisted launch.  (The list travels beside the parameter block, not in it: every other NT kernel keeps its arguments.)
+template <int VARIANT, int BM_T, int BN_T, bool SG, int NSR, int EPI, bool ROWS>
+DEVFN void gemm_nt_body(const GemmNtParams& p, const int32_t* __restrict__ live, int live_flags) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     f16* smem = reinterpret_cast<f16*>(smem_raw);
     constexpr int WN_ = BN_T / 64;        // waves along n
@@ -84,7 +87,8 @@ __global__ __launch_bounds__((BM_T / 64) * (BN_T / 64) * 64, (VARIANT == 3 ? (BN
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
         const int r = srow + RPP * i;
-        const int mr = min(m0 + r, p.M - 1);
+        int mr = min(m0 + r, p.M - 1);
+        if (ROWS && (live_flags & VLP_ROWS_X)) mr = max(live[mr], 0);      // (a pad entry stages row 0: its output row is never written)
         xsrc[i] = p.X + (int64_t)mr * p.ldx + (sx ^ swz_x(r)) * 8;     // logical chunk held at physical slot sx of row r
         lds_off[i] = r * BK + sx * 8;
     }
@@ -349,6 +353,22 @@ __global__ __launch_bounds__((BM_T / 64) * (BN_T / 64) * 64, (VARIANT == 3 ? (BN
     for (int tm = 0; tm < 4; ++tm) {
         const int m = m0 + wm * 64 + 16 * tm + li;
         if (m >= p.M) continue;
+        if constexpr (ROWS) {
+            const int lm = live[m];
+            if (lm < 0) continue;
+            // dropout element = (logical row of live[m], col n): the mask the unlisted launch draws for that row
+            const uint32_t rkey = p.drop.thresh ? drop_rowkey(p.drop, p.row_map ? (uint64_t)(uint32_t)p.row_map[lm] : (uint64_t)lm) : 0u;
+            float v[16];
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[tn * 4 + r] = acc[tm][tn][r] * p.alpha + bias_v[tn * 4 + r];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                nt_epilogue8_rows<SG>(p, (live_flags & VLP_ROWS_Y) ? lm : m, (live_flags & VLP_ROWS_MUL) ? lm : m, (live_flags & VLP_ROWS_RES) ? lm : m,
+                                      ncol0 + 8 * h, v + 8 * h, rkey, true);
+            continue;
+        }
         const uint32_t rkey = p.drop.thresh ? drop_rowkey(p.drop, nt_drop_row(p, m)) : 0u;   // dropout element = (row m, col n)
         float v[16];
 #pragma unroll
@@ -364,6 +384,15 @@ __global__ __launch_bounds__((BM_T / 64) * (BN_T / 64) * 64, (VARIANT == 3 ? (BN
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     NT_TRACE(3);
 #endif
+}
+
+template <int VARIANT, int BM_T, int BN_T, bool SG, int NSR = 0, int EPI = 0>
+__global__ __launch_bounds__((BM_T / 64) * (BN_T / 64) * 64, (VARIANT == 3 ? (BN_T == 256 ? 4 : BM_T / 128) : ((VARIANT == 2 || BN_T == 256) ? 4 : 2))) void gemm_nt_kernel(GemmNtParams p) {
+    gemm_nt_body<VARIANT, BM_T, BN_T, SG, NSR, EPI, false>(p, nullptr, 0);
+}
+// the 128x128 4-stage ring (variant 17) over a row list
+__global__ __launch_bounds__(256, 1) void gemm_nt_rows_kernel(GemmNtParams p, const int32_t* __restrict__ live, int live_flags) {
+    gemm_nt_body<3, 128, 128, false, 0, 0, true>(p, live, live_flags);
 }
 
 int vlp_gemm_nt_fill_params(const vlp_gemm_nt_args* a, GemmNtParams& p) {
@@ -509,6 +538,28 @@ extern "C" int vlp_gemm_nt(const vlp_gemm_nt_args* a, void* stream) {
 #undef LAUNCH_NT
 #undef LAUNCH_NT_
     VLP_CHECK_LAUNCH("vlp_gemm_nt");
+    return VLP_OK;
+}
+
+// Listed-row form: M = entries of `live`; the operands named by `flags` are addressed at row live[m], the others at row m (compact), and an
+// entry < 0 is a pad: its output row is not written.  Always the 128x128 4-stage ring (variant 17; + 8 of a->variant is honoured): one
+// workgroup walks the whole K of its tile in ascending order, as every variant of vlp_gemm_nt does -- no split-K.
+extern "C" int vlp_gemm_nt_rows(const vlp_gemm_nt_args* a, const int32_t* live, int32_t flags, void* stream) {
+    VLP_ENTER(a ? a->X : nullptr, "vlp_gemm_nt_rows");
+    GemmNtParams p;
+    const int frc = vlp_gemm_nt_fill_params(a, p);
+    if (frc != VLP_OK) return frc;
+    VLP_CHECK_ARG(live != nullptr, "vlp_gemm_nt_rows: null row list");
+    VLP_CHECK_ARG((flags & ~(VLP_ROWS_X | VLP_ROWS_MUL | VLP_ROWS_RES | VLP_ROWS_Y)) == 0, "vlp_gemm_nt_rows: bad flags %d", flags);
+    VLP_CHECK_ARG(!a->preact && nt_epilogue_is_light(p) && a->act != VLP_ACT_GELU_SAVE_GRAD,
+                  "vlp_gemm_nt_rows: the listed-row form carries the dgrad epilogues (bias, stored multiplier, dropout, residual) only");
+    p.xcd_remap = (a->variant & 8) ? 1 : 0;
+    t_last_variant = 17 | (a->variant & 8);
+    const size_t smem = (size_t)4 * (128 + 128) * BK * sizeof(f16);
+    VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)gemm_nt_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    p.tiles_n = cdiv(a->N, 128);
+    hipLaunchKernelGGL(gemm_nt_rows_kernel, dim3(cdiv(a->M, 128) * p.tiles_n), dim3(256), smem, (hipStream_t)stream, p, live, (int)flags);
+    VLP_CHECK_LAUNCH("vlp_gemm_nt_rows");
     return VLP_OK;
 }
 

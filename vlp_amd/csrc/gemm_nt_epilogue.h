@@ -20,8 +20,9 @@ DEVFN void st8_pol(const GemmNtParams& p, f16* dst, f16x8 v) {      // store cac
 static inline bool nt_epilogue_is_light(const GemmNtParams& p) {
     return (p.act == VLP_ACT_NONE || p.act == VLP_ACT_RELU) && p.mulmode != VLP_MUL_GELU_GRAD;
 }
+// m = row of Y / preact, m_mul / m_res = rows of mulsrc / residual (a listed-row launch reads them at live[m]; everywhere else all three are m)
 template <bool SG = false, bool LIGHT = false>
-DEVFN void nt_epilogue8(const GemmNtParams& p, int m, int nc, float* vv, uint32_t rkey, bool bias_done = false) {
+DEVFN void nt_epilogue8_rows(const GemmNtParams& p, int m, int m_mul, int m_res, int nc, float* vv, uint32_t rkey, bool bias_done) {
     if (nc >= p.N) return;
     if (p.bias && !bias_done) {
         if (nc + 8 <= p.N) {
@@ -72,7 +73,7 @@ DEVFN void nt_epilogue8(const GemmNtParams& p, int m, int nc, float* vv, uint32_
         }
     }
     if (p.mulmode != VLP_MUL_NONE) {
-        const f16x8 s = ld8(p.mulsrc + (int64_t)m * p.ldm + nc);
+        const f16x8 s = ld8(p.mulsrc + (int64_t)m_mul * p.ldm + nc);
         if (!LIGHT && p.mulmode == VLP_MUL_GELU_GRAD) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) vv[j] *= gelu_grad_f((float)s[j]);
@@ -88,7 +89,7 @@ DEVFN void nt_epilogue8(const GemmNtParams& p, int m, int nc, float* vv, uint32_
         drop_mult8(p.drop, rkey, (uint32_t)nc, vv);
     }
     if (p.residual) {
-        const f16x8 r = ld8(p.residual + (int64_t)m * p.ldr + nc);
+        const f16x8 r = ld8(p.residual + (int64_t)m_res * p.ldr + nc);
 #pragma unroll
         for (int j = 0; j < 8; ++j) vv[j] += (float)r[j];
     }
@@ -96,4 +97,8 @@ DEVFN void nt_epilogue8(const GemmNtParams& p, int m, int nc, float* vv, uint32_
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (nc + j < p.N) ? (f16)vv[j] : (f16)0.f;
     ST8_OUT(p, p.Y + (int64_t)m * p.ldy + nc, o);
+}
+template <bool SG = false, bool LIGHT = false>
+DEVFN void nt_epilogue8(const GemmNtParams& p, int m, int nc, float* vv, uint32_t rkey, bool bias_done = false) {
+    nt_epilogue8_rows<SG, LIGHT>(p, m, m, m, nc, vv, rkey, bias_done);
 }

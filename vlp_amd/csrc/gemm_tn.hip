@@ -32,6 +32,8 @@ struct GemmTnParams {
     f16* bias_out;               // [N] or NULL: column sums of A (bias gradient), fused
     int M, N, K, beta, splits, rows_per_split;
     int tiles_k, tiles_n, xcd_remap, split_major;
+    const int32_t* live;         // listed contraction rows (vlp_gemm_tn_grouped_rows): B row m is read at live[m], < 0 = pad (adds nothing); or nullptr
+    int a_listed;                // with live: A row m is read at live[m] too (else A is compact: row m)
 };
 
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
@@ -224,7 +226,8 @@ DEVFN int tn_swz(int r) { return ((r & 3) | (((r >> 3) & 1) << 2)) << 1; }
 #define TN_SK_WRITE 1
 #define TN_SK_FINAL 2
 #define TN_SK_SLOTS 20       // f32x4 per thread in a partial: 16 accumulator tiles + 4 bias tiles
-template <int BN_T, int BK_T, int NS = 2, int BM_T = TN_BM, bool SK = false>
+// LISTED: the problem walks a row list (p.live, vlp_gemm_tn_grouped_rows); compiled out of every other caller
+template <int BN_T, int BK_T, int NS = 2, int BM_T = TN_BM, bool SK = false, bool LISTED = false>
 DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begin = 0, int sk_m_end = 0, int sk_role = 0, float* sk_part = nullptr,
                         int* sk_flag = nullptr) {
     constexpr int WK_ = BK_T / 64;
@@ -288,7 +291,28 @@ DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begi
         f16* as = smem + buf * (ATILE + BTILE);
         f16* bs = as + ATILE;
         const int mbase = m_begin + st * BM_T;
-        if (mbase + BM_T <= m_end) {            // full stage (wave-uniform): LDS-DMA, 64 lanes = 1 KiB contiguous in LDS
+        if (LISTED) {                             // listed rows: every stage through registers, row m fetched at live[m], pads zero-filled
+#pragma unroll
+            for (int i = 0; i < AP; ++i) {
+                const int r = arow + ARP * i, m = mbase + r;
+                u32x4 v = (u32x4){0, 0, 0, 0};
+                if (m < m_end) {
+                    const int lr = p.live[m];
+                    if (lr >= 0) v = *reinterpret_cast<const u32x4*>(p.A + (int64_t)(p.a_listed ? lr : m) * p.lda + acol[i]);
+                }
+                *reinterpret_cast<u32x4*>(as + r * BN_T + apc * 8) = v;
+            }
+#pragma unroll
+            for (int i = 0; i < BP; ++i) {
+                const int r = brow + BRP * i, m = mbase + r;
+                u32x4 v = (u32x4){0, 0, 0, 0};
+                if (m < m_end) {
+                    const int lr = p.live[m];
+                    if (lr >= 0) v = *reinterpret_cast<const u32x4*>(p.B + (int64_t)lr * p.ldb + bcol[i]);
+                }
+                *reinterpret_cast<u32x4*>(bs + r * BK_T + bpc * 8) = v;
+            }
+        } else if (mbase + BM_T <= m_end) {            // full stage (wave-uniform): LDS-DMA, 64 lanes = 1 KiB contiguous in LDS
             const uint32_t as_l = smem_lds + (uint32_t)(buf * (ATILE + BTILE)) * 2u, bs_l = as_l + (uint32_t)ATILE * 2u;
             const int64_t aoff = (int64_t)st * BM_T * p.lda, boff = (int64_t)st * BM_T * p.ldb;
 #pragma unroll
@@ -351,13 +375,14 @@ DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begi
             if (i < nstages) stage(i, i);
         int buf = 0, nbuf = NS - 1;
         const bool tail_ragged = ((m_end - m_begin) % BM_T) != 0;
+        const bool listed = LISTED;                 // every stage goes through registers + ds_write: nothing stays in flight across the barrier
         for (int st = 0; st < nstages; ++st) {
             // stage st must have landed; up to NS - 2 younger FULL stages may stay in flight.  A ragged last stage goes through registers +
             // ds_write (compiler-tracked loads, waited for -- with everything older -- inside stage()): once it is among the younger
             // ones the queue has been drained already, and vmcnt(0) costs nothing.
             const int left = nstages - 1 - st;
             int younger = left < NS - 2 ? left : NS - 2;
-            if (tail_ragged && st + younger >= nstages - 1) younger = 0;
+            if ((tail_ragged && st + younger >= nstages - 1) || listed) younger = 0;
             if (NS >= 4 && younger == 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LPS) : "memory");
             else if (NS >= 3 && younger >= 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LPS) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -458,6 +483,7 @@ struct TnGroupEntry {
     f16* C; int64_t ldc;
     f16* bias_out;
     int M, N, K, beta, tiles_k, tile_begin;
+    const int32_t* live; int a_listed;      // vlp_gemm_tn_grouped_rows: the problem's row list (GemmTnParams), or nullptr
 };
 struct TnGroupParams {
     TnGroupEntry e[TN_GROUP_MAX];
@@ -480,7 +506,9 @@ __global__ __launch_bounds__((BN_T / 64) * (BK_T / 64) * 64, 2) void gemm_tn_gro
     p.slab = nullptr; p.bias_slab = nullptr; p.bias_out = e.bias_out;
     p.M = e.M; p.N = e.N; p.K = e.K; p.beta = e.beta; p.splits = 1; p.rows_per_split = (e.M + TN_BM - 1) / TN_BM * TN_BM;
     p.tiles_k = e.tiles_k; p.tiles_n = 0; p.xcd_remap = 0; p.split_major = 0;
-    tn_glds_tile<BN_T, BK_T, NS, BM_T>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
+    p.live = e.live; p.a_listed = e.a_listed;
+    if (e.live) tn_glds_tile<BN_T, BK_T, NS, BM_T, false, true>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
+    else tn_glds_tile<BN_T, BK_T, NS, BM_T>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
 }
 
 #ifdef VLP_LAB_BUILD      // measured in round 4 and not kept (profiles/r04_grouped_wgrad_balanced.txt): investigation builds only
@@ -513,6 +541,7 @@ __global__ __launch_bounds__((BN_T / 64) * (BK_T / 64) * 64, 2) void gemm_tn_gro
         p.slab = nullptr; p.bias_slab = nullptr; p.bias_out = e.bias_out;
         p.M = e.M; p.N = e.N; p.K = e.K; p.beta = e.beta; p.splits = 1; p.rows_per_split = 0;
         p.tiles_k = e.tiles_k; p.tiles_n = 0; p.xcd_remap = 0; p.split_major = 0;
+        p.live = nullptr; p.a_listed = 0;
         if (j < 6)
             tn_glds_tile<BN_T, BK_T, NS, BM_T, true>(p, tile - e.tile_begin, reinterpret_cast<f16*>(smem_raw), 0, cut * BM_T, TN_SK_FINAL,
                                                        part + (int64_t)tile * (TN_SK_SLOTS * T * 4), flags + grp);
@@ -616,6 +645,7 @@ extern "C" int vlp_gemm_tn(const vlp_gemm_tn_args* a, void* stream) {
     p.tiles_n = cdiv(a->N, TN_BN);
     p.xcd_remap = (a->variant & 8) ? 1 : 0;
     p.split_major = (a->variant & 16) ? 1 : 0;
+    p.live = nullptr; p.a_listed = 0;
     if (splits > 1) {
         const int64_t need = (int64_t)splits * a->N * a->K * (int64_t)sizeof(float) + (a->bias_out ? (int64_t)splits * a->N * (int64_t)sizeof(float) : 0);
         if (!a->workspace || a->workspace_bytes < need)
@@ -679,9 +709,7 @@ static int tn_check_one(const vlp_gemm_tn_args* a) {
     return VLP_OK;
 }
 
-extern "C" int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, void* stream) {
-    VLP_CHECK_ARG(list != nullptr && count >= 1 && count <= TN_GROUP_MAX, "vlp_gemm_tn_grouped: 1..%d problems", TN_GROUP_MAX);
-    VLP_ENTER(list[0].A, "vlp_gemm_tn_grouped");
+static int tn_grouped_launch(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* lflags, int32_t count, void* stream) {
     // tile shape / ring depth of the grouped launch: 0 = 128x128 tiles, 2 stages (two 4-wave workgroups per CU); 1 = 256x128, 2 stages;
     // 2 = 256x128, 3 stages; 3 = 128x256, 3 stages (8-wave workgroups, one per CU); 4 = 128x128, FOUR stages of 32 contraction rows (same 64 KiB:
     // two workgroups per CU, three stages in flight).  VLP_TN_GROUP_MODE overrides (A/B runs).
@@ -702,6 +730,8 @@ extern "C" int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, 
         e.A = (const f16*)a->A; e.lda = a->lda; e.B = (const f16*)a->B; e.ldb = a->ldb; e.C = (f16*)a->C; e.ldc = a->ldc;
         e.bias_out = (f16*)a->bias_out;
         e.M = a->M; e.N = a->N; e.K = a->K; e.beta = a->beta;
+        e.live = live ? live[i] : nullptr;
+        e.a_listed = (e.live && lflags && (lflags[i] & VLP_ROWS_X)) ? 1 : 0;
         e.tiles_k = cdiv(a->K, bk);
         e.tile_begin = tiles;
         tiles += e.tiles_k * cdiv(a->N, bn);
@@ -715,7 +745,7 @@ extern "C" int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, 
         hipLaunchKernelGGL((gemm_tn_grouped_kernel<BNT, BKT, NSV, BMV>), dim3(tiles), dim3(((BNT) / 64) * ((BKT) / 64) * 64), smem, (hipStream_t)stream, gp); \
     } while (0)
 #ifdef VLP_LAB_BUILD
-    bool sk = (mode == 5);
+    bool sk = (mode == 5) && !live;
     if (sk) {
         const int64_t need = vlp_gemm_tn_grouped_workspace_bytes(tiles);
         sk = tiles % 6 == 0 && list[0].workspace != nullptr && list[0].workspace_bytes >= need && (uintptr_t)list[0].workspace % 16 == 0 && cdiv(list[0].M, 64) >= 14;
@@ -744,4 +774,16 @@ extern "C" int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, 
 #undef LAUNCH_TN_GROUP
     VLP_CHECK_LAUNCH("vlp_gemm_tn_grouped");
     return VLP_OK;
+}
+
+extern "C" int vlp_gemm_tn_grouped(const vlp_gemm_tn_args* list, int32_t count, void* stream) {
+    VLP_CHECK_ARG(list != nullptr && count >= 1 && count <= TN_GROUP_MAX, "vlp_gemm_tn_grouped: 1..%d problems", TN_GROUP_MAX);
+    VLP_ENTER(list[0].A, "vlp_gemm_tn_grouped");
+    return tn_grouped_launch(list, nullptr, nullptr, count, stream);
+}
+
+extern "C" int vlp_gemm_tn_grouped_rows(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* flags, int32_t count, void* stream) {
+    VLP_CHECK_ARG(list != nullptr && live != nullptr && count >= 1 && count <= TN_GROUP_MAX, "vlp_gemm_tn_grouped_rows: 1..%d problems and their row lists", TN_GROUP_MAX);
+    VLP_ENTER(list[0].A, "vlp_gemm_tn_grouped_rows");
+    return tn_grouped_launch(list, live, flags, count, stream);
 }

@@ -227,11 +227,14 @@ DEVFN void lnb_block_partials(Sums sums, float* __restrict__ part, int H) {
 // "prefetch" was waited for in the iteration that issued it -- one row in flight per wave, not two.  Here every iteration issues exactly the
 // same loads (the next row is clamped to M - 1 instead of skipped; the optional operands are template switches), so with EXACT the waits are
 // counted and a wave really keeps two rows of HBM traffic in flight.
-template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP>
+// LIST (vlp_layernorm_bwd_rows): M entries of `live`; entry m names the row of x / mean / rstd (and, by `lflags`, of dy and dx), < 0 is a pad
+// that is skipped.  The row arithmetic is the one of the unlisted kernel: a listed row gets the bits an unlisted launch gives it.
+template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP, bool LIST = false>
 __global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? 4 : (NP == 4 ? 3 : 2)) void layernorm_bwd_kernel(
     const f16* __restrict__ dy, int64_t lddy, const f16* __restrict__ x, int64_t ldx, const f16* __restrict__ gamma,
     const float* __restrict__ mean, const float* __restrict__ rstd, f16* __restrict__ dx, int64_t lddx,
-    f16* __restrict__ dxd, int64_t lddxd, float* __restrict__ part, int M, int H_, DropCtx dyd, DropCtx outd, const int32_t* __restrict__ row_map) {
+    f16* __restrict__ dxd, int64_t lddxd, float* __restrict__ part, int M, int H_, DropCtx dyd, DropCtx outd, const int32_t* __restrict__ row_map,
+    const int32_t* __restrict__ live = nullptr, int lflags = 0) {
     const int H = EXACT ? 256 * NP : H_;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * LNB_WAVES + (threadIdx.x >> 6);
@@ -251,7 +254,24 @@ __global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? 4 : (NP == 4 ? 3 : 2)) void 
     f16x4 xc[NP], dc[NP], xn[NP], dn[NP];
     float mu_c, rs_c, mu_n, rs_n;
     int map_c = 0, map_n = 0;
-    auto fetch = [&](int row, f16x4 (&X)[NP], f16x4 (&D)[NP], float& m_, float& r_, int& mp_) {
+    int lr_c = 0, lr_n = 0;                // LIST: live[row] of the current / next row
+    auto fetch = [&](int row, f16x4 (&X)[NP], f16x4 (&D)[NP], float& m_, float& r_, int& mp_, int& lr_) {
+        if constexpr (LIST) {
+            lr_ = live[row];
+            const int src = max(lr_, 0);       // (a pad entry fetches row 0 and is skipped below)
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int c = 256 * k + 4 * lane;
+                if (EXACT || c < H) {
+                    X[k] = ld4(x + (int64_t)src * ldx + c);
+                    D[k] = ld4(dy + (int64_t)((lflags & VLP_ROWS_X) ? src : row) * lddy + c);
+                }
+            }
+            m_ = mean[src];
+            r_ = rstd[src];
+            if constexpr (HAS_MAP) mp_ = row_map[src];
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int c = 256 * k + 4 * lane;
@@ -264,15 +284,11 @@ __global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? 4 : (NP == 4 ? 3 : 2)) void 
         r_ = rstd[row];
         if constexpr (HAS_MAP) mp_ = row_map[row];
     };
-    if (wave >= M) {                       // (no rows: only the zero partials below)
-        mu_c = rs_c = 0.f;
-    } else {
-        fetch(wave, xc, dc, mu_c, rs_c, map_c);
-    }
-    for (int row = wave; row < M; row += nwaves) {
-        fetch(min(row + nwaves, M - 1), xn, dn, mu_n, rs_n, map_n);        // ALWAYS (the tail re-reads row M - 1): a countable loop body
+    // one row: the current registers (xc, dc, statistics) -> dx (+ twin) and the lane's column sums
+    auto row_body = [&](int row) {
         const float mu = mu_c, rs = rs_c;
-        const uint64_t drow = HAS_MAP ? (uint64_t)(uint32_t)map_c : (uint64_t)row;
+        const int orow = (LIST && (lflags & VLP_ROWS_Y)) ? lr_c : row;
+        const uint64_t drow = HAS_MAP ? (uint64_t)(uint32_t)map_c : (uint64_t)(LIST ? lr_c : row);
         const uint32_t rk_dy = dyd.thresh ? drop_rowkey(dyd, drow) : 0u;
         const uint32_t rk_out = outd.thresh ? drop_rowkey(outd, drow) : 0u;
         float xh[NP][4], d[NP][4];
@@ -313,15 +329,42 @@ __global__ __launch_bounds__(LNB_THREADS, NP <= 3 ? 4 : (NP == 4 ? 3 : 2)) void 
                     o[e] = (f16)t;
                     od[e] = (f16)(t * m4[e]);
                 }
-                st4_out<VLP_SS_LN>(dx + (int64_t)row * lddx + c, o);
+                st4_out<VLP_SS_LN>(dx + (int64_t)orow * lddx + c, o);
                 if (HAS_DXD) st4_out<VLP_SS_LN>(dxd + (int64_t)row * lddxd + c, od);
             }
         }
+    };
+    if constexpr (LIST) {
+        // The listed row live[m] is taken by the wave that walks it in the unlisted launch of the same grid (row % nwaves), in ascending row
+        // order (the list is ascending): the lane's column sums, the block partials and so dgamma / dbeta get the unlisted launch's bits --
+        // there the rows in between add exact zeros.  Every wave scans the list 64 entries at a time; pads (-1) match nobody.
+        for (int base = 0; base < M; base += 64) {
+            const int e = base + lane;
+            const int lv = e < M ? live[e] : -1;
+            unsigned long long mask = __ballot(lv >= 0 && (lv % nwaves) == wave);
+            while (mask) {
+                const int bit = __ffsll(mask) - 1;
+                mask &= mask - 1;
+                fetch(base + bit, xc, dc, mu_c, rs_c, map_c, lr_c);
+                row_body(base + bit);
+            }
+        }
+    } else {
+        if (wave >= M) {                       // (no rows: only the zero partials below)
+            mu_c = rs_c = 0.f;
+        } else {
+            fetch(wave, xc, dc, mu_c, rs_c, map_c, lr_c);
+        }
+        for (int row = wave; row < M; row += nwaves) {
+            fetch(min(row + nwaves, M - 1), xn, dn, mu_n, rs_n, map_n, lr_n);        // ALWAYS (the tail re-reads row M - 1): a countable loop body
+            row_body(row);
 #pragma unroll
-        for (int k = 0; k < NP; ++k) { xc[k] = xn[k]; dc[k] = dn[k]; }
-        mu_c = mu_n;
-        rs_c = rs_n;
-        map_c = map_n;
+            for (int k = 0; k < NP; ++k) { xc[k] = xn[k]; dc[k] = dn[k]; }
+            mu_c = mu_n;
+            rs_c = rs_n;
+            map_c = map_n;
+            lr_c = lr_n;
+        }
     }
     lnb_block_partials<NP, EXACT>([&](int k, int b) { return b ? (f32x4){db[k][0], db[k][1], db[k][2], db[k][3]} : (f32x4){dg[k][0], dg[k][1], dg[k][2], dg[k][3]}; },
                                   part, H);
@@ -377,26 +420,26 @@ extern "C" int64_t vlp_layernorm_bwd_workspace_bytes(int32_t H) {
     return (int64_t)LNB_BLOCKS * 2 * H * (int64_t)sizeof(float);
 }
 
-template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP>
-static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s) {
-    const auto kernel = layernorm_bwd_kernel<NP, EXACT, HAS_DXD, HAS_MAP>;
+template <int NP, bool EXACT, bool HAS_DXD, bool HAS_MAP, bool LIST = false>
+static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s, const int32_t* live = nullptr,
+                          int lflags = 0) {
+    const auto kernel = layernorm_bwd_kernel<NP, EXACT, HAS_DXD, HAS_MAP, LIST>;
     VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LNB_WAVES * 2 * 256 * NP * 4));
     const size_t lnb_smem = (size_t)LNB_WAVES * 2 * a->H * sizeof(float);   // <= 128 KiB at H = 2048
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(LNB_THREADS), lnb_smem, s, (const f16*)a->dy, a->lddy, (const f16*)a->x, a->ldx, (const f16*)a->gamma,
-                       a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, (float*)a->workspace, a->M, a->H, dyd, outd, a->row_map);
+                       a->mean, a->rstd, (f16*)a->dx, a->lddx, (f16*)a->dx_drop, a->lddxd, (float*)a->workspace, a->M, a->H, dyd, outd, a->row_map, live, lflags);
 }
-template <int NP, bool EXACT>
-static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s) {
+template <int NP, bool EXACT, bool LIST = false>
+static void launch_ln_bwd(const vlp_layernorm_bwd_args* a, int blocks, const DropCtx& dyd, const DropCtx& outd, hipStream_t s, const int32_t* live = nullptr,
+                          int lflags = 0) {
     const bool hd = a->dx_drop != nullptr, hm = a->row_map != nullptr && (dyd.thresh || outd.thresh);
-    if (hd && hm) launch_ln_bwd<NP, EXACT, true, true>(a, blocks, dyd, outd, s);
-    else if (hd) launch_ln_bwd<NP, EXACT, true, false>(a, blocks, dyd, outd, s);
-    else if (hm) launch_ln_bwd<NP, EXACT, false, true>(a, blocks, dyd, outd, s);
-    else launch_ln_bwd<NP, EXACT, false, false>(a, blocks, dyd, outd, s);
+    if (hd && hm) launch_ln_bwd<NP, EXACT, true, true, LIST>(a, blocks, dyd, outd, s, live, lflags);
+    else if (hd) launch_ln_bwd<NP, EXACT, true, false, LIST>(a, blocks, dyd, outd, s, live, lflags);
+    else if (hm) launch_ln_bwd<NP, EXACT, false, true, LIST>(a, blocks, dyd, outd, s, live, lflags);
+    else launch_ln_bwd<NP, EXACT, false, false, LIST>(a, blocks, dyd, outd, s, live, lflags);
 }
 
-extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) {
-    VLP_CHECK_ARG(a && a->dy && a->x && a->gamma && a->mean && a->rstd && a->dx && a->dgamma && a->dbeta, "vlp_layernorm_bwd: null operand");
-    VLP_ENTER(a->dy, "vlp_layernorm_bwd");
+static int ln_bwd_launch(const vlp_layernorm_bwd_args* a, const int32_t* live, int lflags, int part_M, void* stream) {
     VLP_CHECK_ARG(a->M > 0 && a->H > 0 && a->H % 8 == 0 && a->H <= 2048, "vlp_layernorm_bwd: H=%d must be a multiple of 8 and <= 2048", a->H);
     VLP_CHECK_ARG(a->lddy % 8 == 0 && a->ldx % 8 == 0 && a->lddx % 8 == 0, "vlp_layernorm_bwd: leading dims");
     VLP_CHECK_ARG(((uintptr_t)a->dy | (uintptr_t)a->x | (uintptr_t)a->dx | (uintptr_t)a->gamma) % 16 == 0, "vlp_layernorm_bwd: alignment");
@@ -405,9 +448,17 @@ extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) 
     if (!a->workspace || a->workspace_bytes < need) return vlp_set_error(VLP_ERR_WORKSPACE, "vlp_layernorm_bwd: workspace %lld < %lld", (long long)a->workspace_bytes, (long long)need);
     const DropCtx dyd = make_drop(a->dy_drop_p, a->dy_seed, a->dy_stream);
     const DropCtx outd = make_drop(a->out_drop_p, a->out_seed, a->out_stream);
-    const int blocks = lnb_blocks(a->M);
+    // listed rows: the grid of the unlisted launch over part_M rows, so that every partial row the deferred reduce reads is written (zeros
+    // where a block saw no row) and every listed row is summed by the wave, and in the order, of that launch
+    const int blocks = lnb_blocks(live ? part_M : a->M);
     hipStream_t s = (hipStream_t)stream;
-    if (a->H == 768) launch_ln_bwd<3, true>(a, blocks, dyd, outd, s);
+    if (live) {
+        if (a->H == 768) launch_ln_bwd<3, true, true>(a, blocks, dyd, outd, s, live, lflags);
+        else if (a->H <= 768) launch_ln_bwd<3, false, true>(a, blocks, dyd, outd, s, live, lflags);
+        else if (a->H <= 1024) launch_ln_bwd<4, false, true>(a, blocks, dyd, outd, s, live, lflags);
+        else launch_ln_bwd<8, false, true>(a, blocks, dyd, outd, s, live, lflags);
+    }
+    else if (a->H == 768) launch_ln_bwd<3, true>(a, blocks, dyd, outd, s);
     else if (a->H <= 768) launch_ln_bwd<3, false>(a, blocks, dyd, outd, s);
     else if (a->H <= 1024) launch_ln_bwd<4, false>(a, blocks, dyd, outd, s);
     else launch_ln_bwd<8, false>(a, blocks, dyd, outd, s);
@@ -417,6 +468,19 @@ extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) 
                        (f16*)a->dbeta, a->beta);
     VLP_CHECK_LAUNCH("vlp_layernorm_bwd_reduce");
     return VLP_OK;
+}
+
+extern "C" int vlp_layernorm_bwd(const vlp_layernorm_bwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->dy && a->x && a->gamma && a->mean && a->rstd && a->dx && a->dgamma && a->dbeta, "vlp_layernorm_bwd: null operand");
+    VLP_ENTER(a->dy, "vlp_layernorm_bwd");
+    return ln_bwd_launch(a, nullptr, 0, 0, stream);
+}
+
+extern "C" int vlp_layernorm_bwd_rows(const vlp_layernorm_bwd_args* a, const int32_t* live, int32_t flags, int32_t part_M, void* stream) {
+    VLP_CHECK_ARG(a && a->dy && a->x && a->gamma && a->mean && a->rstd && a->dx && a->dgamma && a->dbeta && live, "vlp_layernorm_bwd_rows: null operand");
+    VLP_ENTER(a->dy, "vlp_layernorm_bwd_rows");
+    VLP_CHECK_ARG((flags & ~(VLP_ROWS_X | VLP_ROWS_Y)) == 0 && part_M > 0, "vlp_layernorm_bwd_rows: bad flags %d / part_M %d", flags, part_M);
+    return ln_bwd_launch(a, live, flags, part_M, stream);
 }
 
 extern "C" int vlp_layernorm_bwd_reduce_batched(const float* parts, const void* const* dst, int32_t count, int32_t M, int32_t H, int32_t beta, void* stream) {

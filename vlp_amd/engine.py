@@ -150,6 +150,7 @@ class Engine(object):
         self._pk_cache = {}               # kept-length tuple -> (row_off, row_map device tensors, M'): batches repeat in bench / epochs
         self._pk_lens = {}                # id(mask tensor) -> (weakref, version, ..., lens): lengths derived from a dense mask, once per tensor
         self.last_packed_rows = None      # M' of the latest packed forward (None: dense) -- bench.py / tests read it
+        self._live_n = None               # device int32 [1]: rows the latest backward's listed-row path walked (None: the full path ran)
 
     # ------------------------------------------------------------------------------------------
     # parameter packing
@@ -381,6 +382,10 @@ class Engine(object):
             ws.update(sel=h(R, H), tz=h(R, H), tg=h(R, H), tln=h(R, H), tstat=(f(R), f(R)), logits=h(R, Vp), dlogits=h(R, Vp),
                       dlT=h(Vp, _ru(R, 64)),
                       lse_ce=f(R), coef=f(R), row_loss=f(R), dtln=h(R, H), dtg=h(R, H), dtz=h(R, H), dsel=h(R, H))
+            # listed-row backward of the last layer (Engine.backward): the row list (<= R distinct masked rows, -1 padded), its length, and
+            # the compact [R, *] gradients between the kernels that walk the list
+            ws.update(lv_rows=torch.empty(R, device=dev, dtype=torch.int32), lv_n=torch.zeros(1, device=dev, dtype=torch.int32),
+                      lv_dpre2=h(R, H), lv_dpre2_d=h(R, H), lv_dz=h(R, I), lv_dx1=h(R, H), lv_dpre1_d=h(R, H))
         ws["loss"] = f(260)
         if model.tasks == "vqa2":
             NA = model.num_answers
@@ -1350,9 +1355,65 @@ class Engine(object):
         var, sp = self._tn_splits(a, b, c, M, N, Kd, ws)
         K.gemm_tn(a, b, c, M, N, Kd, beta=beta, workspace=ws[ws_key], variant=var, bias_out=bias, splits=sp, **kw)
 
+    @property
+    def last_live_rows(self):
+        """Length of the row list the latest backward ran the last layer over (the distinct masked rows), or None when every row was
+        walked.  The length lives on the device (no host read-back inside the step): reading this property synchronises."""
+        return None if self._live_n is None else int(self._live_n.item())
+
     def _bucket_done(self, idx):
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(idx)
+
+    def _layer_bwd_live(self, i, st, ws, sh, ds, live, R, M, rm, ro, beta, grouped, on_side, use_side, side, ln_slot, scale):
+        """Backward of encoder layer i when only the rows in `live` (device int32 [R], ascending, -1 padded) carry gradient into it: the two
+        LayerNorm backwards, the FFN and attention-output dgrads and their three weight gradients walk the list and read the saved
+        activations in place at row live[m]; the gradients between them are compact [R, *].  Attention backward and the QKV dgrad / wgrad stay
+        dense: they read dctx and the dpre1 residual, which hold exact zeros outside the listed rows."""
+        model = self._model()
+        cfg = model.config
+        H, I, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        B, L, seed = st.B, st.L, st.seed
+        p, pa = st.p_drop
+        Ln = "bert.encoder.layer.%d." % i
+        a, s = ws["layers"][i], sh["layers"][i]
+        x_in = ws["layers"][i - 1]["x2"] if i > 0 else ws["x0"]
+        dx, dctx, dpre1 = ws["dx"], ws["dctx"], ds["dpre1"]      # (dctx and dpre1 were cleared by backward's live_prologue)
+        # BertOutput: dx is read at the listed rows, everything downstream is compact
+        K.layernorm_bwd_rows(dx, a["pre2"], self.P(Ln + "output.LayerNorm.weight"), a["st2"][0], a["st2"][1], ws["lv_dpre2"],
+                             self.G(Ln + "output.LayerNorm.weight"), self.G(Ln + "output.LayerNorm.bias"), live, K.ROWS_X, R, H, ln_slot(2 * i + 1), M,
+                             beta=beta, dx_drop=ws["lv_dpre2_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 3), defer_reduce=True, row_map=rm)
+        dy2 = ws["lv_dpre2_d"] if p > 0 else ws["lv_dpre2"]
+        K.gemm_nt_rows(dy2, s["w2T"], ws["lv_dz"], live, K.ROWS_MUL, R, I, H, mul_src=a["z"], mul_mode=K.MUL_PLAIN)
+        K.gemm_nt_rows(ws["lv_dz"], s["w1T"], ws["lv_dx1"], live, 0, R, H, I, residual=ws["lv_dpre2"])
+        # BertSelfOutput: the undropped dpre1 goes to its rows of the cleared full buffer (residual of the dense QKV dgrad below)
+        K.layernorm_bwd_rows(ws["lv_dx1"], a["pre1"], self.P(Ln + "attention.output.LayerNorm.weight"), a["st1"][0], a["st1"][1], dpre1,
+                             self.G(Ln + "attention.output.LayerNorm.weight"), self.G(Ln + "attention.output.LayerNorm.bias"), live, K.ROWS_Y, R, H,
+                             ln_slot(2 * i), M, beta=beta, dx_drop=ws["lv_dpre1_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 2),
+                             defer_reduce=True, row_map=rm)
+        dy1, dy1_fl = (ws["lv_dpre1_d"], 0) if p > 0 else (dpre1, K.ROWS_X)
+        K.gemm_nt_rows(dy1, s["oT"], dctx, live, dy1_fl | K.ROWS_Y, R, H, H)
+        dqkv = ds["dqkv"]
+        K.attn_bwd(a["qkv"], ws["maskb"], ws["maskt"], a["ctx"], dctx, a["lse"], dqkv, ws["delta"], B, L, A, scale, dropout_p=pa, seed=seed,
+                   rng_stream=16 * i + 1, row_off=ro)
+
+        def last_wgrad():
+            listed = [(dy2, a["g"], self.G(Ln + "output.dense.weight"), R, H, I, beta, self.G(Ln + "output.dense.bias"), live, 0),
+                      (ws["lv_dz"], a["x1"], self.G(Ln + "intermediate.dense.weight"), R, I, H, beta, self.G(Ln + "intermediate.dense.bias"), live, 0),
+                      (dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), R, H, H, beta, self.G(Ln + "attention.output.dense.bias"), live, dy1_fl)]
+            qkv = (dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, beta, self.G(Ln + "attention.self.query.bias"))
+            if grouped:
+                K.gemm_tn_grouped_rows(listed[:2] + [qkv + (None, 0)] + listed[2:])
+            else:
+                K.gemm_tn_grouped_rows(listed)
+                self._tn(*qkv[:6], ws, beta, bias=qkv[7])
+            self._bucket_done(cfg.num_hidden_layers - i)
+            if use_side:
+                ev = torch.cuda.Event()
+                ev.record(side)
+                self._side_done[i & 1] = ev
+        on_side(last_wgrad)
+        self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre1)
 
     def backward(self, st, gscale, task, g_pretext=None, g_rows=None):
         """gscale: device f32 tensor [1] = upstream gradient of the task loss (x loss scale); g_pretext: the same for the pretext loss of
@@ -1407,6 +1468,26 @@ class Engine(object):
         if use_side:
             self._side_busy = True
         head_wgrads = []        # weight gradients of the task head: issued on the side stream once the head's dgrad chain is on the main stream
+
+        # The gradient that enters the encoder is zero outside the masked rows, and LayerNorm backward and the dgrad GEMMs keep a zero row
+        # zero: until attention mixes rows, the last layer's backward runs over the list of masked rows only (VLP_LAST_LAYER_LIVE=0: over all
+        # rows, as every other layer).  Heads whose gradient reaches other rows (vqa2, pretext, per-token log-probabilities) keep the full path.
+        live = live_ready = None
+        if (task != "vqa2" and task != "logprob" and st.has_mlm and P > 0 and st.pretext is None
+                and os.environ.get("VLP_LAST_LAYER_LIVE", "1") != "0"):
+            live, Rl = ws["lv_rows"], B * P
+
+            def live_prologue():
+                # the list and the two cleared full-size buffers the dense kernels of the last layer read (dctx: attention backward; dpre1: the
+                # residual of the QKV dgrad).  None of it depends on the head's gradient: it runs beside the head chain
+                K.live_rows_build(masked_pos.contiguous(), B, P, L, live, ws["lv_n"], row_off=ro)
+                ws["dctx"][:M].zero_()
+                ws["dyset"][(NL - 1) & 1]["dpre1"][:M].zero_()
+            on_side(live_prologue)
+            if use_side:
+                live_ready = torch.cuda.Event()
+                live_ready.record(side)
+        self._live_n = ws["lv_n"] if live is not None else None
 
         # ---- heads ------------------------------------------------------------------------------------
         if task == "vqa2":
@@ -1499,6 +1580,11 @@ class Engine(object):
             ds = ws["dyset"][i & 1]
             if use_side and self._side_done[i & 1] is not None:
                 main.wait_event(self._side_done[i & 1])       # wgrads of layer i+2 have finished reading this set
+            if live is not None and i == NL - 1:
+                if live_ready is not None:
+                    main.wait_event(live_ready)
+                self._layer_bwd_live(i, st, ws, sh, ds, live, Rl, M, rm, ro, beta, grouped, on_side, use_side, side, ln_slot, scale)
+                continue
             # BertOutput: LN(dropout(dense(g)) + x1)   (modeling.py:353-357)
             dpre = ds["dpre2"]
             K.layernorm_bwd(dx, a["pre2"], self.P(Ln + "output.LayerNorm.weight"), a["st2"][0], a["st2"][1], dpre,
