@@ -129,7 +129,7 @@ class Engine(object):
         self._ln_tab = None               # _ln_table()
         self._zero1 = None                # zero_placeholder()
         self._pretext_on = False          # the latest forward ran with mask_image_regions
-        self._pooler_dirty = False        # the latest backward wrote pooler gradients (pretext branch)
+        self._pooler_dirty = False        # the pooler gradient buffer holds something a beta == 0 backward without the pretext branch must clear
         self.prof = None                  # list -> every PROF_EVERY-th NT-GEMM launch is bracketed by HIP events (bench.py roofline)
         self._opt_stream = None           # optimizer stream of the pipelined FusedAdam step (optimization_fp16._step_pipelined)
         self._param_events = None         # {"nodecay" | bucket index: event} of the last pipelined optimizer step, consumed by forward
@@ -1546,10 +1546,11 @@ class Engine(object):
             K.transpose(self.P("bert.pooler.dense.weight"), H, ptw["pT"], H, H, H, H)
             self._nt(ptw["dpool"], ptw["pT"], ptw["dsel0"], B, H, H)
             K.scatter_add_rows(ptw["dsel0"], H, ptw["pos0"], dx, H, B, 1, L, H, row_off=ro)
+            self._pooler_dirty = True
         elif beta == 0 and self._pooler_dirty:
             self.G("bert.pooler.dense.weight").zero_()           # a previous pretext step left gradients there; unused now
             self.G("bert.pooler.dense.bias").zero_()
-        self._pooler_dirty = pt is not None
+            self._pooler_dirty = False                           # (an accumulating backward without the branch leaves buffer and flag as they are)
 
         def head_tail():
             for fn in head_wgrads:
