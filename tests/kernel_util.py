@@ -1,5 +1,6 @@
-"""Helpers shared by the kernel-level GPU tests (test_00, test_05, test_06): the error metric, fp16 random inputs, the Python mirror of
-csrc/common.h's dropout hash, and the product / investigation gating of the NT GEMM variants.  One definition, imported by all."""
+"""Helpers shared by the kernel-level GPU tests (test_00, test_05, test_06, test_32): the error metric, fp16 random inputs, the Python mirror of
+csrc/common.h's dropout hash, the fp64 restatement of the fused Adam update, and the product / investigation gating of the NT GEMM variants.
+One definition, imported by all."""
 import pytest
 import torch
 
@@ -18,6 +19,15 @@ def drop_mult_ref(p, seed, stream, rows, cols, device=DEV):
 
 def h16(*shape, scale=1.0, gen=None):
     return (torch.randn(*shape, device=DEV, generator=gen) * scale).half()
+
+
+def _adam_ref(p, m, v, g, combined, step, b1=0.9, b2=0.999, eps=1e-8, decay=0.01):
+    """fp64 restatement of include/vlp_hip.h's vlp_fused_adam (eps outside the sqrt)."""
+    g = g.double() / combined
+    m2 = b1 * m.double() + (1 - b1) * g
+    v2 = b2 * v.double() + (1 - b2) * g * g
+    p2 = p.double() - step * (m2 / (v2.sqrt() + eps) + decay * p.double())
+    return p2, m2, v2
 
 
 # Investigation variants (phased / k32 NT kernels, further wave-pipelined configurations, two-kernel and exchange-tile attention

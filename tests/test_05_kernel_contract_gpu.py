@@ -25,7 +25,7 @@ from oracle import vlp_oracle as O      # noqa: E402   (checker only)
 
 from tests import guard_util as G                                                                      # noqa: E402
 from tests.guard_util import roundup8                                                                  # noqa: E402
-from tests.kernel_util import DEV, LAB, NT_PRODUCT, attn_mask, attn_ref, drop_mult_ref, h16, rel       # noqa: E402
+from tests.kernel_util import DEV, LAB, NT_PRODUCT, _adam_ref, attn_mask, attn_ref, drop_mult_ref, h16, rel      # noqa: E402
 from tests.test_label_smoothing_cpu import smoothed_grad, smoothed_loss, smoothing_values              # noqa: E402
 
 HALF, F32, I64, I32 = torch.float16, torch.float32, torch.int64, torch.int32
@@ -774,15 +774,6 @@ def test_sumsq_sizes_and_accumulate(n, gen):
         assert float(acc.vec[1]) == 1.0, "overflow flag must be sticky across accumulated ranges"
         K.sumsq(g16.vec[:cuts[1]], cuts[1], acc.vec, part)
         assert float(acc.vec[1]) == 0.0 and float(acc.vec[0]) == float(plain[0][0]), "a plain call resets sum and flag"
-
-
-def _adam_ref(p, m, v, g, combined, step, b1=0.9, b2=0.999, eps=1e-8, decay=0.01):
-    """fp64 restatement of include/vlp_hip.h's vlp_fused_adam (eps outside the sqrt)."""
-    g = g.double() / combined
-    m2 = b1 * m.double() + (1 - b1) * g
-    v2 = b2 * v.double() + (1 - b2) * g * g
-    p2 = p.double() - step * (m2 / (v2.sqrt() + eps) + decay * p.double())
-    return p2, m2, v2
 
 
 @pytest.mark.parametrize("n_kind", ["8", "504", "520", "past_cap"])

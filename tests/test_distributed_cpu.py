@@ -1,4 +1,4 @@
-"""CPU, world_size 2 over gloo: the bucketed gradient reducer used by vlp_amd.distributed.DistributedDataParallel
+"""CPU, world_size 2 and 8 over gloo: the bucketed gradient reducer used by vlp_amd.distributed.DistributedDataParallel
 (the N > 1 path of bench.py / run_img2txt_dist.py).  The engine is emulated by firing the ready-hooks in
 completion order on flat CPU buffers."""
 import os
@@ -77,9 +77,9 @@ def _worker(rank, world, init_file, q):
         finally:
             del os.environ["VLP_DDP_CALIBRATE"]
         assert red4.mode in ("allreduce", "rs_ag") and red4.mode_calibration is not None and "measured at construction" in red4.mode_why
-        modes = [None, None]
+        modes = [None] * world
         dist.all_gather_object(modes, red4.mode)
-        assert modes[0] == modes[1]
+        assert all(m == modes[0] for m in modes), modes
         red4.bucket_ready(0)
         red4.bucket_ready(1)
         red4.finish()
@@ -109,26 +109,35 @@ def test_exchange_form_rule():
         choose_mode(8, "nccl", True, never, env="ring")
 
 
-def test_grad_reducer_world2_gloo():
-    world = 2
+def _run_world(world, target, *extra):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     with tempfile.TemporaryDirectory() as d:
         init_file = os.path.join(d, "nonexistent_file")     # same file:// rendezvous style as the reference (:162)
-        procs = [ctx.Process(target=_worker, args=(r, world, init_file, q)) for r in range(world)]
+        procs = [ctx.Process(target=target, args=(r, world, init_file) + extra + (q,)) for r in range(world)]
         for p in procs:
             p.start()
-        results = [q.get(timeout=120) for _ in range(world)]
+        results = [q.get(timeout=180) for _ in range(world)]
         for p in procs:
             p.join(timeout=60)
-    assert sorted(results) == [(0, "ok"), (1, "ok")], results
+    assert sorted(results) == [(r, "ok") for r in range(world)], results
+
+
+# World 8 is the first multi-GPU run's world size.  The world-2 cases keep their names (they are the cases every earlier run of this suite
+# reports under); each has a world-8 twin on the same worker, and a worker compares ALL ranks wherever it compares ranks.
+def test_grad_reducer_world2_gloo():
+    _run_world(2, _worker)
+
+
+def test_grad_reducer_world8_gloo():
+    _run_world(8, _worker)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the REAL 12-layer bucket plan (no GPU needed: Engine.plan_layout is a pure function of the parameter shapes)
 # ---------------------------------------------------------------------------------------------------------------------
 def test_real_12_layer_bucket_plan():
-    from vlp_amd.distributed import coalesce_buckets
+    from vlp_amd.distributed import check_chunking, coalesce_buckets
     from vlp_amd.engine import ALIGN, is_no_decay
     from vlp_amd.modeling import BertConfig, BertForPreTrainingLossMask
     for tasks in ("img2txt", "vqa2"):
@@ -186,8 +195,11 @@ def test_real_12_layer_bucket_plan():
         for si, b in fire_at.items():
             assert slices[si][1] == buckets[b][1]
         assert 5 <= len(buckets) <= 8, len(buckets)        # 231.9 MB of fp16 gradients in <= 50 MB pieces (the 45 MB embedding slice and the region projections are separate buckets)
-        # rs_ag mode needs bucket sizes divisible by the world size (8)
+        # rs_ag mode needs bucket sizes divisible by the world size (8); sharded mode also needs every CHUNK (size // world) to be a whole
+        # number of 8-element vectors, which is what the optimizer kernels take
         assert all((hi - lo) % 8 == 0 for lo, hi in buckets) and sizes["nodecay"] % 8 == 0
+        assert all(((hi - lo) // 8) % 8 == 0 for lo, hi in buckets) and (sizes["nodecay"] // 8) % 8 == 0
+        check_chunking([hi - lo for lo, hi in buckets] + [sizes["nodecay"]], 8, "sharded")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -284,27 +296,20 @@ def _ddp_worker(rank, world, init_file, mode, q):
         dist.destroy_process_group()
 
 
-def _run_world2(target, *extra):
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    with tempfile.TemporaryDirectory() as d:
-        init_file = os.path.join(d, "nonexistent_file")
-        procs = [ctx.Process(target=target, args=(r, world, init_file) + extra + (q,)) for r in range(world)]
-        for p in procs:
-            p.start()
-        results = [q.get(timeout=180) for _ in range(world)]
-        for p in procs:
-            p.join(timeout=60)
-    assert sorted(results) == [(0, "ok"), (1, "ok")], results
-
-
 def test_ddp_hook_wiring_world2_gloo_allreduce():
-    _run_world2(_ddp_worker, "allreduce")
+    _run_world(2, _ddp_worker, "allreduce")
+
+
+def test_ddp_hook_wiring_world8_gloo_allreduce():
+    _run_world(8, _ddp_worker, "allreduce")
 
 
 def test_ddp_hook_wiring_world2_gloo_reduce_scatter_all_gather():
-    _run_world2(_ddp_worker, "rs_ag")
+    _run_world(2, _ddp_worker, "rs_ag")
+
+
+def test_ddp_hook_wiring_world8_gloo_reduce_scatter_all_gather():
+    _run_world(8, _ddp_worker, "rs_ag")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -380,7 +385,7 @@ def _sharded_worker(rank, world, init_file, q):
             # every rank holds the same parameters after the sharded step
             both = [torch.zeros_like(runs["sharded"][0]) for _ in range(world)]
             dist.all_gather(both, runs["sharded"][0])
-            assert torch.equal(both[0], both[1])
+            assert all(torch.equal(both[0], b) for b in both[1:])
         # divisibility is checked at construction, not discovered per step
         try:
             GradReducer(torch.zeros(6146), [(0, 3073), (3073, 6146)], torch.zeros(7), None, bucket_cap_mb=0.001, mode="sharded")
@@ -396,11 +401,58 @@ def _sharded_worker(rank, world, init_file, q):
 
 
 def test_sharded_optimizer_step_world2_gloo():
-    _run_world2(_sharded_worker)
+    _run_world(2, _sharded_worker)
+
+
+def test_sharded_optimizer_step_world8_gloo():
+    _run_world(8, _sharded_worker)
 
 
 def test_ddp_hook_wiring_world2_gloo_sharded():
-    _run_world2(_ddp_worker, "sharded")
+    _run_world(2, _ddp_worker, "sharded")
+
+
+def test_ddp_hook_wiring_world8_gloo_sharded():
+    _run_world(8, _ddp_worker, "sharded")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what sharded mode accepts: the chunks go to the optimizer kernels, which take whole 8-element vectors (no process group needed)
+# ---------------------------------------------------------------------------------------------------------------------
+def test_sharded_chunk_rule_on_the_real_layouts():
+    from tests.shard_util import real_layout
+    from vlp_amd.distributed import ShardPlan, check_chunking
+    for tasks in ("img2txt", "vqa2"):
+        buckets, tail, slices = real_layout(tasks)
+        sizes = [hi - lo for lo, hi in buckets] + [tail]
+        for world in (1, 2, 4, 8):
+            check_chunking(sizes, world, "sharded")
+            for rank in (0, world - 1):
+                plan = ShardPlan(buckets, tail, slices, world, rank)
+                for key in ("decay", "nodecay"):
+                    assert all(lo % 8 == 0 and (hi - lo) % 8 == 0 and hi > lo for lo, hi in plan.owned(key)), (tasks, world, rank, key)
+    # world 16: the vqa2 tail (161728 elements) divides into chunks of 10108 = 8 * 1263 + 4 elements -- vlp_fused_adam would refuse them
+    # on every rank but 0 in the first step; the plan refuses at construction, naming the size, the world and the way out
+    buckets, tail, slices = real_layout("vqa2")
+    assert tail == 161728 and tail % 16 == 0 and (tail // 16) == 10108
+    sizes = [hi - lo for lo, hi in buckets] + [tail]
+    with pytest.raises(ValueError) as e:
+        check_chunking(sizes, 16, "sharded")
+    msg = str(e.value)
+    assert "161728" in msg and "10108" in msg and "16" in msg and "rs_ag" in msg, msg
+    assert all(str(n) not in msg for n in sizes[:-1]), msg               # only the offending sizes are named
+    with pytest.raises(ValueError):
+        ShardPlan(buckets, tail, slices, 16, 3)
+    # rs_ag and allreduce keep the plain divisibility rule: RCCL has no such need
+    check_chunking(sizes, 16, "rs_ag")
+    with pytest.raises(ValueError) as e:
+        check_chunking([4096, 4100], 8, "rs_ag")
+    assert "4100" in str(e.value) and "4096" not in str(e.value)
+    with pytest.raises(ValueError):
+        check_chunking([4096, 4100], 8, "sharded")
+    check_chunking([64, 4096], 8, "sharded")
+    with pytest.raises(ValueError):
+        check_chunking([32, 4096], 8, "sharded")                          # divisible, but chunks of 4
 
 
 def test_bench_self_spawn_for_n_gpus(monkeypatch):

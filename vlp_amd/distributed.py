@@ -30,7 +30,9 @@ autograd graph, so the reducer lives here instead:
     norm and the overflow flag are ONE 4-float all-reduce, and the updated fp16 PARAMETERS are all-gathered bucket by bucket (the same
     bytes as the gradient all-gather they replace) with per-bucket waits in the next forward.  The update arithmetic per element is the
     unsharded kernel's; parameters are bit-identical to the unsharded rs_ag run whenever the clip is inactive (the global norm is
-    summed in another order).  Unmeasured on more than one GPU (world 2 over gloo on CPU and on one GPU, world 1 over RCCL).
+    summed in another order).  Unmeasured on more than one GPU (world 2 and 8 over gloo on CPU, world 2 on one GPU, world 1 over RCCL; the
+    step itself with the real kernels at world 8 by emulating the ranks in one process, tests/test_32_sharded_step_gpu.py).  Accepted world
+    sizes: every chunk must be a multiple of 8 elements (`check_chunking`) -- 1, 2, 4, 8 for the 12-layer models (img2txt also 16).
 """
 import os
 import time
@@ -123,12 +125,12 @@ class GradReducer(object):
             sizes0 = [hi - lo for lo, hi in self.buckets] + ([flat_tail.numel()] if flat_tail is not None else [])
             self.mode, self.mode_why = choose_mode(self.world, dist.get_backend(process_group), all(n % self.world == 0 for n in sizes0), self._calibrate)
         if self.mode != "allreduce":
-            # every bucket (and the tail) is cut into `world` equal chunks: checked HERE, not discovered per step (the engine lays
-            # parameters out on 64-element boundaries, so any power-of-two world up to 64 divides)
+            # every bucket (and the tail) is cut into `world` equal chunks.  What the chunks must satisfy is checked HERE, not discovered per
+            # step: rs_ag only needs them equal (RCCL takes any element count); sharded also hands every chunk to the optimizer kernels, which
+            # take whole 8-element vectors (check_chunking).  The engine lays parameters out on 64-element boundaries, so bucket sizes are
+            # multiples of 64 -- the tail is a sum of padded bias / LayerNorm vectors and need not be a multiple of 8 * world
             sizes = [hi - lo for lo, hi in self.buckets] + ([flat_tail.numel()] if flat_tail is not None else [])
-            bad = [n for n in sizes if n % self.world]
-            if bad:
-                raise ValueError("VLP_DDP_MODE=%s: bucket sizes %r are not divisible by the world size %d" % (self.mode, bad, self.world))
+            check_chunking(sizes, self.world, self.mode)
         # comm profile (bench.py --gpus N, second un-timed pass): per collective the moment its slice was ready (stamp on the issuing
         # stream) and the moment it completed (stamp on an OBSERVER stream that waits for that collective only), plus the end of
         # backward's compute on the main stream -- so a scaling result can be read as exposed vs overlapped communication
@@ -289,6 +291,27 @@ class GradReducer(object):
         return out
 
 
+SHARD_VEC = 8       # elements: vlp_fused_adam takes n % 8 == 0 and 16-byte aligned fp16 pointers, vlp_sumsq a 16-byte aligned gradient
+
+
+def check_chunking(sizes, world, mode):
+    """The rule every exchange form but all-reduce puts on the sizes (elements) of the buckets and of the tail, cut into `world` equal
+    chunks.  rs_ag: `size % world == 0`, nothing else (RCCL has no alignment need).  sharded: the optimizer kernels run on a rank's
+    chunks, and they refuse a range that is not a whole number of 8-element vectors or an fp16 pointer off a 16-byte boundary -- so
+    every chunk `size // world` must also be a multiple of 8 (the buckets tile the buffer from element 0, so chunk starts are then multiples
+    of 8 too, counted from a 128-byte aligned buffer).
+    Pure: raises ValueError naming the offending sizes, returns nothing."""
+    bad = [n for n in sizes if n % world]
+    if bad:
+        raise ValueError("VLP_DDP_MODE=%s: bucket sizes %r are not divisible by the world size %d" % (mode, bad, world))
+    if mode == "sharded":
+        bad = [n for n in sizes if (n // world) % SHARD_VEC]
+        if bad:
+            raise ValueError("VLP_DDP_MODE=sharded: bucket sizes %r cut into %d chunks give chunks of %r elements, not multiples of %d (the optimizer "
+                             "kernels update whole 8-element vectors); use a world size whose chunks are, or VLP_DDP_MODE=rs_ag, which has "
+                             "no such need" % (bad, world, [n // world for n in bad], SHARD_VEC))
+
+
 def owned_chunk(lo, hi, world, rank):
     """Element range of chunk `rank` of the bucket [lo, hi) cut into `world` equal chunks."""
     n = (hi - lo) // world
@@ -298,12 +321,14 @@ def owned_chunk(lo, hi, world, rank):
 class ShardPlan(object):
     """Who owns what in the sharded optimizer step (VLP_DDP_MODE=sharded).  Pure bookkeeping over element ranges -- it runs on CPU
     tensors over gloo exactly as on the GPU over RCCL, so the partitioning, the norm exchange and the parameter all-gather are
-    covered by the world-2 CPU tests with a torch stand-in for the update kernel."""
+    covered by the world-2 / world-8 CPU tests with a torch stand-in for the update kernel.  Construction refuses a world size whose
+    chunks the optimizer kernels would refuse per step (check_chunking)."""
 
     def __init__(self, buckets, tail_numel, slices, world, rank, process_group=None):
         """buckets: coalesced [(lo, hi)] of the main (decay) buffer in completion order; tail_numel: size of the no-decay buffer;
         slices: the engine's ready-slices (to map `wait_params(slice index)` of the next forward onto a bucket)."""
         self.buckets, self.world, self.rank, self.pg = list(buckets), world, rank, process_group
+        check_chunking([hi - lo for lo, hi in self.buckets] + [tail_numel], world, "sharded")
         self.tail = (0, tail_numel)
         self.owned_main = [owned_chunk(lo, hi, world, rank) for lo, hi in self.buckets]
         self.owned_tail = owned_chunk(0, tail_numel, world, rank)
