@@ -37,6 +37,8 @@ extern "C" {
 /* + vlp_cider_d / vlp_cider_d_workspace_bytes (the SCST reward on the device): purely additive as well. */
 /* + vlp_cider_d_df / vlp_cider_d_df_workspace_bytes (the same reward with document frequencies from a resident table): purely additive as
  * well. */
+/* + vlp_cider_d_multi / vlp_cider_d_multi_df with their workspace functions (2..16 hypotheses per group, leave-one-out reward) and
+ * vlp_sample_rows_rep (several draws per logits row, seed in device memory): they take the existing structs; purely additive as well. */
 /* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 
@@ -506,6 +508,14 @@ int vlp_vis_pe_prep(const vlp_vis_pe_prep_args* a, void* stream);
  * distribution is the same; logp[r*logp_stride] = log_softmax(logits[r])[ids[r]]. */
 int vlp_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, uint64_t seed, uint32_t rng_stream, int64_t* ids,
                     int64_t ids_stride, float* logp, int64_t logp_stride, void* stream);
+/* vlp_sample_rows with `rep` draws per logits row and the seed in device memory: draw r (of `rows`) reads logits row r / rep, its RNG row key
+ * is r (the rep draws of a logits row differ), the seed is *seed_cell + seed_add with seed_cell an 8-byte aligned device address read with a
+ * plain load -- so a launch whose seed changes from call to call has call-invariant arguments and can be replayed from a captured graph.
+ * ids2 (optional, NULL = none) receives the same id at ids2[r*ids2_stride].  With rep == 1, the same effective seed and rng_stream, ids and
+ * logp equal vlp_sample_rows' bit for bit (one shared kernel body). */
+int vlp_sample_rows_rep(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t rep, const uint64_t* seed_cell, uint64_t seed_add,
+                        uint32_t rng_stream, int64_t* ids, int64_t ids_stride, int64_t* ids2, int64_t ids2_stride, float* logp, int64_t logp_stride,
+                        void* stream);
 /* SCST scoring layout: the teacher-forced sequence whose training forward reproduces, for every sampled position, the hidden states of the
  * incremental decoder (replaces differentiating the decoder itself, modeling.py:1210-1251 under autograd in run_img2txt_dist.py:506-507).
  * With T sampled tokens y_0..y_{T-1} the scoring sequence has L' = in_len + 2T - 1 <= 256 slots:
@@ -730,6 +740,20 @@ typedef struct {
 } vlp_cider_d_df_args;
 int64_t vlp_cider_d_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
 int vlp_cider_d_df(const vlp_cider_d_df_args* a, void* stream);
+
+/* The two entries above for K = mult samples per image, 2 <= mult <= 16, with a leave-one-out baseline (self-critical training with several
+ * samples per image).  Same argument structs, same row layout (hypothesis row i belongs to group i % G), same kernels (the scoring block
+ * has 64 * mult threads), every other shape limit unchanged.  Scores are what the specifications above give for that mult: without a table
+ * df(g) = mult * the number of groups that hold g and ref_len = log(mult*G); with a table there is no mult factor.
+ *   - reward (optional) is [mult*G] in the row order of hyp: reward[k*G + g] = s[k*G + g] - (sum over j != k of s[j*G + g]) / (mult - 1),
+ *     the sum over the stored fp32 scores in ascending j starting from 0, then one divide and one subtract: a fixed order, bit-equal
+ *     repeats.  With mult == 2 reward[g] equals the two entries' above bit for bit and reward[G + g] == -reward[g].
+ * Nothing is written outside scores[0, mult*G), reward[0, mult*G) and the workspace; no atomics; two capturable launches.  The workspace
+ * sizes are the functions below (0 for a refused shape, mult == 1 included); vlp_cider_d / vlp_cider_d_df keep refusing mult > 2. */
+int64_t vlp_cider_d_multi_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
+int vlp_cider_d_multi(const vlp_cider_d_args* a, void* stream);
+int64_t vlp_cider_d_multi_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
+int vlp_cider_d_multi_df(const vlp_cider_d_df_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

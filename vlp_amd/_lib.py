@@ -219,6 +219,7 @@ SYMBOLS = {
     "vlp_mask_build": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
     "vlp_vis_pe_prep": (C.c_int, [C.POINTER(VisPePrepArgs), vp]),
     "vlp_sample_rows": (C.c_int, [vp, i64, i32, i32, C.c_uint64, C.c_uint32, vp, i64, vp, i64, vp]),
+    "vlp_sample_rows_rep": (C.c_int, [vp, i64, i32, i32, i32, vp, C.c_uint64, C.c_uint32, vp, i64, vp, i64, vp, i64, vp]),
     "vlp_argmax_rows": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp]),
     "vlp_mask_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "vlp_layernorm_fwd": (C.c_int, [C.POINTER(LayerNormFwdArgs), vp]),
@@ -252,6 +253,10 @@ SYMBOLS = {
     "vlp_cider_d": (C.c_int, [C.POINTER(CiderDArgs), vp]),
     "vlp_cider_d_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vlp_cider_d_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
+    "vlp_cider_d_multi_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "vlp_cider_d_multi": (C.c_int, [C.POINTER(CiderDArgs), vp]),
+    "vlp_cider_d_multi_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "vlp_cider_d_multi_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
     "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
@@ -610,6 +615,18 @@ def sample_rows(logits, ld, rows, V, seed, rng_stream, ids, logp):
     _check(load().vlp_sample_rows(ptr(logits), ld, rows, V, seed, rng_stream, ptr(ids), ids.stride(0), ptr(logp), logp.stride(0), stream_ptr()))
 
 
+def sample_rows_rep(logits, ld, rows, V, rep, seed_cell, seed_add, rng_stream, ids, logp, ids2=None):
+    """sample_rows with `rep` draws per logits row (draw r reads row r // rep, RNG row key r) and the seed *seed_cell + seed_add read on the
+    device: seed_cell is an int64 device tensor of one element holding the uint64 seed's bits.  ids2 (optional) receives the same ids."""
+    _req_cuda(logits, seed_cell, ids, logp, ids2)
+    if seed_cell.dtype not in (torch.int64, torch.uint64) or seed_cell.numel() < 1:
+        raise RuntimeError("vlp_amd.sample_rows_rep: seed_cell must be an int64 device tensor of one element")
+    if logits.numel() < ((rows + rep - 1) // rep - 1) * ld + V:
+        raise RuntimeError("vlp_amd.sample_rows_rep: logits are shorter than ceil(rows / rep) rows of pitch ld")
+    _check(load().vlp_sample_rows_rep(ptr(logits), ld, rows, V, rep, ptr(seed_cell), int(seed_add) & 0xFFFFFFFFFFFFFFFF, rng_stream, ptr(ids),
+                                      ids.stride(0), ptr(ids2), ids2.stride(0) if ids2 is not None else 0, ptr(logp), logp.stride(0), stream_ptr()))
+
+
 def mask_pack(mask_i64, out_u8, B, L, Lp, out_t=None):
     _req_cuda(mask_i64, out_u8, out_t)
     _check(load().vlp_mask_pack(ptr(mask_i64), ptr(out_u8), ptr(out_t), B, L, Lp, stream_ptr()))
@@ -742,8 +759,20 @@ def cider_d(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, workspace
     _check(load().vlp_cider_d(C.byref(a), stream_ptr()))
 
 
-def _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes):
-    """The operand checks and the argument struct cider_d and cider_d_df share."""
+def cider_d_multi_workspace_bytes(G, R, T, mult):
+    """0 for a shape vlp_cider_d_multi refuses (2 <= mult <= 16)."""
+    return int(load().vlp_cider_d_multi_workspace_bytes(G, R, T, mult))
+
+
+def cider_d_multi(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, workspace=None):
+    """cider_d for 2 <= mult <= 16 hypotheses per group with the leave-one-out reward (include/vlp_hip.h vlp_cider_d_multi): reward f32
+    [mult*G] or None, reward[k*G + g] = scores[k*G + g] - mean of the group's other scores.  workspace: cider_d_multi_workspace_bytes()."""
+    a = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, cider_d_multi_workspace_bytes, reward_rows=mult)
+    _check(load().vlp_cider_d_multi(C.byref(a), stream_ptr()))
+
+
+def _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes, reward_rows=1):
+    """The operand checks and the argument struct the cider_d entries share (reward_rows: the reward holds reward_rows * G elements)."""
     _req_cuda(hyp, ref, ref_count, scores, reward, workspace)
     if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
         raise RuntimeError("vlp_amd.cider_d: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
@@ -754,8 +783,8 @@ def _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, w
         raise RuntimeError("vlp_amd.cider_d: ref_count must be contiguous int32 [%d]" % G)
     if scores.dtype != torch.float32 or not scores.is_contiguous() or scores.numel() < mult * G:
         raise RuntimeError("vlp_amd.cider_d: scores must be contiguous f32 [%d]" % (mult * G))
-    if reward is not None and (reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() < G):
-        raise RuntimeError("vlp_amd.cider_d: reward must be contiguous f32 [%d]" % G)
+    if reward is not None and (reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() < reward_rows * G):
+        raise RuntimeError("vlp_amd.cider_d: reward must be contiguous f32 [%d]" % (reward_rows * G))
     if workspace is None:
         workspace = torch.empty(max(workspace_bytes(G, R, T, mult), 1), device=hyp.device, dtype=torch.uint8)
     a = CiderDArgs(ptr(hyp), hyp.stride(0), ptr(ref), ref.stride(0), ref.stride(1), ptr(ref_count), G, R, T, mult, sigma, ptr(scores), ptr(reward),
@@ -773,14 +802,33 @@ def cider_d_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, rewa
     """cider_d with document frequencies from a resident table (include/vlp_hip.h vlp_cider_d_df; vlp_amd.scst.DocFreq.to(device) makes the
     two tensors): df_keys int64 [N] holding the table's uint64 keys bit for bit (ascending as unsigned), df_vals int32 [N], n_docs the
     number of documents.  N = 0 is an empty table.  workspace: cider_d_df_workspace_bytes() bytes.  Everything else as cider_d."""
+    a = _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, cider_d_df_workspace_bytes, 1)
+    _check(load().vlp_cider_d_df(C.byref(a), stream_ptr()))
+
+
+def _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, workspace_bytes, reward_rows):
+    """The table checks and the argument struct cider_d_df and cider_d_multi_df share."""
     _req_cuda(df_keys, df_vals)
     if (df_keys.dtype not in (torch.int64, torch.uint64) or df_vals.dtype != torch.int32 or df_keys.dim() != 1 or df_vals.dim() != 1
             or not df_keys.is_contiguous() or not df_vals.is_contiguous() or df_keys.numel() != df_vals.numel()):
         raise RuntimeError("vlp_amd.cider_d_df: df_keys int64 [N] (the uint64 keys' bits) and df_vals int32 [N], contiguous")
-    s = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, cider_d_df_workspace_bytes)
+    s = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes, reward_rows=reward_rows)
     n = df_keys.numel()
     a = CiderDDfArgs(s, ptr(df_keys) if n else None, ptr(df_vals) if n else None, n, int(n_docs))
-    _check(load().vlp_cider_d_df(C.byref(a), stream_ptr()))
+    a._keep = s                              # (its workspace lives until the launch has been enqueued)
+    return a
+
+
+def cider_d_multi_df_workspace_bytes(G, R, T, mult):
+    """0 for a shape vlp_cider_d_multi_df refuses (2 <= mult <= 16)."""
+    return int(load().vlp_cider_d_multi_df_workspace_bytes(G, R, T, mult))
+
+
+def cider_d_multi_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward=None, sigma=6.0, workspace=None):
+    """cider_d_multi with document frequencies from a resident table (cider_d_df's table arguments); workspace:
+    cider_d_multi_df_workspace_bytes() bytes."""
+    a = _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, cider_d_multi_df_workspace_bytes, mult)
+    _check(load().vlp_cider_d_multi_df(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

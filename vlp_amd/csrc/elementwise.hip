@@ -1143,12 +1143,13 @@ extern "C" int vlp_kv_gather(const void* src, int64_t src_rows_per_batch, void* 
 // (This kernel keeps its hand-written passes and LDS trees: on row_visit / block_reduce_max / argmax_block256 its loops compile to the same
 // instructions, yet a launch at 64 rows measured 37.5 us against 36.1 us, and 38.8 us with the reduction words moved in LDS: a code-placement
 // effect that is not understood.  profiles/vocab_row_refactor_ab.txt)
-__global__ __launch_bounds__(256) void sample_rows_kernel(const f16* logits, int64_t ld, int V, DropCtx rng, int64_t* ids, int64_t ids_stride, float* logp,
-                                                          int64_t logp_stride) {
+// (sample_row_body is that kernel's body, inlined into both kernels below: the existing entry keeps its instruction stream.)
+// One block draws one id: `row` keys the RNG, x is the logits row it reads; ids2 (or NULL) receives the same id.
+DEVFN void sample_row_body(const f16* x, int V, const DropCtx& rng, int row, int64_t* ids, int64_t ids_stride, int64_t* ids2, int64_t ids2_stride,
+                           float* logp, int64_t logp_stride) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const f16* x = logits + (int64_t)row * ld;
+    const int tid = threadIdx.x;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) mx = fmaxf(mx, (float)x[v]);
     sv[tid] = mx;
@@ -1192,8 +1193,14 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const f16* logits, int
     }
     if (tid == 0) {
         ids[row * ids_stride] = si[0];
+        if (ids2) ids2[row * ids2_stride] = si[0];
         logp[row * logp_stride] = (float)x[si[0]] - lse;
     }
+}
+__global__ __launch_bounds__(256) void sample_rows_kernel(const f16* logits, int64_t ld, int V, DropCtx rng, int64_t* ids, int64_t ids_stride, float* logp,
+                                                          int64_t logp_stride) {
+    const int row = blockIdx.x;
+    sample_row_body(logits + (int64_t)row * ld, V, rng, row, ids, ids_stride, nullptr, 0, logp, logp_stride);
 }
 extern "C" int vlp_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, uint64_t seed, uint32_t rng_stream, int64_t* ids,
                                int64_t ids_stride, float* logp, int64_t logp_stride, void* stream) {
@@ -1202,6 +1209,34 @@ extern "C" int vlp_sample_rows(const void* logits, int64_t ld, int32_t rows, int
     DropCtx rng = make_drop(0.5f, seed, rng_stream);
     hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16*)logits, ld, V, rng, ids, ids_stride, logp, logp_stride);
     VLP_CHECK_LAUNCH("vlp_sample_rows");
+    return VLP_OK;
+}
+
+// vlp_sample_rows_rep: draw r reads logits row r / rep under the RNG row key r, and the seed is *seed_cell + seed_add, read on the device (a
+// plain load): the launch has the same arguments on every call, so a captured token step draws afresh.  The keys are make_drop's, computed
+// here (integer arithmetic only: the same bits).
+__global__ __launch_bounds__(256) void sample_rows_rep_kernel(const f16* logits, int64_t ld, int V, int rep, const uint64_t* seed_cell, uint64_t seed_add,
+                                                              uint32_t rng_stream, int64_t* ids, int64_t ids_stride, int64_t* ids2, int64_t ids2_stride,
+                                                              float* logp, int64_t logp_stride) {
+    const int row = blockIdx.x;
+    const uint64_t seed = *seed_cell + seed_add;
+    const uint64_t s = seed * 0x9E3779B97F4A7C15ull + (uint64_t)rng_stream * 0xD1B54A32D192ED03ull + 0x632BE59BD9B4E019ull;
+    DropCtx rng;
+    rng.k0 = (uint32_t)s;
+    rng.k1 = (uint32_t)(s >> 32) | 1u;
+    rng.thresh = 0u;                                  // (the draw reads the keys only)
+    rng.scale = 1.f;
+    sample_row_body(logits + (int64_t)(row / rep) * ld, V, rng, row, ids, ids_stride, ids2, ids2_stride, logp, logp_stride);
+}
+extern "C" int vlp_sample_rows_rep(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t rep, const uint64_t* seed_cell, uint64_t seed_add,
+                                   uint32_t rng_stream, int64_t* ids, int64_t ids_stride, int64_t* ids2, int64_t ids2_stride, float* logp,
+                                   int64_t logp_stride, void* stream) {
+    VLP_CHECK_ARG(logits && ids && logp && seed_cell && (uintptr_t)seed_cell % 8 == 0 && rows > 0 && V > 0 && ld >= V && rep >= 1,
+                  "vlp_sample_rows_rep: bad args");
+    VLP_ENTER(logits, "vlp_sample_rows_rep");
+    hipLaunchKernelGGL(sample_rows_rep_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (const f16*)logits, ld, V, rep, seed_cell, seed_add, rng_stream,
+                       ids, ids_stride, ids2, ids2_stride, logp, logp_stride);
+    VLP_CHECK_LAUNCH("vlp_sample_rows_rep");
     return VLP_OK;
 }
 

@@ -16,6 +16,9 @@
 //   cider_score_kernel   one block per group, one wave per hypothesis, one lane per position: tf of the hypothesis' n-grams in each
 //                        valid reference of its group, the clipped dot products, norms, length penalty, mean; then the reward.
 //
+// vlp_cider_d_multi / vlp_cider_d_multi_df are the same two kernels with 2..16 hypotheses per group (64 * mult threads in the scoring block) and
+// the leave-one-out reward: every hypothesis against the mean of the group's other scores.
+//
 // vlp_cider_d_df takes df from a resident table (sorted uint64 keys, int32 df; vlp_amd/scst.py DocFreq) instead of the call's references.
 // Both kernels are the ones above with TABLE = true: the counting pass drops its loop over the groups -- every (position, order) of the
 // block's string gets a lane of its own that packs the n-gram's key and looks it up (a lower-bound binary search of dependent global loads:
@@ -213,11 +216,13 @@ __global__ __launch_bounds__(CD_THREADS) void cider_count_kernel(vlp_cider_d_arg
 }
 
 // TABLE: idf of each hypothesis position and order comes from idf_in (the counting pass wrote it), not from the packed group count.
+// LOO: reward [mult*G] = each score minus the mean of the group's other scores, else reward [G] = scores[g] - scores[G + g] (mult == 2).
+#define CD_MAX_MULT 16
 template <bool TABLE>
-__global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const float* norms, const float* idf_in) {
+__global__ __launch_bounds__(64 * CD_MAX_MULT) void cider_score_kernel(vlp_cider_d_args a, const int* info, const float* norms, const float* idf_in, int loo) {
     extern __shared__ __attribute__((aligned(16))) int cd_refs[];      // [R][T + CD_PAD]
     __shared__ int ref_len_s[8];
-    __shared__ float sc[2];
+    __shared__ float sc[CD_MAX_MULT];
     const int T = a.T, R = a.R, G = a.G, ldr = T + CD_PAD, SH = a.mult * G;
     const int g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, h = w * G + g;
     cd_stage_refs(a, g * R, R, cd_refs, ref_len_s, 64, blockDim.x);
@@ -274,9 +279,19 @@ __global__ void cider_score_kernel(vlp_cider_d_args a, const int* info, const fl
         a.scores[h] = score;
         sc[w] = score;
     }
-    if (a.reward) {                                                    // mult == 2 (checked by the entry): sample - greedy
+    if (a.reward) {
         __syncthreads();
-        if (threadIdx.x == 0) a.reward[g] = sc[0] - sc[1];
+        if (loo) {                                                     // lane k: hypothesis k of the group against the others, ascending j
+            const int k = threadIdx.x;
+            if (k < a.mult) {
+                float others = 0.f;
+                for (int j = 0; j < a.mult; ++j)
+                    if (j != k) others += sc[j];
+                a.reward[(int64_t)k * G + g] = sc[k] - others / (float)(a.mult - 1);
+            }
+        } else if (threadIdx.x == 0) {                                 // mult == 2 (checked by the entry): sample - greedy
+            a.reward[g] = sc[0] - sc[1];
+        }
     }
 }
 
@@ -286,35 +301,39 @@ static int cd_pow2_at_least(int T) {
     return P;
 }
 
-static bool cd_shape_ok(int32_t G, int32_t R, int32_t T, int32_t mult) {
-    return T >= 1 && T <= 64 && R >= 1 && R <= 8 && G >= 1 && G <= 1024 && (mult == 1 || mult == 2);
+// multi: the vlp_cider_d_multi* entries (2..CD_MAX_MULT hypotheses per group), else vlp_cider_d / vlp_cider_d_df (1 or 2)
+static bool cd_shape_ok(int32_t G, int32_t R, int32_t T, int32_t mult, bool multi = false) {
+    return T >= 1 && T <= 64 && R >= 1 && R <= 8 && G >= 1 && G <= 1024 && (multi ? (mult >= 2 && mult <= CD_MAX_MULT) : (mult == 1 || mult == 2));
 }
 // workspace: int32 info[mult*G][4][T] (df groups, tf, first per hypothesis position and order), then f32 norms[mult*G + G*R][4]
 static int64_t cd_info_ints(int32_t G, int32_t T, int32_t mult) { return (int64_t)mult * G * 4 * T; }
 
-extern "C" int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
-    if (!cd_shape_ok(G, R, T, mult)) return 0;
-    const int64_t bytes = 4 * (cd_info_ints(G, T, mult) + 4 * ((int64_t)mult * G + (int64_t)G * R));
+static int64_t cd_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult, bool table) {
+    const int64_t bytes = 4 * ((table ? 2 : 1) * cd_info_ints(G, T, mult) + 4 * ((int64_t)mult * G + (int64_t)G * R));
     return (bytes + 255) / 256 * 256;
 }
+extern "C" int64_t vlp_cider_d_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    return cd_shape_ok(G, R, T, mult) ? cd_workspace_bytes(G, R, T, mult, false) : 0;
+}
+extern "C" int64_t vlp_cider_d_multi_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    return cd_shape_ok(G, R, T, mult, true) ? cd_workspace_bytes(G, R, T, mult, false) : 0;
+}
 
-// the operand checks both entry points share; `need` is the entry's own workspace size
-#define CD_CHECK_ARGS(a, who, need)                                                                                                              \
-    VLP_CHECK_ARG(cd_shape_ok((a)->G, (a)->R, (a)->T, (a)->mult), who ": needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult 1 or 2 (G %d, R %d, T %d, mult %d)", \
-                  (a)->G, (a)->R, (a)->T, (a)->mult);                                                                                            \
+// the operand checks the entry points share; `need` is the entry's own workspace size, `multi` as in cd_shape_ok
+#define CD_CHECK_ARGS(a, who, need, multi)                                                                                                       \
+    VLP_CHECK_ARG(cd_shape_ok((a)->G, (a)->R, (a)->T, (a)->mult, multi), who ": needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, mult %s (G %d, R %d, T %d, mult %d)", \
+                  (multi) ? "in 2..16" : "1 or 2", (a)->G, (a)->R, (a)->T, (a)->mult);                                                          \
     VLP_CHECK_ARG((a)->hyp && (a)->ref && (a)->scores && (a)->workspace, who ": null operand");                                                  \
-    VLP_CHECK_ARG(!(a)->reward || (a)->mult == 2, who ": reward = scores[g] - scores[G + g] needs mult == 2");                                   \
+    VLP_CHECK_ARG((multi) || !(a)->reward || (a)->mult == 2, who ": reward = scores[g] - scores[G + g] needs mult == 2");                        \
     VLP_CHECK_ARG((a)->hyp_ld >= (a)->T && (a)->ref_ld >= (a)->T && (a)->ref_group_stride >= (int64_t)((a)->R - 1) * (a)->ref_ld + (a)->T,       \
                   who ": strides shorter than the rows");                                                                                        \
     VLP_CHECK_ARG((a)->sigma > 0.f, who ": sigma must be positive");                                                                             \
     VLP_CHECK_ARG((a)->workspace_bytes >= (need) && (uintptr_t)(a)->workspace % 16 == 0, who ": workspace of %lld bytes, needs %lld (16-byte aligned)", \
                   (long long)(a)->workspace_bytes, (long long)(need))
 
-extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
-    VLP_CHECK_ARG(a, "vlp_cider_d: null args");
-    const int64_t need = vlp_cider_d_workspace_bytes(a->G, a->R, a->T, a->mult);
-    CD_CHECK_ARGS(a, "vlp_cider_d", need);
-    VLP_ENTER(a->ref, "vlp_cider_d");
+// the two launches of vlp_cider_d and vlp_cider_d_multi (`who` names the entry in messages; args checked by the caller)
+static int cd_run(const vlp_cider_d_args* a, void* stream, bool multi, const char* who) {
+    VLP_ENTER(a->ref, who);
     const int SH = a->mult * a->G, SR = a->G * a->R, ldr = a->T + CD_PAD;
     const int P = cd_pow2_at_least(a->T);
     int tile_groups = CD_TILE_INTS / (a->R * ldr);                     // >= 15 at the largest accepted R, T
@@ -323,39 +342,71 @@ extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
     float* norms = (float*)(info + cd_info_ints(a->G, a->T, a->mult));
     hipLaunchKernelGGL(cider_count_kernel<false>, dim3(SH + SR), dim3(CD_THREADS), (size_t)tile_groups * a->R * ldr * sizeof(int), (hipStream_t)stream, *a, P,
                        tile_groups, info, norms, cd_table{}, (float*)nullptr);
-    VLP_CHECK_LAUNCH("vlp_cider_d (count)");
+    VLP_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(cider_score_kernel<false>, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
-                       (const float*)norms, (const float*)nullptr);
-    VLP_CHECK_LAUNCH("vlp_cider_d (score)");
+                       (const float*)norms, (const float*)nullptr, multi ? 1 : 0);
+    VLP_CHECK_LAUNCH(who);
     return VLP_OK;
+}
+
+extern "C" int vlp_cider_d(const vlp_cider_d_args* a, void* stream) {
+    VLP_CHECK_ARG(a, "vlp_cider_d: null args");
+    const int64_t need = vlp_cider_d_workspace_bytes(a->G, a->R, a->T, a->mult);
+    CD_CHECK_ARGS(a, "vlp_cider_d", need, false);
+    return cd_run(a, stream, false, "vlp_cider_d");
+}
+
+extern "C" int vlp_cider_d_multi(const vlp_cider_d_args* a, void* stream) {
+    VLP_CHECK_ARG(a, "vlp_cider_d_multi: null args");
+    const int64_t need = vlp_cider_d_multi_workspace_bytes(a->G, a->R, a->T, a->mult);
+    CD_CHECK_ARGS(a, "vlp_cider_d_multi", need, true);
+    return cd_run(a, stream, true, "vlp_cider_d_multi");
 }
 
 // workspace: int32 info[mult*G][4][T] (tf, first), f32 idf[mult*G][4][T], then f32 norms[mult*G + G*R][4]
 extern "C" int64_t vlp_cider_d_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
-    if (!cd_shape_ok(G, R, T, mult)) return 0;
-    const int64_t bytes = 4 * (2 * cd_info_ints(G, T, mult) + 4 * ((int64_t)mult * G + (int64_t)G * R));
-    return (bytes + 255) / 256 * 256;
+    return cd_shape_ok(G, R, T, mult) ? cd_workspace_bytes(G, R, T, mult, true) : 0;
+}
+extern "C" int64_t vlp_cider_d_multi_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult) {
+    return cd_shape_ok(G, R, T, mult, true) ? cd_workspace_bytes(G, R, T, mult, true) : 0;
 }
 
-extern "C" int vlp_cider_d_df(const vlp_cider_d_df_args* d, void* stream) {
-    VLP_CHECK_ARG(d, "vlp_cider_d_df: null args");
+#define CD_CHECK_TABLE(d, who)                                                                                                                   \
+    VLP_CHECK_ARG((d)->df_n >= 0 && (d)->n_docs >= 1 && (d)->n_docs <= (1 << 24), who ": needs df_n >= 0 and 1 <= n_docs <= 2^24 (df_n %lld, n_docs %lld)", \
+                  (long long)(d)->df_n, (long long)(d)->n_docs);                                                                                 \
+    VLP_CHECK_ARG((d)->df_n == 0 || ((d)->df_keys && (d)->df_vals && (uintptr_t)(d)->df_keys % 8 == 0 && (uintptr_t)(d)->df_vals % 4 == 0),      \
+                  who ": a table of %lld keys needs non-null df_keys (8-byte aligned) and df_vals (4-byte aligned)", (long long)(d)->df_n)
+
+static int cd_run_df(const vlp_cider_d_df_args* d, void* stream, bool multi, const char* who) {
     const vlp_cider_d_args* a = &d->s;
-    const int64_t need = vlp_cider_d_df_workspace_bytes(a->G, a->R, a->T, a->mult);
-    CD_CHECK_ARGS(a, "vlp_cider_d_df", need);
-    VLP_CHECK_ARG(d->df_n >= 0 && d->n_docs >= 1 && d->n_docs <= (1 << 24), "vlp_cider_d_df: needs df_n >= 0 and 1 <= n_docs <= 2^24 (df_n %lld, n_docs %lld)",
-                  (long long)d->df_n, (long long)d->n_docs);
-    VLP_CHECK_ARG(d->df_n == 0 || (d->df_keys && d->df_vals && (uintptr_t)d->df_keys % 8 == 0 && (uintptr_t)d->df_vals % 4 == 0),
-                  "vlp_cider_d_df: a table of %lld keys needs non-null df_keys (8-byte aligned) and df_vals (4-byte aligned)", (long long)d->df_n);
-    VLP_ENTER(a->ref, "vlp_cider_d_df");
+    VLP_ENTER(a->ref, who);
     const int SH = a->mult * a->G, SR = a->G * a->R, ldr = a->T + CD_PAD;
     int* info = (int*)a->workspace;
     float* idf = (float*)(info + cd_info_ints(a->G, a->T, a->mult));
     float* norms = idf + cd_info_ints(a->G, a->T, a->mult);
     const cd_table tab = {d->df_keys, d->df_vals, d->df_n, (float)d->n_docs};
     hipLaunchKernelGGL(cider_count_kernel<true>, dim3(SH + SR), dim3(CD_THREADS), 0, (hipStream_t)stream, *a, 64, 0, info, norms, tab, idf);
-    VLP_CHECK_LAUNCH("vlp_cider_d_df (count)");
+    VLP_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(cider_score_kernel<true>, dim3(a->G), dim3(64 * a->mult), (size_t)a->R * ldr * sizeof(int), (hipStream_t)stream, *a, (const int*)info,
-                       (const float*)norms, (const float*)idf);
-    VLP_CHECK_LAUNCH("vlp_cider_d_df (score)");
+                       (const float*)norms, (const float*)idf, multi ? 1 : 0);
+    VLP_CHECK_LAUNCH(who);
     return VLP_OK;
+}
+
+extern "C" int vlp_cider_d_df(const vlp_cider_d_df_args* d, void* stream) {
+    VLP_CHECK_ARG(d, "vlp_cider_d_df: null args");
+    const vlp_cider_d_args* a = &d->s;
+    const int64_t need = vlp_cider_d_df_workspace_bytes(a->G, a->R, a->T, a->mult);
+    CD_CHECK_ARGS(a, "vlp_cider_d_df", need, false);
+    CD_CHECK_TABLE(d, "vlp_cider_d_df");
+    return cd_run_df(d, stream, false, "vlp_cider_d_df");
+}
+
+extern "C" int vlp_cider_d_multi_df(const vlp_cider_d_df_args* d, void* stream) {
+    VLP_CHECK_ARG(d, "vlp_cider_d_multi_df: null args");
+    const vlp_cider_d_args* a = &d->s;
+    const int64_t need = vlp_cider_d_multi_df_workspace_bytes(a->G, a->R, a->T, a->mult);
+    CD_CHECK_ARGS(a, "vlp_cider_d_multi_df", need, true);
+    CD_CHECK_TABLE(d, "vlp_cider_d_multi_df");
+    return cd_run_df(d, stream, true, "vlp_cider_d_multi_df");
 }

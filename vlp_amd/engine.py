@@ -113,6 +113,7 @@ class Engine(object):
         self.packed = False
         self.gen = 0
         self.step_seed = 0
+        self._warned_group_unfused = False        # decode_sample_group beyond 512 sequences: said once
         self.base_seed = 0x5EED
         self.grads_dirty = False          # False -> next backward overwrites (beta = 0), True -> accumulates
         self.grad_ready_hook = None       # callable(bucket_index) set by the DDP wrapper
@@ -912,8 +913,9 @@ class Engine(object):
     # ------------------------------------------------------------------------------------------
     # incremental greedy decoding with a K/V cache (modeling.py:1189-1253, :856-875, :386-394)
     # ------------------------------------------------------------------------------------------
-    def _decode_workspace(self, B, T0, Lcap, Kb=1):
-        key = ("dec", B, T0, Lcap, Kb)
+    def _decode_workspace(self, B, T0, Lcap, Kb=1, group=False):
+        """group: Kb samples per image that never permute (decode_sample_group) instead of Kb beams."""
+        key = ("dec", B, T0, Lcap, Kb) + (("group",) if group else ())
         ws = self._ws.get(key)
         if ws is not None:
             return ws
@@ -945,7 +947,13 @@ class Engine(object):
                   slab=f(self.DEC_SPLITS, R * 2, H),      # fp32 split-K partial sums of the token-step out-projection / FFN-down (vlp_dec_gemm -> vlp_dec_reduce_ln)
                   sk_ws=torch.empty(K.gemm_nt_splitk_workspace_bytes(min(M, 1024), max(I, 3 * H), max(tuning.SKINNY_SPLITS)), device=dev,
                                     dtype=torch.uint8))
-        if Kb > 1:
+        if group:
+            # one cache per row for the generated positions (the prefix stays in `kv`, once per image), the outputs of all R rows, and the
+            # device cell the sampling launches read their seed from (uint64 bits)
+            ws.update(out_ids=i64(R, Lcap), out_val=f(R, Lcap), seed_cell=torch.zeros(1, device=dev, dtype=torch.long))
+            if Kb > 1:
+                ws.update(kvS=[h(R, Lcap, 2 * H) for _ in range(NL)])
+        elif Kb > 1:
             # beams: two caches per layer (select_beam_items permutes rows: gather from one into the other, then swap)
             ws.update(kvA=[h(R, Lcap, 2 * H) for _ in range(NL)], kvB=[h(R, Lcap, 2 * H) for _ in range(NL)],
                       kk_s=f(R, Kb), kk_i=i64(R, Kb), src_rows=i64(R), tot=f(Lcap, B, Kb), wids=i64(Lcap, B, Kb), ptrs=i64(Lcap, B, Kb),
@@ -1181,11 +1189,72 @@ class Engine(object):
                                         B, 2, st, False)
                 pick(s)
             if sample:
-                step()                       # the seed changes every step: not plannable
+                step()                       # the seed is a launch argument here and changes every step: not plannable (decode_sample_group
+                                             # reads it from a device cell and is)
             else:
                 self._run_planned(ws, ("greedy", s), step)
         ws["calls"] += 1
         return out_ids[:, :n_steps].clone(), out_val[:, :n_steps].clone()
+
+    def decode_sample_group(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, n_samples):
+        """K = n_samples sampled captions per image (self-critical training with a leave-one-out baseline).  Step 0 runs the B prefixes as in
+        decode_beam and draws K first tokens from each of the B logits rows; steps s >= 1 decode R = B*K rows against the per-image prefix
+        cache, each row with a cache of its own for the generated positions -- rows never permute, so nothing is gathered.  The seed of
+        step s is base_seed + step_seed + 1 + s (decode_greedy(sample=True)'s sequence), read by the sampling launches from a device cell
+        the host sets once per call: every launch of a token step has call-invariant arguments and the steps are captured / replayed
+        (_run_planned).  Returns (ids [K*B, n] int64, logp [K*B, n] f32) sample-major: row k*B + b is sample k of image b."""
+        self.pack()
+        self.wait_params()
+        V = self._model().config.vocab_size
+        Ks = int(n_samples)
+        B, in_len, out_len = self._decode_check(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask)
+        if Ks < 1 or Ks > 16:
+            raise RuntimeError("vlp_amd: decode_sample_group draws 1..16 samples per image (got %d)" % Ks)
+        n_steps, T0 = out_len - in_len, in_len + 1
+        R = B * Ks
+        if R > 1024:
+            raise RuntimeError("vlp_amd: %d samples of %d images are %d sequences; the sampled decode takes at most 1024" % (Ks, B, R))
+        if R > 512 and not self._warned_group_unfused:
+            self._warned_group_unfused = True
+            import warnings
+            warnings.warn("vlp_amd: %d sequences in a sampled decode: the fused token step takes at most 512 (1024 rows), the decode runs on the "
+                          "unfused path" % R, VlpPerformanceWarning)
+        ws = self._decode_workspace(B, T0, out_len, Ks, group=True)
+        dev = self.device
+        attention_mask = attention_mask.to(torch.long)
+        if attention_mask.stride(2) != 1:
+            attention_mask = attention_mask.contiguous()
+        token_type_ids, position_ids = token_type_ids.to(torch.long), position_ids.to(torch.long)
+        self._decode_regions(ws, vis_feats, vis_pe)
+        self._decode_static_inputs(ws, token_type_ids, position_ids, attention_mask, in_len, out_len, Ks)
+        out_ids, out_val, am, cell = ws["out_ids"], ws["out_val"], ws["mask_static"], ws["seed_cell"]
+        x_first = torch.cat((input_ids.to(torch.long), torch.full((B, 1), int(mask_word_id), device=dev, dtype=torch.long)), dim=1).contiguous()
+        ws["xids"][:, 1] = int(mask_word_id)
+        seed = (self.base_seed + self.step_seed + 1) & 0xFFFFFFFFFFFFFFFF
+        cell.fill_(seed - (1 << 64) if seed >= (1 << 63) else seed)            # the uint64's bits in an int64 cell
+        self.step_seed += n_steps
+        # one sample per image: the rows are the images, their cache is `kv` itself (decode_greedy's launches)
+        caches, prefix = (ws["kvS"], (ws["kv"], in_len, Ks)) if Ks > 1 else (ws["kv"], None)
+
+        def pick(s, rep):
+            K.sample_rows_rep(ws["logits"], ws["Vp"], R, V, rep, cell, s, 7001, out_ids[:, s], out_val[:, s], ids2=ws["xids"][:, 0])
+
+        self._decode_model_step(ws, ws["kv"], out_len, x_first, token_type_ids[:, :T0].contiguous(), position_ids[:, :T0].contiguous(),
+                                attention_mask[:, :T0, :T0], B, T0, 0, True)
+        pick(0, Ks)
+        for s in range(1, n_steps):
+            st = in_len + s - 1
+
+            def step(s=s, st=st):
+                self._decode_model_step(ws, caches, out_len, ws["xids"], ws["tt_steps"][s], ws["pid_steps"][s], am[:, st:st + 2, :st + 2], R, 2, st,
+                                        False, prefix=prefix)
+                pick(s, 1)
+            self._run_planned(ws, ("sample_group", s), step)
+        ws["calls"] += 1
+
+        def sample_major(t):             # decode row b*K + k -> row k*B + b, one permuted copy
+            return t[:, :n_steps].view(B, Ks, n_steps).transpose(0, 1).reshape(R, n_steps)
+        return sample_major(out_ids), sample_major(out_val)
 
     NGRAM_MAX_FRAMES = 256       # csrc/elementwise.hip: NGRAM_MAX_FRAMES frames per hypothesis (and <= TOPK_LIST_MAX = 1024 ids per list)
 

@@ -628,11 +628,34 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     def engine(self):
         return self.__dict__["_engine"]
 
-    def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy"):
+    def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy",
+                n_samples=1):
         """Returns (output_ids [B, n], output_probs [B, n]) with n = token_type_ids.shape[1] - input_ids.shape[1], as :1253.
-        output_probs are the maximal prediction scores (logits), exactly what the reference returns in greedy mode (:1228)."""
+        output_probs are the maximal prediction scores (logits), exactly what the reference returns in greedy mode (:1228).
+        n_samples = K > 1 with sample_mode='sample' (not in the reference): K draws per image, returned sample-major as [K*B, n] ids and
+        log-probabilities (row k*B + b is sample k of image b; Engine.decode_sample_group); in train() mode with gradients enabled the
+        log-probabilities are differentiable, scored as K*B independent sequences."""
         if not input_ids.is_cuda:
             raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only (inputs must be on the GPU); there is no CPU path")
+        n_samples = int(n_samples)
+        if n_samples != 1:
+            if n_samples < 1 or sample_mode != "sample":
+                raise ValueError("n_samples=%d needs sample_mode='sample' and n_samples >= 1" % n_samples)
+            if self.search_beam_size > 1:
+                raise ValueError("n_samples=%d with search_beam_size=%d: several samples per image are drawn, not searched" %
+                                 (n_samples, self.search_beam_size))
+            eng = self.engine
+            with torch.no_grad():
+                ids, logp = eng.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
+                                                    n_samples)
+            if not (self.training and torch.is_grad_enabled()):
+                return ids, logp
+
+            def tiled(t):                    # row k*B + b of the scoring batch is image b
+                return t.repeat(n_samples, *([1] * (t.dim() - 1)))
+            st, logp = eng.score_samples(tiled(vis_feats), tiled(vis_pe), tiled(input_ids), tiled(token_type_ids), tiled(position_ids),
+                                         tiled(attention_mask), ids, self.mask_word_id)
+            return ids, _LogprobFn.apply(eng._anchor, logp, eng, st)
         if self.search_beam_size > 1:
             with torch.no_grad():
                 return self.beam_search(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=task_idx)

@@ -151,6 +151,11 @@ def build_parser():
                         "sample.  'image' scores against up to 5 captions of the sample's image (all of COCO's), which is how CIDEr is defined -- a "
                         "deliberate departure from the reference's objective; needs --packed_features (the loader collects the captions per "
                         "image id from --token_file)")
+    p.add_argument("--scst_samples", type=int, default=1, metavar="K",
+                   help="--scst: samples drawn per image.  1 is the reference's estimator: one sample against a greedy decode.  K in 2..16 draws K "
+                        "samples per image and baselines each with the mean reward of the other K - 1 (leave-one-out): no greedy decode, lower "
+                        "variance -- a deliberate departure from the reference's estimator.  --train_batch_size stays the number of images per "
+                        "step; K x that many sequences (at most 1024) are decoded and scored")
     p.add_argument("--scst_df", default="batch", metavar="{batch,train,PATH}",
                    help="--scst: the document frequencies of the CIDEr-D reward.  'batch' is the reference's Cider(df='corpus'): counted over the "
                         "references of each step.  'train' counts them once at start-up over ALL captions of --token_file, one document per image "
@@ -179,6 +184,15 @@ def derive_args(args):
         assert args.max_pred == 0 and args.mask_prob == 0, "no mask for scst!"
     if args.scst_refs == "image" and not (args.scst and args.packed_features):
         raise ValueError("--scst_refs image needs --scst and --packed_features (the captions of an image come from the packed loader)")
+    if not 1 <= args.scst_samples <= 16:
+        raise ValueError("--scst_samples %d: 1 (the reference's estimator) or 2..16 samples per image" % args.scst_samples)
+    if args.scst_samples > 1:
+        if not args.scst:
+            raise ValueError("--scst_samples %d needs --scst (it chooses the estimator of self-critical training)" % args.scst_samples)
+        per_step = args.train_batch_size // max(args.gradient_accumulation_steps, 1)
+        if args.scst_samples * per_step > 1024:
+            raise ValueError("--scst_samples %d x %d images per step = %d sequences; the sampled decode takes at most 1024: lower --train_batch_size "
+                             "or --scst_samples, or raise --gradient_accumulation_steps" % (args.scst_samples, per_step, args.scst_samples * per_step))
     if args.scst_df != "batch":
         if not args.scst:
             raise ValueError("--scst_df %s needs --scst (it chooses the document frequencies of the SCST reward)" % args.scst_df)
@@ -336,7 +350,8 @@ def scst_doc_freq(args):
     return table
 
 
-def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host", df=None):
+def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host", df=None,
+              samples=1):
     """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
     train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
     baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
@@ -345,11 +360,15 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     reward_on="device" (--scst_reward device) computes the reward with vlp_amd.scst.self_critical_reward_device instead: nothing leaves the
     device between the sampled decode and the backward, and the phase is marked "reward_device".  A batch whose 12th element is a CaptionRefs
     (--scst_refs image) is scored against those references, on either side, instead of its own ground-truth ids.  df (--scst_df): a
-    vlp_amd.scst.DocFreq whose document frequencies the reward uses, on either side, instead of the step's own references'; None = those."""
+    vlp_amd.scst.DocFreq whose document frequencies the reward uses, on either side, instead of the step's own references'; None = those.
+    samples=K >= 2 (--scst_samples): K samples per image, each baselined by the mean score of the image's other K - 1
+    (self_critical_reward_group / _group_device).  There is no greedy decode and no "greedy_decode" phase; the log-probabilities, the reward
+    and RewardCriterion run over the K*B rows (row k*B + b is sample k of image b)."""
     if mark is None:
         def mark(phase):
             pass
-    from .scst import clean_captions, self_critical_reward, self_critical_reward_device, self_critical_reward_refs
+    from .scst import (clean_captions, self_critical_reward, self_critical_reward_device, self_critical_reward_refs, self_critical_reward_group,
+                       self_critical_reward_group_device)
     (input_ids, segment_ids, input_mask, lm_label_ids, masked_pos, masked_weights, is_next, task_idx, img, vis_masked_pos, vis_pe,
      ans_labels) = batch
     L = input_ids.shape[1]
@@ -357,22 +376,40 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
         input_mask = input_mask.dense(L)                  # the decoder reads the dense [B, L, L] mask
     position_ids = torch.arange(L, dtype=input_ids.dtype, device=input_ids.device).unsqueeze(0).expand_as(input_ids)
     input_dummy = input_ids[:, :len_vis_input + 2]        # +2 for [CLS] and [SEP]
-    model.eval()
-    with torch.no_grad():
-        greedy_raw, _ = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="greedy")
-    mark("greedy_decode")
-    model.train()
-    gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample")
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("scst_step: samples must be >= 1 (got %d)" % samples)
+    if samples == 1:
+        model.eval()
+        with torch.no_grad():
+            greedy_raw, _ = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="greedy")
+        mark("greedy_decode")
+        model.train()
+        gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample")
+    else:
+        model.train()
+        gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample",
+                                         n_samples=samples)
     mark("sample_forward")
-    greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gt_ids = input_ids[:, len_vis_input + 2:]
     kw = {} if df is None else {"df": df}
-    if reward_on == "device":
+    if samples > 1:
+        refs = ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids
+        if reward_on == "device":
+            reward, _ = self_critical_reward_group_device(gen_result, refs, samples, **kw)
+        else:
+            reward, _ = self_critical_reward_group(gen_result, refs, samples, **kw)
+            reward = torch.from_numpy(reward).float().to(gen_result.device)
+        mean_reward = reward.mean()
+        mark("reward_device" if reward_on == "device" else "reward_host")
+    elif reward_on == "device":
+        greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
         reward, _ = self_critical_reward_device(greedy_res, ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids, gen_result, **kw)
         mean_reward = reward.mean()
         mark("reward_device")
     else:
+        greedy_res = clean_captions(greedy_raw, synthetic.SEP_ID, synthetic.PAD_ID)
         if isinstance(ans_labels, CaptionRefs):
             reward, _ = self_critical_reward_refs(greedy_res, ans_labels, gen_result, **kw)
         else:
@@ -522,7 +559,8 @@ def main(argv=None):
             lr = args.learning_rate * warmup_linear(global_step / t_total, args.warmup_proportion)
             if args.scst:
                 loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
-                                         accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward, df=scst_df)
+                                         accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward, df=scst_df,
+                                         samples=args.scst_samples)
                 rewards.append(mean_r.detach())
             else:
                 lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,

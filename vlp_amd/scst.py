@@ -368,3 +368,78 @@ def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, w
         keys, vals = df.to(hyp.device)
         K.cider_d_df(hyp, ids, count, 2, scores, keys, vals, df.n_docs, reward=diff, sigma=_table_scorer(df).sigma, workspace=workspace)
     return diff.unsqueeze(1).expand(B, T), scores
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# K samples per image with a leave-one-out baseline (--scst_samples K).  A deliberate departure from the reference's estimator (one sample
+# against a greedy decode): every sample is baselined by the mean score of the image's other K - 1 samples, so no greedy decode is needed.
+# Rows are sample-major: row k*B + b is sample k of image b (the reward kernels' `i % G`).
+# ------------------------------------------------------------------------------------------------------------------------------------------
+MAX_SAMPLES = 16
+
+
+def _check_samples(n_rows, n_samples):
+    n_samples = int(n_samples)
+    if not 2 <= n_samples <= MAX_SAMPLES:
+        raise ValueError("the leave-one-out reward needs 2..%d samples per image (got %d)" % (MAX_SAMPLES, n_samples))
+    if n_rows % n_samples:
+        raise ValueError("%d rows are not %d samples of every image" % (n_rows, n_samples))
+    return n_samples, n_rows // n_samples
+
+
+def self_critical_reward_group(gen_result, refs, n_samples, df=None):
+    """The leave-one-out reward of K = n_samples samples per image, on the host with CiderD in fp64: the specification of
+    self_critical_reward_group_device and the `--scst_reward host` path.  gen_result [K*B, T] ids, row k*B + b = sample k of image b; refs
+    the [B, T] ground-truth ids or a CaptionRefs (image b is scored against its first count[b] rows).  The K*B hypotheses each list their
+    image's references, which is what coco-caption's Cider(df='corpus') sees: df counts every image K times and ref_len = log(K*B); a
+    DocFreq `df` replaces both, without a K anywhere.  reward[k*B + b] = s[k*B + b] - (sum of s[j*B + b] over j != k, ascending j) / (K - 1).
+    Returns (reward [K*B, T] float64 ndarray -- the [K*B] rewards repeated over the columns --, scores [K*B])."""
+    def host(x):
+        return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    from .input_prep import CaptionRefs
+    gen_result = host(gen_result)
+    K, B = _check_samples(len(gen_result), n_samples)
+    if isinstance(refs, CaptionRefs):
+        ids, count = host(refs.ids), host(refs.count)
+        R = ids.shape[1]
+        gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
+    else:
+        gt_s = [[array_to_str(r)] for r in host(refs)[:B].tolist()]
+    res, gts = OrderedDict(), OrderedDict()
+    for i, row in enumerate(gen_result.tolist()):
+        res[i], gts[i] = [array_to_str(row)], gt_s[i % B]
+    _, scores = _table_scorer(df).compute_score(gts, res)
+    s = np.asarray(scores, dtype=np.float64).reshape(K, B)
+    reward = np.empty_like(s)
+    for k in range(K):
+        others = np.zeros(B)
+        for j in range(K):
+            if j != k:
+                others = others + s[j]
+        reward[k] = s[k] - others / (K - 1)
+    return np.repeat(reward.reshape(-1)[:, np.newaxis], gen_result.shape[1], 1), scores
+
+
+def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=None, workspace=None, df=None):
+    """self_critical_reward_group on the device (vlp_cider_d_multi / vlp_cider_d_multi_df, csrc/reward.hip): gen_result int64 [K*B, T] on the
+    GPU, refs the [B, T] ground-truth ids or a CaptionRefs of the same T.  Returns (reward f32 [K*B, T] -- expanded over the columns --,
+    scores f32 [K*B]) as device tensors; scores_out (f32 [K*B]) receives the scores when given; workspace: the caller's kernel scratch
+    (_lib.cider_d_multi_workspace_bytes(B, R, T, K) or ..._multi_df_... bytes, uint8), else allocated per call.  No device -> host transfer,
+    no synchronisation: two launches on the current stream, capturable.  df: as in self_critical_reward_device."""
+    from . import _lib as K_
+    from .input_prep import CaptionRefs
+    KB, T = gen_result.shape
+    K, B = _check_samples(KB, n_samples)
+    if isinstance(refs, CaptionRefs):
+        refs.check(B, T)
+    ids, count = _refs_parts(refs, B)
+    if ids.shape[0] != B or ids.shape[2] != T:
+        raise RuntimeError("self_critical_reward_group_device: %d samples of %d images need references [%d, R, %d]" % (K, B, B, T))
+    scores = scores_out if scores_out is not None else torch.empty(KB, dtype=torch.float32, device=gen_result.device)
+    reward = torch.empty(KB, dtype=torch.float32, device=gen_result.device)
+    if df is None:
+        K_.cider_d_multi(gen_result, ids, count, K, scores, reward=reward, sigma=_scorer.sigma, workspace=workspace)
+    else:
+        keys, vals = df.to(gen_result.device)
+        K_.cider_d_multi_df(gen_result, ids, count, K, scores, keys, vals, df.n_docs, reward=reward, sigma=_table_scorer(df).sigma, workspace=workspace)
+    return reward.unsqueeze(1).expand(KB, T), scores
