@@ -516,6 +516,23 @@ int vlp_sample_rows(const void* logits, int64_t ld, int32_t rows, int32_t V, uin
 int vlp_sample_rows_rep(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t rep, const uint64_t* seed_cell, uint64_t seed_add,
                         uint32_t rng_stream, int64_t* ids, int64_t ids_stride, int64_t* ids2, int64_t ids2_stride, float* logp, int64_t logp_stride,
                         void* stream);
+/* vlp_sample_rows_rep's draw from a tempered and truncated distribution.  With l_v the fp16 logit of column v < V:
+ *   z_v = l_v / temperature;
+ *   top-k (0 < top_k < V): S_k = {v : l_v >= tau_k}, tau_k the top_k-th largest logit counted with multiplicity -- ties at the threshold are all
+ *     kept; otherwise S_k is every column;
+ *   top-p (top_p < 1): with q_v = softmax(z) over S_k, tau_p is the largest fp16 value t whose columns {v in S_k : l_v >= t} carry a mass
+ *     >= top_p, and S = {v in S_k : l_v >= tau_p}; otherwise S = S_k;
+ *   ids[r*ids_stride] = argmax over S of z_v + g_v with vlp_sample_rows_rep's Gumbel values (same row key r, same hash), and
+ *   logp[r*logp_stride] = log of the id's probability under softmax(z) over S, the distribution drawn from.
+ * S is a value threshold and always holds the row's maximum; -inf logits are never drawn.  rows, rep, seed_cell, seed_add, rng_stream, ids2
+ * and the strides are vlp_sample_rows_rep's (call-invariant arguments: the launch can be captured); with temperature = 1, top_k = 0 and
+ * top_p = 1 the ids are vlp_sample_rows_rep's.  cutoff (optional, NULL = none): cutoff[r] = the smallest kept logit (the row minimum when
+ * nothing is filtered); kept (optional): kept[r] = |S|.  Repeated launches return the same bits in all four outputs.
+ * VLP_ERR_BAD_ARG, nothing launched: temperature <= 0 or not finite, top_k < 0, top_p <= 0, top_p > 1, rep < 1, or top_p < 1 with V > 2^22
+ * (the probability mass of a row is summed in 64-bit integers of 2^-40 of the largest column's). */
+int vlp_sample_rows_filtered(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t rep, const uint64_t* seed_cell, uint64_t seed_add,
+                             uint32_t rng_stream, float temperature, int32_t top_k, float top_p, int64_t* ids, int64_t ids_stride, int64_t* ids2,
+                             int64_t ids2_stride, float* logp, int64_t logp_stride, float* cutoff, int32_t* kept, void* stream);
 /* SCST scoring layout: the teacher-forced sequence whose training forward reproduces, for every sampled position, the hidden states of the
  * incremental decoder (replaces differentiating the decoder itself, modeling.py:1210-1251 under autograd in run_img2txt_dist.py:506-507).
  * With T sampled tokens y_0..y_{T-1} the scoring sequence has L' = in_len + 2T - 1 <= 256 slots:

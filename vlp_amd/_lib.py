@@ -220,6 +220,8 @@ SYMBOLS = {
     "vlp_vis_pe_prep": (C.c_int, [C.POINTER(VisPePrepArgs), vp]),
     "vlp_sample_rows": (C.c_int, [vp, i64, i32, i32, C.c_uint64, C.c_uint32, vp, i64, vp, i64, vp]),
     "vlp_sample_rows_rep": (C.c_int, [vp, i64, i32, i32, i32, vp, C.c_uint64, C.c_uint32, vp, i64, vp, i64, vp, i64, vp]),
+    "vlp_sample_rows_filtered": (C.c_int, [vp, i64, i32, i32, i32, vp, C.c_uint64, C.c_uint32, C.c_float, i32, C.c_float, vp, i64, vp, i64, vp, i64,
+                                           vp, vp, vp]),
     "vlp_argmax_rows": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp]),
     "vlp_mask_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "vlp_layernorm_fwd": (C.c_int, [C.POINTER(LayerNormFwdArgs), vp]),
@@ -625,6 +627,25 @@ def sample_rows_rep(logits, ld, rows, V, rep, seed_cell, seed_add, rng_stream, i
         raise RuntimeError("vlp_amd.sample_rows_rep: logits are shorter than ceil(rows / rep) rows of pitch ld")
     _check(load().vlp_sample_rows_rep(ptr(logits), ld, rows, V, rep, ptr(seed_cell), int(seed_add) & 0xFFFFFFFFFFFFFFFF, rng_stream, ptr(ids),
                                       ids.stride(0), ptr(ids2), ids2.stride(0) if ids2 is not None else 0, ptr(logp), logp.stride(0), stream_ptr()))
+
+
+def sample_rows_filtered(logits, ld, rows, V, rep, seed_cell, seed_add, rng_stream, temperature, top_k, top_p, ids, logp, ids2=None, cutoff=None,
+                         kept=None):
+    """sample_rows_rep's draw from softmax(logits / temperature) restricted to the top_k largest logits (0 = off; ties kept) and then to the
+    smallest value threshold that holds a mass of top_p (1 = off); logp is the log-probability under that distribution.  cutoff (f32 [rows])
+    / kept (int32 [rows]), optional and contiguous: the smallest kept logit and the size of the kept set of every draw."""
+    _req_cuda(logits, seed_cell, ids, logp, ids2, cutoff, kept)
+    if seed_cell.dtype not in (torch.int64, torch.uint64) or seed_cell.numel() < 1:
+        raise RuntimeError("vlp_amd.sample_rows_filtered: seed_cell must be an int64 device tensor of one element")
+    if rep >= 1 and logits.numel() < ((rows + rep - 1) // rep - 1) * ld + V:
+        raise RuntimeError("vlp_amd.sample_rows_filtered: logits are shorter than ceil(rows / rep) rows of pitch ld")
+    if cutoff is not None and (cutoff.dtype != torch.float32 or not cutoff.is_contiguous() or cutoff.numel() < rows):
+        raise RuntimeError("vlp_amd.sample_rows_filtered: cutoff must be a contiguous float32 tensor of `rows` elements")
+    if kept is not None and (kept.dtype != torch.int32 or not kept.is_contiguous() or kept.numel() < rows):
+        raise RuntimeError("vlp_amd.sample_rows_filtered: kept must be a contiguous int32 tensor of `rows` elements")
+    _check(load().vlp_sample_rows_filtered(ptr(logits), ld, rows, V, rep, ptr(seed_cell), int(seed_add) & 0xFFFFFFFFFFFFFFFF, rng_stream,
+                                           float(temperature), int(top_k), float(top_p), ptr(ids), ids.stride(0), ptr(ids2),
+                                           ids2.stride(0) if ids2 is not None else 0, ptr(logp), logp.stride(0), ptr(cutoff), ptr(kept), stream_ptr()))
 
 
 def mask_pack(mask_i64, out_u8, B, L, Lp, out_t=None):

@@ -1196,13 +1196,17 @@ class Engine(object):
         ws["calls"] += 1
         return out_ids[:, :n_steps].clone(), out_val[:, :n_steps].clone()
 
-    def decode_sample_group(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, n_samples):
+    def decode_sample_group(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, n_samples,
+                            temperature=1.0, top_k=0, top_p=1.0):
         """K = n_samples sampled captions per image (self-critical training with a leave-one-out baseline).  Step 0 runs the B prefixes as in
         decode_beam and draws K first tokens from each of the B logits rows; steps s >= 1 decode R = B*K rows against the per-image prefix
         cache, each row with a cache of its own for the generated positions -- rows never permute, so nothing is gathered.  The seed of
         step s is base_seed + step_seed + 1 + s (decode_greedy(sample=True)'s sequence), read by the sampling launches from a device cell
         the host sets once per call: every launch of a token step has call-invariant arguments and the steps are captured / replayed
-        (_run_planned).  Returns (ids [K*B, n] int64, logp [K*B, n] f32) sample-major: row k*B + b is sample k of image b."""
+        (_run_planned).  temperature / top_k / top_p other than (1, 0, 1) draw from the tempered, truncated distribution instead
+        (vlp_sample_rows_filtered: same seed cell, seed_add and RNG stream; logp is the log-probability under that distribution); the
+        values (1, 0, 1) issue the launches of a call without them.
+        Returns (ids [K*B, n] int64, logp [K*B, n] f32) sample-major: row k*B + b is sample k of image b."""
         self.pack()
         self.wait_params()
         V = self._model().config.vocab_size
@@ -1210,6 +1214,11 @@ class Engine(object):
         B, in_len, out_len = self._decode_check(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask)
         if Ks < 1 or Ks > 16:
             raise RuntimeError("vlp_amd: decode_sample_group draws 1..16 samples per image (got %d)" % Ks)
+        filt = (float(temperature), int(top_k), float(top_p))
+        if not (0.0 < filt[0] < float("inf")) or filt[1] < 0 or filt[1] >= 1 << 31 or not (0.0 < filt[2] <= 1.0):
+            raise RuntimeError("vlp_amd: decode_sample_group needs a finite temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got %r, %r, %r)" %
+                               (temperature, top_k, top_p))
+        plain = filt == (1.0, 0, 1.0)
         n_steps, T0 = out_len - in_len, in_len + 1
         R = B * Ks
         if R > 1024:
@@ -1236,8 +1245,18 @@ class Engine(object):
         # one sample per image: the rows are the images, their cache is `kv` itself (decode_greedy's launches)
         caches, prefix = (ws["kvS"], (ws["kv"], in_len, Ks)) if Ks > 1 else (ws["kv"], None)
 
+        if not plain and "filter_cutoff" not in ws:
+            # the smallest kept logit and the size of the kept set of every draw of the last filtered call, [step, row]: one store each,
+            # and what makes the set a call drew from checkable from outside
+            ws.update(filter_cutoff=torch.zeros(ws["out_ids"].shape[1], R, device=dev, dtype=torch.float32),
+                      filter_kept=torch.zeros(ws["out_ids"].shape[1], R, device=dev, dtype=torch.int32))
+
         def pick(s, rep):
-            K.sample_rows_rep(ws["logits"], ws["Vp"], R, V, rep, cell, s, 7001, out_ids[:, s], out_val[:, s], ids2=ws["xids"][:, 0])
+            if plain:
+                K.sample_rows_rep(ws["logits"], ws["Vp"], R, V, rep, cell, s, 7001, out_ids[:, s], out_val[:, s], ids2=ws["xids"][:, 0])
+            else:
+                K.sample_rows_filtered(ws["logits"], ws["Vp"], R, V, rep, cell, s, 7001, filt[0], filt[1], filt[2], out_ids[:, s], out_val[:, s],
+                                       ids2=ws["xids"][:, 0], cutoff=ws["filter_cutoff"][s], kept=ws["filter_kept"][s])
 
         self._decode_model_step(ws, ws["kv"], out_len, x_first, token_type_ids[:, :T0].contiguous(), position_ids[:, :T0].contiguous(),
                                 attention_mask[:, :T0, :T0], B, T0, 0, True)
@@ -1249,7 +1268,8 @@ class Engine(object):
                 self._decode_model_step(ws, caches, out_len, ws["xids"], ws["tt_steps"][s], ws["pid_steps"][s], am[:, st:st + 2, :st + 2], R, 2, st,
                                         False, prefix=prefix)
                 pick(s, 1)
-            self._run_planned(ws, ("sample_group", s), step)
+            # a replayed step carries its own call's parameters: they are part of the key (the unfiltered steps keep theirs)
+            self._run_planned(ws, ("sample_group", s) + (() if plain else filt), step)
         ws["calls"] += 1
 
         def sample_major(t):             # decode row b*K + k -> row k*B + b, one permuted copy

@@ -629,15 +629,36 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         return self.__dict__["_engine"]
 
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy",
-                n_samples=1):
+                n_samples=1, temperature=1.0, top_k=0, top_p=1.0):
         """Returns (output_ids [B, n], output_probs [B, n]) with n = token_type_ids.shape[1] - input_ids.shape[1], as :1253.
         output_probs are the maximal prediction scores (logits), exactly what the reference returns in greedy mode (:1228).
         n_samples = K > 1 with sample_mode='sample' (not in the reference): K draws per image, returned sample-major as [K*B, n] ids and
         log-probabilities (row k*B + b is sample k of image b; Engine.decode_sample_group); in train() mode with gradients enabled the
-        log-probabilities are differentiable, scored as K*B independent sequences."""
+        log-probabilities are differentiable, scored as K*B independent sequences.
+        temperature / top_k / top_p (not in the reference; sample_mode='sample' without beam search, eval or no_grad only): any value other
+        than (1, 0, 1) draws every token from softmax(logits / temperature) restricted to the top_k largest logits (0 = all; ties kept) and
+        then to the smallest set of largest logits holding a mass of top_p (vlp_sample_rows_filtered, Engine.decode_sample_group for every
+        n_samples >= 1); the second output is the log-probability under that distribution.  (1, 0, 1) changes nothing."""
         if not input_ids.is_cuda:
             raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only (inputs must be on the GPU); there is no CPU path")
         n_samples = int(n_samples)
+        temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+        if not (0.0 < temperature < float("inf")) or top_k < 0 or top_k >= 1 << 31 or not (0.0 < top_p <= 1.0):
+            raise ValueError("temperature must be finite and > 0, top_k >= 0 and 0 < top_p <= 1 (got %r, %r, %r)" % (temperature, top_k, top_p))
+        if (temperature, top_k, top_p) != (1.0, 0, 1.0):
+            what = "temperature=%g, top_k=%d, top_p=%g" % (temperature, top_k, top_p)
+            if sample_mode != "sample":
+                raise ValueError("%s shape the distribution sample_mode='sample' draws from; sample_mode is %r" % (what, sample_mode))
+            if self.search_beam_size > 1:
+                raise ValueError("%s with search_beam_size=%d: beam search is not filtered" % (what, self.search_beam_size))
+            if n_samples < 1:
+                raise ValueError("n_samples=%d: n_samples >= 1" % n_samples)
+            if self.training and torch.is_grad_enabled():
+                raise ValueError("%s in train() mode with gradients enabled: the scoring pass differentiates the unfiltered log-softmax, a "
+                                 "policy gradient of the filtered draw would be wrong; call under eval() or torch.no_grad()" % what)
+            with torch.no_grad():
+                return self.engine.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
+                                                       n_samples, temperature=temperature, top_k=top_k, top_p=top_p)
         if n_samples != 1:
             if n_samples < 1 or sample_mode != "sample":
                 raise ValueError("n_samples=%d needs sample_mode='sample' and n_samples >= 1" % n_samples)
