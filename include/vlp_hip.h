@@ -39,6 +39,8 @@ extern "C" {
  * well. */
 /* + vlp_cider_d_multi / vlp_cider_d_multi_df with their workspace functions (2..16 hypotheses per group, leave-one-out reward) and
  * vlp_sample_rows_rep (several draws per logits row, seed in device memory): they take the existing structs; purely additive as well. */
+/* + vlp_bleu4 (sentence BLEU-4 of the SCST hypotheses, mixed with the CIDEr-D scores, with the baseline) and its argument struct: purely
+ * additive as well. */
 /* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 
@@ -771,6 +773,45 @@ int64_t vlp_cider_d_multi_workspace_bytes(int32_t G, int32_t R, int32_t T, int32
 int vlp_cider_d_multi(const vlp_cider_d_args* a, void* stream);
 int64_t vlp_cider_d_multi_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
 int vlp_cider_d_multi_df(const vlp_cider_d_df_args* a, void* stream);
+
+/* Sentence BLEU-4 of id strings, the weighted mix with the CIDEr-D scores of a preceding vlp_cider_d* launch and the baseline of the mixed
+ * scores (SCST with the reward cider_weight * CIDEr-D + bleu_weight * BLEU-4).  The specification is vlp_amd/scst.py Bleu.compute_score
+ * (coco-caption's per-sentence BLEU with option='closest') on the strings array_to_str makes.  Strings, groups and ref_count are
+ * vlp_cider_d's: a string is a row's ids up to AND INCLUDING the first 0 (all T without one), hypothesis row i belongs to group i % G, the
+ * first ref_count[g] (clamped to 1..R, NULL = R) reference rows of a group are valid; nothing behind a row's first 0 and no invalid
+ * reference row is read as text.  n-grams are compared token by token, never hashed.  Per hypothesis h:
+ *   - len_h = its number of tokens; reflen = the valid reference length closest to len_h, the shorter on a tie;
+ *   - correct_k (k = 1..4) = sum over the distinct k-grams g of h of min(count_h(g), max over the valid references of count_r(g)), exact
+ *     integers; guess_k = max(0, len_h - k + 1);
+ *   - fp32: p_0 = 1, p_k = p_(k-1) * ((correct_k + 1e-15f) / (guess_k + 1e-9f)); bleu4 = powf(p_4, 0.25f), times
+ *     expf((len_h - reflen) / len_h) when len_h < reflen (the brevity penalty exp(1 - reflen / len_h));
+ *   - stats (optional) [i][0..6) = correct_1..4, len_h, reflen: the integers the score is made of;
+ *   - mixed (optional) [i] = w_base * base[i] + w_bleu * bleu4[i] -- two fp32 multiplications and one fp32 addition, never contracted into
+ *     an fma -- or w_bleu * bleu4[i] when base is NULL.  mixed may be the same array as base (element i is read before it is written, by
+ *     the thread that writes it);
+ *   - reward (optional, needs mixed) over the stored mixed values m, with the formulas and summation order of the vlp_cider_d entries:
+ *     VLP_BLEU_REWARD_PAIR (mult == 2): reward [G], [g] = m[g] - m[G + g];  VLP_BLEU_REWARD_LOO (mult >= 2): reward [mult*G],
+ *     [k*G + g] = m[k*G + g] - (sum over j != k of m[j*G + g], ascending j from 0) / (mult - 1).
+ * One launch (one block per group, one wave per hypothesis, one lane per position), no workspace, no host involvement, capturable; the
+ * accurate logf / expf / powf, every sum in a fixed order, no atomics: equal inputs give bit-equal outputs.  Nothing is written outside
+ * bleu4[0, mult*G), stats[0, 6*mult*G), mixed[0, mult*G) and reward.
+ * Accepted: 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, 1 <= mult <= 16, non-null hyp / ref / bleu4, hyp_ld / ref_ld >= T, ref_group_stride
+ * >= (R-1) * ref_ld + T, reward only with mixed and a mode that fits mult.  Anything else returns VLP_ERR_BAD_ARG before a launch. */
+enum { VLP_BLEU_REWARD_PAIR = 0, VLP_BLEU_REWARD_LOO = 1 };
+typedef struct {
+    const int64_t* hyp; int64_t hyp_ld;                        /* [mult*G, T]; row i is scored against group i % G */
+    const int64_t* ref; int64_t ref_group_stride, ref_ld;      /* [G, R, T] */
+    const int32_t* ref_count;                                  /* [G] or NULL = all R */
+    int32_t G, R, T, mult;
+    float* bleu4;                                              /* [mult*G] out */
+    int32_t* stats;                                            /* optional [mult*G, 6] out */
+    const float* base;                                         /* optional [mult*G]: the CIDEr-D scores */
+    float w_base, w_bleu;
+    float* mixed;                                              /* optional [mult*G] out */
+    float* reward;                                             /* optional out, [G] (pair) or [mult*G] (leave-one-out); needs mixed */
+    int32_t reward_mode;                                       /* VLP_BLEU_REWARD_* */
+} vlp_bleu4_args;
+int vlp_bleu4(const vlp_bleu4_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

@@ -1,7 +1,7 @@
 """Per-phase timing of one self-critical (--scst) training step on one MI355X -> profiles/scst_step.json.
 
     python tools/scst_bench.py [--batches 16 64] [--steps 5] [--warmup 2] [--reward host|device] [--refs R] [--df N] [--samples K]
-                               [--out profiles/scst_step.json]
+                               [--cider_weight W] [--bleu_weight W] [--out profiles/scst_step.json]
 
 Every step is the entry script's own vlp_amd.run_img2txt_dist.scst_step (the model's sample_mode paths, the reward, RewardCriterion, the fp16
 optimizer) at L = 123 (COCO's --max_len_b 20), 12 layers, the bert-base-cased vocabulary, on a seeded synthetic batch.  scst_step reports the
@@ -26,7 +26,10 @@ search per n-gram on the host.  Its default --out is profiles/scst_reward_df.jso
 --samples K >= 2 times the step of --scst_samples K: K samples per image with a leave-one-out baseline.  There is no greedy_decode phase;
 sample_decode is Engine.decode_sample_group (K*B rows, graph-planned token steps), score_fwd / score_bwd run over K*B sequences and the
 reward phase scores K*B captions.  --batches stays the number of images.  Its default --out is profiles/scst_samples.json; each record names
-its samples (1 = the one-sample estimator above) and its sample_decode_token_step_ms (the phase over the T token steps)."""
+its samples (1 = the one-sample estimator above) and its sample_decode_token_step_ms (the phase over the T token steps).
+--cider_weight / --bleu_weight other than 1 / 0 time the step of --scst_cider_weight / --scst_bleu_weight: the reward phase then scores sentence
+BLEU-4 as well (vlp_bleu4 on the device, vlp_amd.scst.Bleu on the host).  With 1 / 0 scst_step is called without the keyword, as before.  Their
+default --out is profiles/scst_bleu.json; each record names its reward_weights."""
 import argparse
 import json
 import os
@@ -77,7 +80,7 @@ def seeded_table(n, n_docs=113287, vocab=28996, seed=5):
     return DocFreq(key, rng.randint(1, n_docs + 1, size=len(key)).astype(np.int32), n_docs, 20, S.SEP_ID)
 
 
-def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1):
+def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1, weights=(1.0, 0.0)):
     cfg = BertConfig(28996, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, type_vocab_size=6)
     torch.manual_seed(0)
     m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=100).half().to(dev)
@@ -111,12 +114,13 @@ def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1):
     for it in range(warmup + steps):
         clock["rec"] = it >= warmup
         mark(None)                          # the step starts here
-        R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark, reward_on=reward, df=df, **({"samples": samples} if samples > 1 else {}))
+        R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark, reward_on=reward, df=df, **({"samples": samples} if samples > 1 else {}),
+                    **({"reward_weights": weights} if tuple(weights) != (1.0, 0.0) else {}))
     L = batch.input_ids.shape[1]
     out = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v))} for k, v in times.items()}
     out["step_ms_sum_of_medians"] = float(sum(out[k]["median_ms"] for k in phases))
     out.update(B=B, L=L, T=L - 102, scoring_length=102 + 2 * (L - 102) - 1, layers=12, vocab=28996, steps=steps, warmup=warmup, reward=reward, refs=refs,
-               df_ngrams=0 if df is None else len(df), samples=samples, sample_decode_token_step_ms=out["sample_decode"]["median_ms"] / (L - 102))
+               df_ngrams=0 if df is None else len(df), samples=samples, reward_weights=list(weights), sample_decode_token_step_ms=out["sample_decode"]["median_ms"] / (L - 102))
     return out
 
 
@@ -130,15 +134,19 @@ def main():
     ap.add_argument("--df", type=int, default=0, metavar="N", help="score with a document-frequency table of N seeded n-grams (0 = the step's own references)")
     ap.add_argument("--samples", type=int, default=1, metavar="K", help="samples per image (--scst_samples): 1 = one sample against a greedy decode, "
                                                                         "2..16 = K samples with a leave-one-out baseline")
+    ap.add_argument("--cider_weight", type=float, default=1.0, help="the weight of CIDEr-D in the reward (--scst_cider_weight)")
+    ap.add_argument("--bleu_weight", type=float, default=0.0, help="the weight of sentence BLEU-4 in the reward (--scst_bleu_weight); 0 = CIDEr-D alone")
     ap.add_argument("--out", default=None, help="default: profiles/scst_step.json for --reward host --refs 1, profiles/scst_reward_df.json with --df, "
-                                                "profiles/scst_samples.json with --samples above 1, else profiles/scst_reward_device.json")
+                                                "profiles/scst_samples.json with --samples above 1, "
+                                                "profiles/scst_bleu.json with reward weights other than 1 / 0, else profiles/scst_reward_device.json")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "scst_samples.json" if a.samples > 1 else "scst_reward_df.json" if a.df else
+        a.out = os.path.join(ROOT, "profiles", "scst_bleu.json" if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "scst_samples.json" if a.samples > 1 else "scst_reward_df.json" if a.df else
                              "scst_step.json" if (a.reward == "host" and a.refs == 1) else "scst_reward_device.json")
     dev = torch.device("cuda")
     tool = "tools/scst_bench.py --batches %s --steps %d --warmup %d --reward %s --refs %d" % (" ".join(map(str, a.batches)), a.steps, a.warmup, a.reward,
-                                                                                             a.refs) + (" --df %d" % a.df if a.df else "") + (" --samples %d" % a.samples if a.samples > 1 else "")
+                                                                                             a.refs) + (" --df %d" % a.df if a.df else "") + (" --samples %d" % a.samples if a.samples > 1 else "") + (
+        " --cider_weight %g --bleu_weight %g" % (a.cider_weight, a.bleu_weight) if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "")
     df = seeded_table(a.df) if a.df else None
     res = {"device": torch.cuda.get_device_name(0), "note": NOTE, "runs": []}
     yardstick = os.path.realpath(a.out) == os.path.realpath(os.path.join(ROOT, "profiles", "scst_step.json"))
@@ -154,7 +162,7 @@ def main():
                     res[k] = v
         res["tools"].append(tool)
     for B in a.batches:
-        r = bench(B, a.steps, a.warmup, dev, a.reward, a.refs, df, a.samples)
+        r = bench(B, a.steps, a.warmup, dev, a.reward, a.refs, df, a.samples, (a.cider_weight, a.bleu_weight))
         print(json.dumps(r, sort_keys=True), flush=True)
         res["runs"].append(r)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

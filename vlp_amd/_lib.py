@@ -154,6 +154,12 @@ class CiderDDfArgs(C.Structure):
     _fields_ = [("s", CiderDArgs), ("df_keys", vp), ("df_vals", vp), ("df_n", i64), ("n_docs", i64)]
 
 
+class Bleu4Args(C.Structure):
+    _fields_ = [("hyp", vp), ("hyp_ld", i64), ("ref", vp), ("ref_group_stride", i64), ("ref_ld", i64), ("ref_count", vp),
+                ("G", i32), ("R", i32), ("T", i32), ("mult", i32), ("bleu4", vp), ("stats", vp), ("base", vp), ("w_base", f32), ("w_bleu", f32),
+                ("mixed", vp), ("reward", vp), ("reward_mode", i32)]
+
+
 class MlmLossFwdArgs(C.Structure):
     _fields_ = [("logits", vp), ("ld_logits", i64), ("labels", vp), ("weights", vp), ("loss", vp), ("lse", vp), ("coef", vp),
                 ("row_loss", vp), ("B", i32), ("P", i32), ("V", i32), ("drop_worst_ratio", f32)]
@@ -259,6 +265,7 @@ SYMBOLS = {
     "vlp_cider_d_multi": (C.c_int, [C.POINTER(CiderDArgs), vp]),
     "vlp_cider_d_multi_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vlp_cider_d_multi_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
+    "vlp_bleu4": (C.c_int, [C.POINTER(Bleu4Args), vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
     "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
@@ -850,6 +857,36 @@ def cider_d_multi_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs
     cider_d_multi_df_workspace_bytes() bytes."""
     a = _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, cider_d_multi_df_workspace_bytes, mult)
     _check(load().vlp_cider_d_multi_df(C.byref(a), stream_ptr()))
+
+
+BLEU_REWARD_PAIR, BLEU_REWARD_LOO = 0, 1
+
+
+def bleu4(hyp, ref, ref_count, mult, bleu4, stats=None, base=None, w_base=1.0, w_bleu=1.0, mixed=None, reward=None, loo=False):
+    """Sentence BLEU-4 on the device with the mix and the baseline (include/vlp_hip.h vlp_bleu4): hyp, ref, ref_count as for cider_d (mult in
+    1..16); bleu4 f32 [mult*G]; stats int32 [mult*G, 6] or None (correct_1..4, len_h, reflen); base f32 [mult*G] or None (the CIDEr-D scores);
+    mixed f32 [mult*G] or None = w_base * base + w_bleu * bleu4 (w_bleu * bleu4 without base; may be the same tensor as base); reward f32 or
+    None: [G] = mixed[:G] - mixed[G:] (mult == 2), or with loo=True [mult*G], every mixed score minus the mean of its group's others.  One
+    launch on the current stream, no workspace."""
+    _req_cuda(hyp, ref, ref_count, bleu4, stats, base, mixed, reward)
+    if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
+        raise RuntimeError("vlp_amd.bleu4: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
+    G, R, T = ref.shape
+    n = mult * G
+    if hyp.shape[0] != n or hyp.shape[1] != T:
+        raise RuntimeError("vlp_amd.bleu4: hyp must be [%d, %d]" % (n, T))
+    if ref_count is not None and (ref_count.dtype != torch.int32 or not ref_count.is_contiguous() or ref_count.numel() != G):
+        raise RuntimeError("vlp_amd.bleu4: ref_count must be contiguous int32 [%d]" % G)
+    for name, t, need in (("bleu4", bleu4, n), ("base", base, n), ("mixed", mixed, n), ("reward", reward, n if loo else G)):
+        if t is None and name != "bleu4":
+            continue
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need:
+            raise RuntimeError("vlp_amd.bleu4: %s must be contiguous f32 [%d]" % (name, need))
+    if stats is not None and (stats.dtype != torch.int32 or not stats.is_contiguous() or stats.numel() < 6 * n):
+        raise RuntimeError("vlp_amd.bleu4: stats must be contiguous int32 [%d, 6]" % n)
+    a = Bleu4Args(ptr(hyp), hyp.stride(0), ptr(ref), ref.stride(0), ref.stride(1), ptr(ref_count), G, R, T, mult, ptr(bleu4), ptr(stats), ptr(base),
+                  w_base, w_bleu, ptr(mixed), ptr(reward), BLEU_REWARD_LOO if loo else BLEU_REWARD_PAIR)
+    _check(load().vlp_bleu4(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

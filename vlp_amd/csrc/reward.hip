@@ -19,6 +19,9 @@
 // vlp_cider_d_multi / vlp_cider_d_multi_df are the same two kernels with 2..16 hypotheses per group (64 * mult threads in the scoring block) and
 // the leave-one-out reward: every hypothesis against the mean of the group's other scores.
 //
+// vlp_bleu4 (at the end of this file) is a third kernel of the scoring kernel's shape: sentence BLEU-4 of the hypotheses, its weighted mix with the
+// CIDEr-D scores and the reward of the mixed scores, in one launch.
+//
 // vlp_cider_d_df takes df from a resident table (sorted uint64 keys, int32 df; vlp_amd/scst.py DocFreq) instead of the call's references.
 // Both kernels are the ones above with TABLE = true: the counting pass drops its loop over the groups -- every (position, order) of the
 // block's string gets a lane of its own that packs the n-gram's key and looks it up (a lower-bound binary search of dependent global loads:
@@ -409,4 +412,155 @@ extern "C" int vlp_cider_d_multi_df(const vlp_cider_d_df_args* d, void* stream) 
     CD_CHECK_ARGS(a, "vlp_cider_d_multi_df", need, true);
     CD_CHECK_TABLE(d, "vlp_cider_d_multi_df");
     return cd_run_df(d, stream, true, "vlp_cider_d_multi_df");
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// vlp_bleu4: sentence BLEU-4 of the hypotheses (vlp_amd/scst.py Bleu), mixed with the CIDEr-D scores of a preceding launch, and the baseline
+// of the mixed scores.  One block per group, one wave per hypothesis, one lane per position, the group's valid references staged in LDS as
+// above.  Per position and order a lane holds the n-gram's multiplicity in its own string (tf), whether it is the first occurrence there,
+// and the maximum over the references of its count: the first occurrence of every distinct n-gram contributes min(tf, max count), an integer
+// wave sum gives correct_k.  Lane 0 turns the six integers into the score in fp32.
+// ------------------------------------------------------------------------------------------------------------------------------------------
+struct bleu_out {
+    float* bleu4;
+    int32_t* stats;
+    const float* base;
+    float w_base, w_bleu;
+    float* mixed;
+    float* reward;
+    int loo;
+};
+
+DEVFN int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// wa * a + wb * b as two fp32 multiplications and one fp32 addition.  The library is built with -ffp-contract=fast, which fuses across
+// statements and disregards pragmas (and __fmul_rn is a plain product here), so each product passes through an empty asm statement: the
+// compiler cannot look through it, and what reaches the addition is the rounded product.
+DEVFN float mix_unfused(float wa, float a, float wb, float b) {
+    float x = wa * a, y = wb * b;
+    asm volatile("" : "+v"(x), "+v"(y));
+    return x + y;
+}
+
+__global__ __launch_bounds__(64 * CD_MAX_MULT) void bleu4_kernel(vlp_cider_d_args a, bleu_out o) {
+    extern __shared__ __attribute__((aligned(16))) int cd_refs[];      // [R][T + CD_PAD]
+    __shared__ int ref_len_s[8];
+    __shared__ int hrow[CD_MAX_MULT][64 + CD_PAD];                     // each wave's own string with a reference's sentinel
+    __shared__ float sc[CD_MAX_MULT];
+    const int T = a.T, R = a.R, G = a.G, ldr = T + CD_PAD;
+    const int g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, h = w * G + g;
+    cd_stage_refs(a, g * R, R, cd_refs, ref_len_s, 64, blockDim.x);
+
+    const int tok = lane < T ? (int)a.hyp[(int64_t)h * a.hyp_ld + lane] : CD_HYP_END;
+    const unsigned long long zm = __ballot(lane < T && tok == 0);
+    const int len = zm ? (int)__builtin_ctzll(zm) + 1 : T;
+    int av[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = __shfl(tok, (lane + j) & 63, 64);
+        av[j] = lane + j < len ? t : CD_HYP_END;
+    }
+    hrow[w][lane] = lane < len ? tok : CD_REF_END;
+    if (lane < CD_PAD) hrow[w][64 + lane] = CD_REF_END;
+    __syncthreads();
+
+    // multiplicity and first occurrence of the k-gram at this lane inside the own string
+    int tf[4] = {0, 0, 0, 0}, first[4] = {1, 1, 1, 1}, best[4] = {0, 0, 0, 0};
+    {
+        const int* row = hrow[w];
+        int b0 = row[0], b1 = row[1], b2 = row[2];
+        for (int q = 0; q < T; ++q) {
+            const int b3 = row[q + 3];
+            const int m = cd_match(av[0], av[1], av[2], av[3], b0, b1, b2, b3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                tf[k] += m > k;
+                first[k] &= !(m > k && q < lane);
+            }
+            b0 = b1; b1 = b2; b2 = b3;
+        }
+    }
+    // its count in every valid reference: the maximum; the closest reference length, the shorter on a tie
+    const int nr = cd_ref_count(a.ref_count, g, R);
+    int reflen = 0, refdist = 1 << 30;
+    for (int r = 0; r < nr; ++r) {
+        const int* row = cd_refs + r * ldr;
+        int t[4] = {0, 0, 0, 0};
+        int b0 = row[0], b1 = row[1], b2 = row[2];
+        for (int q = 0; q < T; ++q) {
+            const int b3 = row[q + 3];
+            const int m = cd_match(av[0], av[1], av[2], av[3], b0, b1, b2, b3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] += m > k;
+            b0 = b1; b1 = b2; b2 = b3;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) best[k] = max(best[k], t[k]);
+        const int lr = ref_len_s[r], d = abs(lr - len);
+        if (d < refdist || (d == refdist && lr < reflen)) { refdist = d; reflen = lr; }
+    }
+    int correct[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) correct[k] = wave_sum_int((tf[k] > 0 && first[k]) ? min(tf[k], best[k]) : 0);
+
+    if (lane == 0) {
+        float p = 1.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p = p * (((float)correct[k] + 1e-15f) / ((float)max(0, len - k) + 1e-9f));
+        float b = powf(p, 0.25f);
+        if (len < reflen) b *= expf((float)(len - reflen) / (float)len);       // exp(1 - reflen / len_h)
+        o.bleu4[h] = b;
+        if (o.stats) {
+            int32_t* st = o.stats + (int64_t)h * 6;
+            st[0] = correct[0]; st[1] = correct[1]; st[2] = correct[2]; st[3] = correct[3]; st[4] = len; st[5] = reflen;
+        }
+        if (o.mixed) {
+            const float m = o.base ? mix_unfused(o.w_base, o.base[h], o.w_bleu, b) : o.w_bleu * b;
+            o.mixed[h] = m;
+            sc[w] = m;
+        }
+    }
+    if (o.reward) {                                                    // (the entry checked that mixed is there)
+        __syncthreads();
+        if (o.loo) {                                                   // thread k: hypothesis k of the group against the others, ascending j
+            const int k = threadIdx.x;
+            if (k < a.mult) {
+                float others = 0.f;
+                for (int j = 0; j < a.mult; ++j)
+                    if (j != k) others += sc[j];
+                o.reward[(int64_t)k * G + g] = sc[k] - others / (float)(a.mult - 1);
+            }
+        } else if (threadIdx.x == 0) {                                 // mult == 2 (checked by the entry)
+            o.reward[g] = sc[0] - sc[1];
+        }
+    }
+}
+
+extern "C" int vlp_bleu4(const vlp_bleu4_args* b, void* stream) {
+    VLP_CHECK_ARG(b, "vlp_bleu4: null args");
+    VLP_CHECK_ARG(b->T >= 1 && b->T <= 64 && b->R >= 1 && b->R <= 8 && b->G >= 1 && b->G <= 1024 && b->mult >= 1 && b->mult <= CD_MAX_MULT,
+                  "vlp_bleu4: needs 1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, 1 <= mult <= 16 (G %d, R %d, T %d, mult %d)", b->G, b->R, b->T, b->mult);
+    VLP_CHECK_ARG(b->hyp && b->ref && b->bleu4, "vlp_bleu4: null operand");
+    VLP_CHECK_ARG(b->hyp_ld >= b->T && b->ref_ld >= b->T && b->ref_group_stride >= (int64_t)(b->R - 1) * b->ref_ld + b->T,
+                  "vlp_bleu4: strides shorter than the rows");
+    if (b->reward) {
+        VLP_CHECK_ARG(b->mixed, "vlp_bleu4: the reward is computed from the mixed scores: reward without mixed");
+        VLP_CHECK_ARG(b->reward_mode == VLP_BLEU_REWARD_PAIR || b->reward_mode == VLP_BLEU_REWARD_LOO, "vlp_bleu4: unknown reward_mode %d", b->reward_mode);
+        VLP_CHECK_ARG(b->reward_mode != VLP_BLEU_REWARD_PAIR || b->mult == 2, "vlp_bleu4: reward = mixed[g] - mixed[G + g] needs mult == 2 (mult %d)", b->mult);
+        VLP_CHECK_ARG(b->reward_mode != VLP_BLEU_REWARD_LOO || b->mult >= 2, "vlp_bleu4: the leave-one-out reward needs mult >= 2 (mult %d)", b->mult);
+    }
+    VLP_ENTER(b->ref, "vlp_bleu4");
+    vlp_cider_d_args a = {};
+    a.hyp = b->hyp; a.hyp_ld = b->hyp_ld;
+    a.ref = b->ref; a.ref_group_stride = b->ref_group_stride; a.ref_ld = b->ref_ld;
+    a.ref_count = b->ref_count;
+    a.G = b->G; a.R = b->R; a.T = b->T; a.mult = b->mult;
+    const bleu_out o = {b->bleu4, b->stats, b->base, b->w_base, b->w_bleu, b->mixed, b->reward, b->reward_mode == VLP_BLEU_REWARD_LOO ? 1 : 0};
+    hipLaunchKernelGGL(bleu4_kernel, dim3(b->G), dim3(64 * b->mult), (size_t)b->R * (b->T + CD_PAD) * sizeof(int), (hipStream_t)stream, a, o);
+    VLP_CHECK_LAUNCH("vlp_bleu4");
+    return VLP_OK;
 }

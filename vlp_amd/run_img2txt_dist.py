@@ -163,6 +163,14 @@ def build_parser():
                         "list); a PATH loads a table saved by `python -m vlp_amd.cider_df` (its --max_len_b and [SEP] id must be this run's).  A "
                         "deliberate departure from the reference's objective, like --scst_refs image; works with either --scst_reward and either "
                         "--scst_refs (with 'device' the table is uploaded once and stays resident)")
+    p.add_argument("--scst_cider_weight", type=float, default=1.0, metavar="W",
+                   help="--scst: the reward of a caption is W x CIDEr-D + --scst_bleu_weight x sentence BLEU-4 (the usual self-critical recipe; "
+                        "CIDEr-D here is on its 0..10 scale, BLEU-4 on 0..1).  1 and 0, the defaults, are the reference's CIDEr-D-only reward")
+    p.add_argument("--scst_bleu_weight", type=float, default=0.0, metavar="W",
+                   help="--scst: the weight of sentence BLEU-4 (coco-caption's per-sentence BLEU with the closest reference length, "
+                        "vlp_amd.scst.Bleu) in the reward; 0 = off.  Works with either --scst_reward (on the device one more kernel, vlp_bleu4, "
+                        "scores, mixes and baselines), either --scst_refs, any --scst_df (which keeps applying to CIDEr-D only) and any "
+                        "--scst_samples.  Weights must be finite and not negative, and not both 0")
     return p
 
 
@@ -201,6 +209,14 @@ def derive_args(args):
                              "--token_file); or give the path of a table saved by `python -m vlp_amd.cider_df`")
         if args.scst_df != "train" and not os.path.isfile(args.scst_df):
             raise ValueError("--scst_df: 'batch', 'train' or the path of a saved table; there is no file %s" % args.scst_df)
+    if (args.scst_cider_weight, args.scst_bleu_weight) != (1.0, 0.0):
+        if not args.scst:
+            raise ValueError("--scst_cider_weight / --scst_bleu_weight need --scst (they weigh the two metrics of the SCST reward)")
+        from .scst import check_reward_weights
+        try:
+            check_reward_weights(args.scst_cider_weight, args.scst_bleu_weight)
+        except ValueError as e:
+            raise ValueError("--scst_cider_weight %r --scst_bleu_weight %r: %s" % (args.scst_cider_weight, args.scst_bleu_weight, e))
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -351,7 +367,7 @@ def scst_doc_freq(args):
 
 
 def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host", df=None,
-              samples=1):
+              samples=1, reward_weights=(1.0, 0.0)):
     """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
     train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
     baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
@@ -363,7 +379,9 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     vlp_amd.scst.DocFreq whose document frequencies the reward uses, on either side, instead of the step's own references'; None = those.
     samples=K >= 2 (--scst_samples): K samples per image, each baselined by the mean score of the image's other K - 1
     (self_critical_reward_group / _group_device).  There is no greedy decode and no "greedy_decode" phase; the log-probabilities, the reward
-    and RewardCriterion run over the K*B rows (row k*B + b is sample k of image b)."""
+    and RewardCriterion run over the K*B rows (row k*B + b is sample k of image b).
+    reward_weights (--scst_cider_weight, --scst_bleu_weight): the score of a caption is cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4,
+    in whichever of the five reward functions the step calls; (1, 0) calls them as before.  The phase marks do not change."""
     if mark is None:
         def mark(phase):
             pass
@@ -394,6 +412,8 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gt_ids = input_ids[:, len_vis_input + 2:]
     kw = {} if df is None else {"df": df}
+    if tuple(reward_weights) != (1.0, 0.0):
+        kw.update(cider_weight=float(reward_weights[0]), bleu_weight=float(reward_weights[1]))
     if samples > 1:
         refs = ans_labels if isinstance(ans_labels, CaptionRefs) else gt_ids
         if reward_on == "device":
@@ -560,7 +580,7 @@ def main(argv=None):
             if args.scst:
                 loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
                                          accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward, df=scst_df,
-                                         samples=args.scst_samples)
+                                         samples=args.scst_samples, reward_weights=(args.scst_cider_weight, args.scst_bleu_weight))
                 rewards.append(mean_r.detach())
             else:
                 lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,

@@ -25,6 +25,11 @@ n-gram -> number of IMAGES whose captions hold it, built once from the example l
 with every caption in the exact string form the reward sees.  CiderD(df=<DocFreq>) takes df from it and ref_len = log(n_docs); an n-gram the
 table does not hold has df 0.  The three self_critical_reward* functions pass a `df=` table through (None = the call's own references, the
 reference's behaviour); on the device the table is two resident arrays searched by the vlp_cider_d_df kernels.
+
+A second metric: Bleu is sentence BLEU-1..4 (coco-caption's per-sentence values, closest reference length).  Every self_critical_reward*
+function takes cider_weight / bleu_weight and scores a hypothesis with cider_weight * CIDEr-D + bleu_weight * BLEU-4 (CIDEr-D is 0..10 here,
+BLEU-4 0..1); the defaults (1, 0) are the CIDEr-D reward, computed exactly as before.  On the device one more kernel, vlp_bleu4, scores
+BLEU-4, mixes and baselines.
 """
 import itertools
 from collections import Counter, OrderedDict
@@ -244,6 +249,59 @@ class CiderD(object):
         return np.mean(scores), scores
 
 
+class Bleu(object):
+    """Sentence BLEU-1..4 (coco-caption's BLEU scorer with option='closest', its per-sentence values); compute_score(gts, res) -> (mean BLEU-4,
+    scores float64 [4, N]).  Same dictionaries of strings as CiderD.compute_score; tokens are the whitespace split (array_to_str's strings: the
+    terminating 0 is a token).  Per hypothesis h with references r_1..r_m, in fp64:
+      * reflen = the reference length closest to len_h, the shorter on a tie: the minimum over (|len_r - len_h|, len_r);
+      * guess_k = max(0, len_h - k + 1); correct_k = sum over the distinct k-grams g of h of min(count_h(g), max_j count_{r_j}(g));
+      * p_0 = 1, p_k = p_{k-1} * (correct_k + TINY) / (guess_k + SMALL), bleu_k = p_k ** (1 / k);
+      * ratio = (len_h + TINY) / (reflen + SMALL); ratio < 1 multiplies every bleu_k by exp(1 - 1 / ratio).
+    The specification of the vlp_bleu4 kernel (csrc/reward.hip); sentence_stats gives the integers a score is made of."""
+    TINY, SMALL = 1e-15, 1e-9
+
+    def __init__(self, n=4):
+        self.n = n
+
+    def sentence_stats(self, hypo, refs):
+        """(correct_1..n, len_h, reflen) of one hypothesis string against its reference strings, as python ints."""
+        h = hypo.split()
+        rs = [r.split() for r in refs]
+        best = Counter()
+        for r in rs:
+            for g, c in _ngrams(r, self.n).items():
+                if c > best[g]:
+                    best[g] = c
+        correct = [0] * self.n
+        for g, c in _ngrams(h, self.n).items():
+            correct[len(g) - 1] += min(c, best.get(g, 0))
+        reflen = min((abs(len(r) - len(h)), len(r)) for r in rs)[1]
+        return correct, len(h), reflen
+
+    def sentence_scores(self, correct, len_h, reflen):
+        """bleu_1..n (float64 [n]) from sentence_stats' integers."""
+        out = np.empty(self.n)
+        p = 1.0
+        for k in range(1, self.n + 1):
+            p = p * (correct[k - 1] + self.TINY) / (max(0, len_h - k + 1) + self.SMALL)
+            out[k - 1] = p ** (1.0 / k)
+        ratio = (len_h + self.TINY) / (reflen + self.SMALL)
+        if ratio < 1:
+            out *= np.exp(1 - 1 / ratio)
+        return out
+
+    def compute_score(self, gts, res):
+        assert gts.keys() == res.keys()
+        keys = list(gts.keys())
+        scores = np.empty((self.n, len(keys)))
+        for i, k in enumerate(keys):
+            hypo, ref = res[k], gts[k]
+            assert type(hypo) is list and len(hypo) == 1
+            assert type(ref) is list and len(ref) > 0
+            scores[:, i] = self.sentence_scores(*self.sentence_stats(hypo[0], ref))
+        return (float(np.mean(scores[-1])) if keys else 0.0), scores
+
+
 def array_to_str(arr):
     """scst_utils.py:27-33: the ids up to and including the first 0, space separated."""
     out = []
@@ -277,11 +335,41 @@ def _table_scorer(df):
     return df._scorer
 
 
-def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None, df=None):
+_bleu = Bleu()
+
+
+def check_reward_weights(cider_weight, bleu_weight):
+    """(cider_weight, bleu_weight) of the mixed reward cider_weight * CIDEr-D + bleu_weight * BLEU-4 as floats; negative or non-finite weights,
+    and both zero, raise ValueError."""
+    cw, bw = float(cider_weight), float(bleu_weight)
+    if not (np.isfinite(cw) and np.isfinite(bw)) or cw < 0 or bw < 0:
+        raise ValueError("the reward weights must be finite and not negative (cider_weight %r, bleu_weight %r)" % (cider_weight, bleu_weight))
+    if cw == 0 and bw == 0:
+        raise ValueError("the reward weights are both zero: there is no reward")
+    return cw, bw
+
+
+def _mixed_scores(gts, res, scorer, cider_weight, bleu_weight):
+    """cider_weight * CIDEr-D + bleu_weight * BLEU-4 per key (CIDEr-D here is 0..10, BLEU-4 0..1).  (1, 0) is the scorer's own array; a scorer
+    whose weight is 0 is not called."""
+    cw, bw = check_reward_weights(cider_weight, bleu_weight)
+    if cw == 1 and bw == 0:
+        return scorer.compute_score(gts, res)[1]
+    scores = None
+    if cw > 0:
+        scores = cw * np.asarray(scorer.compute_score(gts, res)[1], dtype=np.float64)
+    if bw > 0:
+        b = bw * _bleu.compute_score(gts, res)[1][3]
+        scores = b if scores is None else scores + b
+    return scores
+
+
+def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None, df=None, cider_weight=1.0, bleu_weight=0.0):
     """scst_utils.py:36-63: CIDEr-D of the B samples and the B greedy captions (2B hypotheses), each against its own ground truth (so the 2B
     reference sets are the ground truths twice); reward[b, :] = score(sample_b) - score(greedy_b) repeated over the T columns.  Arguments are
     id tensors or arrays [B, T]; returns (reward [B, T] float64 ndarray, scores [2B]).  df: a DocFreq whose document frequencies replace the
-    call's own (ignored when a scorer is given)."""
+    call's own (ignored when a scorer is given).  cider_weight / bleu_weight: the score of a hypothesis is cider_weight * CIDEr-D +
+    bleu_weight * sentence BLEU-4 (Bleu); (1, 0) is the CIDEr-D reward as it always was."""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     greedy_res, gt_ids, gen_result = host(greedy_res), host(gt_ids), host(gen_result)
@@ -294,7 +382,7 @@ def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None
         res[i], gts[i] = [gen_s[i]], [gt_s[i]]
     for i in range(B):
         res[B + i], gts[B + i] = [gre_s[i]], [gt_s[i]]
-    _, scores = (scorer or _table_scorer(df)).compute_score(gts, res)
+    scores = _mixed_scores(gts, res, scorer or _table_scorer(df), cider_weight, bleu_weight)
     d = scores[:B] - scores[B:]
     return np.repeat(d[:, np.newaxis], gen_result.shape[1], 1), scores
 
@@ -319,17 +407,18 @@ def _refs_parts(refs, B):
     return refs[:B].unsqueeze(1), None
 
 
-def self_critical_reward_refs(greedy_res, refs, gen_result, df=None):
+def self_critical_reward_refs(greedy_res, refs, gen_result, df=None, cider_weight=1.0, bleu_weight=0.0):
     """self_critical_reward against one OR several references per sample, on the host with CiderD: `refs` is the [B, T] ground-truth ids
     (then this is self_critical_reward itself) or a CaptionRefs (ids [B, R, T], count [B]: sample b is scored against the first count[b]
     rows).  Returns (reward [B, T] float64 ndarray, scores [2B]).  The oracle of self_critical_reward_device, and the host path of
-    multi-reference training.  df: a DocFreq whose document frequencies replace the call's own."""
+    multi-reference training.  df: a DocFreq whose document frequencies replace the call's own.  cider_weight / bleu_weight: as in
+    self_critical_reward."""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     from .input_prep import CaptionRefs
     B = len(gen_result)
     if not isinstance(refs, CaptionRefs):
-        return self_critical_reward(greedy_res, refs, gen_result, B, df=df)
+        return self_critical_reward(greedy_res, refs, gen_result, B, df=df, cider_weight=cider_weight, bleu_weight=bleu_weight)
     greedy_res, gen_result, ids, count = host(greedy_res), host(gen_result), host(refs.ids), host(refs.count)
     R = ids.shape[1]
     gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
@@ -338,20 +427,24 @@ def self_critical_reward_refs(greedy_res, refs, gen_result, df=None):
         res[i], gts[i] = [array_to_str(gen_result[i].tolist())], gt_s[i]
     for i in range(B):
         res[B + i], gts[B + i] = [array_to_str(greedy_res[i].tolist())], gt_s[i]
-    _, scores = _table_scorer(df).compute_score(gts, res)
+    scores = _mixed_scores(gts, res, _table_scorer(df), cider_weight, bleu_weight)
     d = scores[:B] - scores[B:]
     return np.repeat(d[:, np.newaxis], gen_result.shape[1], 1), scores
 
 
-def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, workspace=None, df=None):
+def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, workspace=None, df=None, cider_weight=1.0, bleu_weight=0.0):
     """self_critical_reward_refs on the device (vlp_cider_d, csrc/reward.hip): id tensors [B, T] on the GPU, `refs` the [B, T] ground-truth
     ids or a CaptionRefs with ids [B, R, T] of the same T.  Returns (reward f32 [B, T] -- the [B] differences expanded over the columns --,
     scores f32 [2B]) as device tensors; scores_out (f32 [2B]) receives the scores when given; workspace: the caller's kernel scratch
     (_lib.cider_d_workspace_bytes(B, R, T, 2) bytes, uint8), else allocated per call.  No device -> host transfer, no synchronisation: two
     kernel launches on the current stream, capturable into a graph.
     df: a DocFreq -- the vlp_cider_d_df kernels score with its document frequencies (workspace: _lib.cider_d_df_workspace_bytes).  The table
-    is uploaded by the first call that uses it on a device (DocFreq.to) and stays resident; make that call before a graph capture."""
+    is uploaded by the first call that uses it on a device (DocFreq.to) and stays resident; make that call before a graph capture.
+    cider_weight / bleu_weight other than (1, 0): the CIDEr-D launches (only with cider_weight > 0) write their scores, then one vlp_bleu4
+    launch scores sentence BLEU-4, replaces the scores by cider_weight * CIDEr-D + bleu_weight * BLEU-4 and writes the reward of those
+    mixed scores: the returned scores are the mixed ones; df applies to the CIDEr-D part only.  Still no host work and capturable."""
     from . import _lib as K
+    cw, bw = check_reward_weights(cider_weight, bleu_weight)
     from .input_prep import CaptionRefs
     B, T = gen_result.shape
     if isinstance(refs, CaptionRefs):
@@ -361,12 +454,18 @@ def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, w
         raise RuntimeError("self_critical_reward_device: samples, greedy captions and references must share [B, T] = [%d, %d]" % (B, T))
     hyp = torch.cat([gen_result, greedy_res], 0)
     scores = scores_out if scores_out is not None else torch.empty(2 * B, dtype=torch.float32, device=hyp.device)
-    diff = torch.empty(B, dtype=torch.float32, device=hyp.device)
-    if df is None:
-        K.cider_d(hyp, ids, count, 2, scores, reward=diff, sigma=_scorer.sigma, workspace=workspace)
-    else:
-        keys, vals = df.to(hyp.device)
-        K.cider_d_df(hyp, ids, count, 2, scores, keys, vals, df.n_docs, reward=diff, sigma=_table_scorer(df).sigma, workspace=workspace)
+    mix = not (cw == 1 and bw == 0)
+    out = torch.empty(3 * B if mix else B, dtype=torch.float32, device=hyp.device)      # the reward, then the BLEU-4 of the 2B hypotheses
+    diff = out[:B]
+    if cw > 0:
+        first = None if mix else diff                   # mixed: the reward is the vlp_bleu4 launch's
+        if df is None:
+            K.cider_d(hyp, ids, count, 2, scores, reward=first, sigma=_scorer.sigma, workspace=workspace)
+        else:
+            keys, vals = df.to(hyp.device)
+            K.cider_d_df(hyp, ids, count, 2, scores, keys, vals, df.n_docs, reward=first, sigma=_table_scorer(df).sigma, workspace=workspace)
+    if mix:
+        K.bleu4(hyp, ids, count, 2, out[B:], base=scores if cw > 0 else None, w_base=cw, w_bleu=bw, mixed=scores, reward=diff)
     return diff.unsqueeze(1).expand(B, T), scores
 
 
@@ -387,13 +486,14 @@ def _check_samples(n_rows, n_samples):
     return n_samples, n_rows // n_samples
 
 
-def self_critical_reward_group(gen_result, refs, n_samples, df=None):
+def self_critical_reward_group(gen_result, refs, n_samples, df=None, cider_weight=1.0, bleu_weight=0.0):
     """The leave-one-out reward of K = n_samples samples per image, on the host with CiderD in fp64: the specification of
     self_critical_reward_group_device and the `--scst_reward host` path.  gen_result [K*B, T] ids, row k*B + b = sample k of image b; refs
     the [B, T] ground-truth ids or a CaptionRefs (image b is scored against its first count[b] rows).  The K*B hypotheses each list their
     image's references, which is what coco-caption's Cider(df='corpus') sees: df counts every image K times and ref_len = log(K*B); a
     DocFreq `df` replaces both, without a K anywhere.  reward[k*B + b] = s[k*B + b] - (sum of s[j*B + b] over j != k, ascending j) / (K - 1).
-    Returns (reward [K*B, T] float64 ndarray -- the [K*B] rewards repeated over the columns --, scores [K*B])."""
+    Returns (reward [K*B, T] float64 ndarray -- the [K*B] rewards repeated over the columns --, scores [K*B]).  cider_weight / bleu_weight:
+    s is cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4, as in self_critical_reward."""
     def host(x):
         return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     from .input_prep import CaptionRefs
@@ -408,7 +508,7 @@ def self_critical_reward_group(gen_result, refs, n_samples, df=None):
     res, gts = OrderedDict(), OrderedDict()
     for i, row in enumerate(gen_result.tolist()):
         res[i], gts[i] = [array_to_str(row)], gt_s[i % B]
-    _, scores = _table_scorer(df).compute_score(gts, res)
+    scores = _mixed_scores(gts, res, _table_scorer(df), cider_weight, bleu_weight)
     s = np.asarray(scores, dtype=np.float64).reshape(K, B)
     reward = np.empty_like(s)
     for k in range(K):
@@ -420,13 +520,15 @@ def self_critical_reward_group(gen_result, refs, n_samples, df=None):
     return np.repeat(reward.reshape(-1)[:, np.newaxis], gen_result.shape[1], 1), scores
 
 
-def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=None, workspace=None, df=None):
+def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=None, workspace=None, df=None, cider_weight=1.0, bleu_weight=0.0):
     """self_critical_reward_group on the device (vlp_cider_d_multi / vlp_cider_d_multi_df, csrc/reward.hip): gen_result int64 [K*B, T] on the
     GPU, refs the [B, T] ground-truth ids or a CaptionRefs of the same T.  Returns (reward f32 [K*B, T] -- expanded over the columns --,
     scores f32 [K*B]) as device tensors; scores_out (f32 [K*B]) receives the scores when given; workspace: the caller's kernel scratch
     (_lib.cider_d_multi_workspace_bytes(B, R, T, K) or ..._multi_df_... bytes, uint8), else allocated per call.  No device -> host transfer,
-    no synchronisation: two launches on the current stream, capturable.  df: as in self_critical_reward_device."""
+    no synchronisation: two launches on the current stream, capturable.  df, cider_weight, bleu_weight: as in self_critical_reward_device
+    (the vlp_bleu4 launch then writes the leave-one-out reward of the mixed scores)."""
     from . import _lib as K_
+    cw, bw = check_reward_weights(cider_weight, bleu_weight)
     from .input_prep import CaptionRefs
     KB, T = gen_result.shape
     K, B = _check_samples(KB, n_samples)
@@ -436,10 +538,16 @@ def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=No
     if ids.shape[0] != B or ids.shape[2] != T:
         raise RuntimeError("self_critical_reward_group_device: %d samples of %d images need references [%d, R, %d]" % (K, B, B, T))
     scores = scores_out if scores_out is not None else torch.empty(KB, dtype=torch.float32, device=gen_result.device)
-    reward = torch.empty(KB, dtype=torch.float32, device=gen_result.device)
-    if df is None:
-        K_.cider_d_multi(gen_result, ids, count, K, scores, reward=reward, sigma=_scorer.sigma, workspace=workspace)
-    else:
-        keys, vals = df.to(gen_result.device)
-        K_.cider_d_multi_df(gen_result, ids, count, K, scores, keys, vals, df.n_docs, reward=reward, sigma=_table_scorer(df).sigma, workspace=workspace)
+    mix = not (cw == 1 and bw == 0)
+    out = torch.empty(2 * KB if mix else KB, dtype=torch.float32, device=gen_result.device)      # the reward, then the BLEU-4 of the hypotheses
+    reward = out[:KB]
+    if cw > 0:
+        first = None if mix else reward                 # mixed: the reward is the vlp_bleu4 launch's
+        if df is None:
+            K_.cider_d_multi(gen_result, ids, count, K, scores, reward=first, sigma=_scorer.sigma, workspace=workspace)
+        else:
+            keys, vals = df.to(gen_result.device)
+            K_.cider_d_multi_df(gen_result, ids, count, K, scores, keys, vals, df.n_docs, reward=first, sigma=_table_scorer(df).sigma, workspace=workspace)
+    if mix:
+        K_.bleu4(gen_result, ids, count, K, out[KB:], base=scores if cw > 0 else None, w_base=cw, w_bleu=bw, mixed=scores, reward=reward, loo=True)
     return reward.unsqueeze(1).expand(KB, T), scores
