@@ -41,6 +41,8 @@ extern "C" {
  * vlp_sample_rows_rep (several draws per logits row, seed in device memory): they take the existing structs; purely additive as well. */
 /* + vlp_bleu4 (sentence BLEU-4 of the SCST hypotheses, mixed with the CIDEr-D scores, with the baseline) and its argument struct: purely
  * additive as well. */
+/* + vlp_caption_eval / vlp_caption_eval_workspace_bytes (caption metrics of word strings: CIDEr-D, the BLEU integers, LCS for ROUGE-L) and
+ * its argument struct: purely additive as well. */
 /* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 
@@ -812,6 +814,33 @@ typedef struct {
     int32_t reward_mode;                                       /* VLP_BLEU_REWARD_* */
 } vlp_bleu4_args;
 int vlp_bleu4(const vlp_bleu4_args* a, void* stream);
+
+/* Caption metrics of id strings (evaluation, not a reward): per group g -- one image -- the CIDEr-D score of its one hypothesis against a
+ * resident document-frequency table, the six integers corpus BLEU-1..4 is made of, and per reference the longest common subsequence
+ * ROUGE-L is made of.  The specifications are vlp_amd/scst.py CiderD(df=<DocFreq>).compute_score and Bleu.sentence_stats and
+ * vlp_amd/caption_metrics.py lcs_len.  Operands, strides, ref_count and the table are vlp_cider_d_df's (d.s.mult must be 1, d.s.reward NULL;
+ * d.s.scores is the cider output), with ONE difference in how a row is read:
+ *   - a string is a WORD STRING: the ids of a row BEFORE its first 0, or all T ids without one.  The 0 is padding and never a token, an
+ *     empty string is legal, nothing from the first 0 on is read as text, and no invalid reference row is read at all.
+ * Outputs:
+ *   - d.s.scores [G] f32: vlp_cider_d_df's arithmetic on the word strings (same operations, same order).  An empty string has no n-grams,
+ *     zero norms and length 0;
+ *   - bleu_stats [G, 6] int32 = correct_1..4, len_h, reflen: vlp_bleu4's stats on the word strings (reflen = the valid reference length
+ *     closest to len_h, the shorter on a tie; an empty valid reference has length 0);
+ *   - lcs [G, R, 2] int32 = (length of the longest common subsequence of the hypothesis and reference r, len_r), (0, 0) for an invalid
+ *     reference row.
+ * Three launches (counting, scoring, LCS), no host involvement, capturable; no atomics, every sum in a fixed order: equal inputs give
+ * bit-equal outputs.  Nothing is written outside the three outputs and the workspace.
+ * Accepted: what vlp_cider_d_df accepts with mult == 1 (1 <= T <= 64, 1 <= R <= 8, 1 <= G <= 1024, the strides, sigma > 0, the table
+ * conditions), non-null bleu_stats and lcs, a 16-byte aligned workspace of vlp_caption_eval_workspace_bytes() bytes (0 for a refused
+ * shape).  Anything else returns VLP_ERR_BAD_ARG before a launch. */
+typedef struct {
+    vlp_cider_d_df_args d;                                     /* strings, shapes, cider output, workspace and table */
+    int32_t* bleu_stats;                                       /* [G, 6] out */
+    int32_t* lcs;                                              /* [G, R, 2] out */
+} vlp_caption_eval_args;
+int64_t vlp_caption_eval_workspace_bytes(int32_t G, int32_t R, int32_t T);
+int vlp_caption_eval(const vlp_caption_eval_args* a, void* stream);
 
 /* VQA loss (modeling.py:1030,1140): BCEWithLogits(mean) * num_answers. fwd -> loss[0] (loss must hold
  * 257 floats: loss[1..257) is scratch);

@@ -154,6 +154,10 @@ class CiderDDfArgs(C.Structure):
     _fields_ = [("s", CiderDArgs), ("df_keys", vp), ("df_vals", vp), ("df_n", i64), ("n_docs", i64)]
 
 
+class CaptionEvalArgs(C.Structure):
+    _fields_ = [("d", CiderDDfArgs), ("bleu_stats", vp), ("lcs", vp)]
+
+
 class Bleu4Args(C.Structure):
     _fields_ = [("hyp", vp), ("hyp_ld", i64), ("ref", vp), ("ref_group_stride", i64), ("ref_ld", i64), ("ref_count", vp),
                 ("G", i32), ("R", i32), ("T", i32), ("mult", i32), ("bleu4", vp), ("stats", vp), ("base", vp), ("w_base", f32), ("w_bleu", f32),
@@ -266,6 +270,8 @@ SYMBOLS = {
     "vlp_cider_d_multi_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vlp_cider_d_multi_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
     "vlp_bleu4": (C.c_int, [C.POINTER(Bleu4Args), vp]),
+    "vlp_caption_eval_workspace_bytes": (i64, [i32, i32, i32]),
+    "vlp_caption_eval": (C.c_int, [C.POINTER(CaptionEvalArgs), vp]),
     "vlp_mlm_loss_fwd": (C.c_int, [C.POINTER(MlmLossFwdArgs), vp]),
     "vlp_mlm_loss_bwd": (C.c_int, [C.POINTER(MlmLossBwdArgs), vp]),
     "vlp_mlm_loss_ls_fwd": (C.c_int, [C.POINTER(MlmLossLsFwdArgs), vp]),
@@ -887,6 +893,29 @@ def bleu4(hyp, ref, ref_count, mult, bleu4, stats=None, base=None, w_base=1.0, w
     a = Bleu4Args(ptr(hyp), hyp.stride(0), ptr(ref), ref.stride(0), ref.stride(1), ptr(ref_count), G, R, T, mult, ptr(bleu4), ptr(stats), ptr(base),
                   w_base, w_bleu, ptr(mixed), ptr(reward), BLEU_REWARD_LOO if loo else BLEU_REWARD_PAIR)
     _check(load().vlp_bleu4(C.byref(a), stream_ptr()))
+
+
+def caption_eval_workspace_bytes(G, R, T):
+    """0 for a shape vlp_caption_eval refuses."""
+    return int(load().vlp_caption_eval_workspace_bytes(G, R, T))
+
+
+def caption_eval(hyp, ref, ref_count, cider, bleu_stats, lcs, df_keys, df_vals, n_docs, sigma=6.0, workspace=None):
+    """Caption metrics of word strings on the device (include/vlp_hip.h vlp_caption_eval): hyp int64 [G, T] (one hypothesis per image), ref
+    int64 [G, R, T], ref_count int32 [G] or None, the table as for cider_d_df.  A string is the ids of a row BEFORE its first 0.  Outputs:
+    cider f32 [G], bleu_stats int32 [G, 6] (correct_1..4, len_h, reflen), lcs int32 [G, R, 2] (LCS length, len_r; (0, 0) for an invalid
+    reference).  workspace: caption_eval_workspace_bytes() bytes or None (a fresh allocation).  Three launches on the current stream."""
+    _req_cuda(bleu_stats, lcs)
+    d = _cider_d_df_args(hyp, ref, ref_count, 1, cider, df_keys, df_vals, n_docs, None, sigma, workspace,
+                         lambda G, R, T, mult: caption_eval_workspace_bytes(G, R, T), 1)
+    G, R, T = ref.shape
+    if bleu_stats.dtype != torch.int32 or not bleu_stats.is_contiguous() or bleu_stats.numel() < 6 * G:
+        raise RuntimeError("vlp_amd.caption_eval: bleu_stats must be contiguous int32 [%d, 6]" % G)
+    if lcs.dtype != torch.int32 or not lcs.is_contiguous() or lcs.numel() < 2 * G * R:
+        raise RuntimeError("vlp_amd.caption_eval: lcs must be contiguous int32 [%d, %d, 2]" % (G, R))
+    a = CaptionEvalArgs(d, ptr(bleu_stats), ptr(lcs))
+    a._keep = d                              # (its workspace lives until the launches have been enqueued)
+    _check(load().vlp_caption_eval(C.byref(a), stream_ptr()))
 
 
 def region_mask_build(vis_masked_pos, out, B, Pm, Nv):

@@ -11,7 +11,7 @@ Every flag of the reference script keeps its name and default.  What differs:
   * there is no tokenizer: the vocabulary file only maps the special tokens and --forbid_ignore_word to ids and the decoded ids back to word
     pieces.  Without one the ids of vlp_amd.synthetic are used and captions are written as space-joined token ids;
   * the predictions [{"image_id", "caption"}, ...] (input order; the list the reference hands to language_eval) are written to --output_file;
-    scoring them is left to the caller.
+    python -m vlp_amd.eval_captions scores them (BLEU-1..4, ROUGE-L, CIDEr; no Java).
 --do_lower_case, --image_root, --region_bbox_file and --region_det_file_prefix are accepted for the reference's command lines and not used: there is
 no tokenizer, and the features come from the packed store.
 A short last batch is filled up with its last image (and the extra rows dropped), so every batch runs the same launches.

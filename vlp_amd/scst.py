@@ -24,7 +24,8 @@ Document frequencies of a whole training set (coco-caption's `df=<file>` mode, t
 n-gram -> number of IMAGES whose captions hold it, built once from the example list (DocFreq.from_examples, `python -m vlp_amd.cider_df`)
 with every caption in the exact string form the reward sees.  CiderD(df=<DocFreq>) takes df from it and ref_len = log(n_docs); an n-gram the
 table does not hold has df 0.  The three self_critical_reward* functions pass a `df=` table through (None = the call's own references, the
-reference's behaviour); on the device the table is two resident arrays searched by the vlp_cider_d_df kernels.
+reference's behaviour); on the device the table is two resident arrays searched by the vlp_cider_d_df kernels.  DocFreq.from_token_lists
+builds the table of an evaluation instead (vlp_amd/caption_metrics.py): word strings as they are, nothing appended.
 
 A second metric: Bleu is sentence BLEU-1..4 (coco-caption's per-sentence values, closest reference length).  Every self_critical_reward*
 function takes cider_weight / bleu_weight and scores a hypothesis with cider_weight * CIDEr-D + bleu_weight * BLEU-4 (CIDEr-D is 0..10 here,
@@ -147,6 +148,54 @@ class DocFreq(object):
         keys, inv = np.unique(np.concatenate(parts_k), return_inverse=True)
         vals = np.bincount(inv, weights=np.concatenate(parts_v), minlength=len(keys)).astype(np.int32)
         return cls(keys.astype(np.uint64), vals, len(index), max_len_b, sep_id)
+
+    @classmethod
+    def from_token_lists(cls, docs, chunk=1 << 14):
+        """The table of an evaluation (vlp_amd.caption_metrics): docs is one entry per image, each a list of WORD STRINGS -- lists of word ids
+        in 1..65534, the empty list included; nothing is appended (from_examples adds [SEP] and the 0 of the reward's strings; a word string
+        has neither, so no key is ever formed from 0).  df(g) = the number of images one of whose strings holds g; n_docs = len(docs).
+        Vectorised numpy per chunk of `chunk` images."""
+        n_docs = len(docs)
+        if not n_docs:
+            raise ValueError("DocFreq: no documents")
+        parts_k, parts_v = [], []
+        for lo in range(0, n_docs, chunk):
+            caps, owner = [], []
+            for d in range(lo, min(lo + chunk, n_docs)):
+                for c in docs[d]:
+                    caps.append(c)
+                    owner.append(d)
+            lens = np.fromiter((len(c) for c in caps), dtype=np.int64, count=len(caps))
+            if not len(caps) or not int(lens.sum()):
+                continue
+            flat = np.fromiter(itertools.chain.from_iterable(caps), dtype=np.int64, count=int(lens.sum()))
+            if flat.min() < 1 or flat.max() > MAX_TOKEN_ID:
+                raise ValueError("DocFreq: a word id is outside 1..%d" % MAX_TOKEN_ID)
+            T = int(lens.max())
+            cols = np.arange(T)
+            rows = np.zeros((len(caps), T + 3), dtype=np.uint64)                      # id + 1; 0 = past the string
+            rows[:, :T][cols[None, :] < lens[:, None]] = (flat + 1).astype(np.uint64)
+            owner = np.asarray(owner, dtype=np.int64)
+            key = np.zeros((len(caps), T), dtype=np.uint64)
+            pairs_k, pairs_d = [], []
+            for k in range(4):
+                key = key | (rows[:, k:k + T] << np.uint64(48 - 16 * k))
+                ok = cols[None, :] + (k + 1) <= lens[:, None]
+                pairs_k.append(key[ok])
+                pairs_d.append(np.broadcast_to(owner[:, None], ok.shape)[ok])
+            pk, pd = np.concatenate(pairs_k), np.concatenate(pairs_d)
+            o = np.lexsort((pk, pd))
+            pk, pd = pk[o], pd[o]
+            new = np.ones(len(pk), dtype=bool)
+            new[1:] = (pk[1:] != pk[:-1]) | (pd[1:] != pd[:-1])                       # an n-gram counts once per image
+            k_u, k_c = np.unique(pk[new], return_counts=True)
+            parts_k.append(k_u)
+            parts_v.append(k_c)
+        if not parts_k:
+            return cls(np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int32), n_docs)
+        keys, inv = np.unique(np.concatenate(parts_k), return_inverse=True)
+        vals = np.bincount(inv, weights=np.concatenate(parts_v), minlength=len(keys)).astype(np.int32)
+        return cls(keys.astype(np.uint64), vals, n_docs)
 
     def save(self, path):
         """An .npz of keys, vals, n_docs, max_len_b and sep_id (-1 = unknown), nothing else."""
