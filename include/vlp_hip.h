@@ -702,6 +702,39 @@ typedef struct {
 } vlp_token_logprob_bwd_args;
 int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* stream);
 
+/* The SCST policy pi_T = softmax(logits / T) of one chosen token per row, and its entropy (--scst_temperature, --scst_entropy_weight).  For
+ * one row, l_v the fp16 logit of column v < V as fp32 (columns >= V do not exist), T = temperature, finite and > 0:
+ *   z_v = l_v / T;  lse = log sum_v exp(z_v);  q_v = exp(z_v - lse);  logp = z_id - lse  (id clamped to [0, V));
+ *   H = -sum_v q_v log q_v, with 0 log 0 = 0: a column with q_v = 0 (a -inf logit included) adds nothing.
+ * fwd writes lse (that of z), logp and, when `entropy` is not NULL, H; computed as H = log S - A / S with d = (l_v - l_max) / T,
+ * S = sum e^d, A = sum e^d d (subtracted before divided, so a small T does not overflow).
+ * bwd takes the per-row upstream gradients g[r] = dL/dlogp_r and h[r] = dL/dH_r (optional; either sign, both carry the loss scale):
+ *   dlogits[r, v] = (1/T) (g[r] ([v == id] - q_v) - h[r] q_v (log q_v + H_r))  for v < V, 0 for V <= v < ld_dlogits;
+ * a column with q_v = 0 gets exactly 0 from the entropy term.  `entropy` (the forward's) is read only with h and required then.
+ * T = 1 without entropy / h gives vlp_token_logprob_fwd / _bwd's bits.  VLP_ERR_BAD_ARG before any launch: a temperature that is not finite
+ * or <= 0 (or subnormal: its reciprocal overflows), a null required operand, the layout / alignment rules of vlp_token_logprob_*, h without entropy. */
+typedef struct {
+    const void* logits; int64_t ld_logits;    /* [rows, V] fp16 */
+    const int64_t* ids;                       /* [rows] */
+    float* logp; float* lse;                  /* [rows] out */
+    float* entropy;                           /* [rows] out, or NULL */
+    int32_t rows, V;
+    float temperature;
+} vlp_token_policy_fwd_args;
+int vlp_token_policy_fwd(const vlp_token_policy_fwd_args* a, void* stream);
+typedef struct {
+    const void* logits; int64_t ld_logits;
+    const int64_t* ids;
+    const float* lse;                         /* written by vlp_token_policy_fwd with the same temperature */
+    const float* entropy;                     /* written by vlp_token_policy_fwd; NULL without h */
+    const float* g;                           /* [rows] device upstream gradient of logp */
+    const float* h;                           /* [rows] device upstream gradient of the entropy, or NULL */
+    void* dlogits; int64_t ld_dlogits;        /* [rows, ld] fp16 out */
+    int32_t rows, V;
+    float temperature;
+} vlp_token_policy_bwd_args;
+int vlp_token_policy_bwd(const vlp_token_policy_bwd_args* a, void* stream);
+
 /* CIDEr-D of id strings (SCST, the reward the reference computes on the host: scst_utils.py:36-63 with pycocoevalcap's Cider(df='corpus')).
  * The specification is vlp_amd/scst.py CiderD.compute_score on the strings array_to_str makes:
  *   - a string is the ids of a row up to AND INCLUDING the first 0, or all T ids without one; nothing behind the first 0 is read as text.

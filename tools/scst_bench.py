@@ -29,7 +29,10 @@ reward phase scores K*B captions.  --batches stays the number of images.  Its de
 its samples (1 = the one-sample estimator above) and its sample_decode_token_step_ms (the phase over the T token steps).
 --cider_weight / --bleu_weight other than 1 / 0 time the step of --scst_cider_weight / --scst_bleu_weight: the reward phase then scores sentence
 BLEU-4 as well (vlp_bleu4 on the device, vlp_amd.scst.Bleu on the host).  With 1 / 0 scst_step is called without the keyword, as before.  Their
-default --out is profiles/scst_bleu.json; each record names its reward_weights."""
+default --out is profiles/scst_bleu.json; each record names its reward_weights.
+--temperature / --entropy_weight other than 1 / 0 time the step of --scst_temperature / --scst_entropy_weight: score_fwd then ends with
+vlp_token_policy_fwd and score_bwd starts with vlp_token_policy_bwd.  Their default --out is profiles/scst_policy.json; each record names its
+temperature and entropy_weight."""
 import argparse
 import json
 import os
@@ -80,7 +83,7 @@ def seeded_table(n, n_docs=113287, vocab=28996, seed=5):
     return DocFreq(key, rng.randint(1, n_docs + 1, size=len(key)).astype(np.int32), n_docs, 20, S.SEP_ID)
 
 
-def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1, weights=(1.0, 0.0)):
+def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1, weights=(1.0, 0.0), temperature=1.0, entropy_weight=0.0):
     cfg = BertConfig(28996, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, type_vocab_size=6)
     torch.manual_seed(0)
     m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=100).half().to(dev)
@@ -115,12 +118,14 @@ def bench(B, steps, warmup, dev, reward="host", refs=1, df=None, samples=1, weig
         clock["rec"] = it >= warmup
         mark(None)                          # the step starts here
         R.scst_step(m, opt, batch, 1e-6, 100, crit, mark=mark, reward_on=reward, df=df, **({"samples": samples} if samples > 1 else {}),
-                    **({"reward_weights": weights} if tuple(weights) != (1.0, 0.0) else {}))
+                    **({"reward_weights": weights} if tuple(weights) != (1.0, 0.0) else {}),
+                    **({"temperature": temperature} if temperature != 1.0 else {}), **({"entropy_weight": entropy_weight} if entropy_weight else {}))
     L = batch.input_ids.shape[1]
     out = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v))} for k, v in times.items()}
     out["step_ms_sum_of_medians"] = float(sum(out[k]["median_ms"] for k in phases))
     out.update(B=B, L=L, T=L - 102, scoring_length=102 + 2 * (L - 102) - 1, layers=12, vocab=28996, steps=steps, warmup=warmup, reward=reward, refs=refs,
-               df_ngrams=0 if df is None else len(df), samples=samples, reward_weights=list(weights), sample_decode_token_step_ms=out["sample_decode"]["median_ms"] / (L - 102))
+               df_ngrams=0 if df is None else len(df), samples=samples, reward_weights=list(weights), temperature=temperature,
+               entropy_weight=entropy_weight, sample_decode_token_step_ms=out["sample_decode"]["median_ms"] / (L - 102))
     return out
 
 
@@ -136,17 +141,21 @@ def main():
                                                                         "2..16 = K samples with a leave-one-out baseline")
     ap.add_argument("--cider_weight", type=float, default=1.0, help="the weight of CIDEr-D in the reward (--scst_cider_weight)")
     ap.add_argument("--bleu_weight", type=float, default=0.0, help="the weight of sentence BLEU-4 in the reward (--scst_bleu_weight); 0 = CIDEr-D alone")
-    ap.add_argument("--out", default=None, help="default: profiles/scst_step.json for --reward host --refs 1, profiles/scst_reward_df.json with --df, "
+    ap.add_argument("--temperature", type=float, default=1.0, help="the temperature of the sampled policy (--scst_temperature)")
+    ap.add_argument("--entropy_weight", type=float, default=0.0, help="the weight of the entropy bonus (--scst_entropy_weight); 0 = off")
+    ap.add_argument("--out", default=None, help="default: profiles/scst_policy.json with --temperature / --entropy_weight other than 1 / 0, else "
+                                                "profiles/scst_step.json for --reward host --refs 1, profiles/scst_reward_df.json with --df, "
                                                 "profiles/scst_samples.json with --samples above 1, "
                                                 "profiles/scst_bleu.json with reward weights other than 1 / 0, else profiles/scst_reward_device.json")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "scst_bleu.json" if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "scst_samples.json" if a.samples > 1 else "scst_reward_df.json" if a.df else
+        a.out = os.path.join(ROOT, "profiles", "scst_policy.json" if (a.temperature, a.entropy_weight) != (1.0, 0.0) else "scst_bleu.json" if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "scst_samples.json" if a.samples > 1 else "scst_reward_df.json" if a.df else
                              "scst_step.json" if (a.reward == "host" and a.refs == 1) else "scst_reward_device.json")
     dev = torch.device("cuda")
     tool = "tools/scst_bench.py --batches %s --steps %d --warmup %d --reward %s --refs %d" % (" ".join(map(str, a.batches)), a.steps, a.warmup, a.reward,
                                                                                              a.refs) + (" --df %d" % a.df if a.df else "") + (" --samples %d" % a.samples if a.samples > 1 else "") + (
-        " --cider_weight %g --bleu_weight %g" % (a.cider_weight, a.bleu_weight) if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "")
+        " --cider_weight %g --bleu_weight %g" % (a.cider_weight, a.bleu_weight) if (a.cider_weight, a.bleu_weight) != (1.0, 0.0) else "") + (
+        " --temperature %g --entropy_weight %g" % (a.temperature, a.entropy_weight) if (a.temperature, a.entropy_weight) != (1.0, 0.0) else "")
     df = seeded_table(a.df) if a.df else None
     res = {"device": torch.cuda.get_device_name(0), "note": NOTE, "runs": []}
     yardstick = os.path.realpath(a.out) == os.path.realpath(os.path.join(ROOT, "profiles", "scst_step.json"))
@@ -162,7 +171,7 @@ def main():
                     res[k] = v
         res["tools"].append(tool)
     for B in a.batches:
-        r = bench(B, a.steps, a.warmup, dev, a.reward, a.refs, df, a.samples, (a.cider_weight, a.bleu_weight))
+        r = bench(B, a.steps, a.warmup, dev, a.reward, a.refs, df, a.samples, (a.cider_weight, a.bleu_weight), a.temperature, a.entropy_weight)
         print(json.dumps(r, sort_keys=True), flush=True)
         res["runs"].append(r)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

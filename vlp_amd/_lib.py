@@ -129,6 +129,16 @@ class TokenLogprobBwdArgs(C.Structure):
                 ("rows", i32), ("V", i32)]
 
 
+class TokenPolicyFwdArgs(C.Structure):
+    _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("logp", vp), ("lse", vp), ("entropy", vp), ("rows", i32), ("V", i32),
+                ("temperature", f32)]
+
+
+class TokenPolicyBwdArgs(C.Structure):
+    _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("lse", vp), ("entropy", vp), ("g", vp), ("h", vp), ("dlogits", vp),
+                ("ld_dlogits", i64), ("rows", i32), ("V", i32), ("temperature", f32)]
+
+
 class PretextFwdArgs(C.Structure):
     _fields_ = [("vis_h", vp), ("vispe_h", vp), ("pooled", vp), ("vis_masked_pos", vp), ("probs", vp), ("sample_loss", vp), ("loss", vp),
                 ("B", i32), ("Nv", i32), ("Pm", i32), ("H", i32)]
@@ -245,6 +255,8 @@ SYMBOLS = {
     "vlp_scst_layout": (C.c_int, [C.POINTER(ScstLayoutArgs), vp]),
     "vlp_token_logprob_fwd": (C.c_int, [C.POINTER(TokenLogprobFwdArgs), vp]),
     "vlp_token_logprob_bwd": (C.c_int, [C.POINTER(TokenLogprobBwdArgs), vp]),
+    "vlp_token_policy_fwd": (C.c_int, [C.POINTER(TokenPolicyFwdArgs), vp]),
+    "vlp_token_policy_bwd": (C.c_int, [C.POINTER(TokenPolicyBwdArgs), vp]),
     "vlp_region_mask_build": (C.c_int, [vp, i32, i32, i32, vp, vp]),
     "vlp_pretext_fwd": (C.c_int, [C.POINTER(PretextFwdArgs), vp]),
     "vlp_pretext_bwd": (C.c_int, [C.POINTER(PretextBwdArgs), vp]),
@@ -776,6 +788,20 @@ def token_logprob_bwd(logits, ld, ids, lse, g, dlogits, ldd, rows, V):
     _req_cuda(logits, ids, lse, g, dlogits)
     a = TokenLogprobBwdArgs(ptr(logits), ld, ptr(ids), ptr(lse), ptr(g), ptr(dlogits), ldd, rows, V)
     _check(load().vlp_token_logprob_bwd(C.byref(a), stream_ptr()))
+
+
+def token_policy_fwd(logits, ld, ids, logp, lse, rows, V, temperature=1.0, entropy=None):
+    """logp / lse (and entropy [rows] f32, when given) of softmax(logits / temperature) at ids (include/vlp_hip.h vlp_token_policy_fwd)."""
+    _req_cuda(logits, ids, logp, lse, entropy)
+    a = TokenPolicyFwdArgs(ptr(logits), ld, ptr(ids), ptr(logp), ptr(lse), ptr(entropy), rows, V, float(temperature))
+    _check(load().vlp_token_policy_fwd(C.byref(a), stream_ptr()))
+
+
+def token_policy_bwd(logits, ld, ids, lse, g, dlogits, ldd, rows, V, temperature=1.0, h=None, entropy=None):
+    """dlogits of g . logp + h . entropy under softmax(logits / temperature); h (with the forward's entropy) is optional."""
+    _req_cuda(logits, ids, lse, g, dlogits, h, entropy)
+    a = TokenPolicyBwdArgs(ptr(logits), ld, ptr(ids), ptr(lse), ptr(entropy), ptr(g), ptr(h), ptr(dlogits), ldd, rows, V, float(temperature))
+    _check(load().vlp_token_policy_bwd(C.byref(a), stream_ptr()))
 
 
 def cider_d_workspace_bytes(G, R, T, mult):

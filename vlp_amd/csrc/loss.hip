@@ -10,7 +10,8 @@
 
 // ---------------------------------------------------------------------------------------------
 // Vocabulary-row losses.  Forward: one block per row, a max pass and a sum-exp pass give lse[row] = m + log S; a policy says whether
-// A = sum (z - m) is accumulated as well (SUM_D) and what the row's second output is.  Backward: grid (chunks of the row, rows), every
+// A = sum (z - m) is accumulated as well (SUM_D) and what the row's second output is; TEMPERED scales z - m by the policy's 1 / T (the row is
+// that of z / T, lse included) and SUM_ED accumulates A = sum e^d d, the entropy's sum.  Backward: grid (chunks of the row, rows), every
 // 8-column chunk of [0, ldd) is written -- the policy's per-element expression below V, zeros in the pad columns [V, ldd) and on a row the
 // policy zeroes.  Labels are clamped to [0, V).
 // ---------------------------------------------------------------------------------------------
@@ -25,16 +26,21 @@ __global__ __launch_bounds__(CE_THREADS) void row_lse_kernel(const f16* __restri
     mx = block_reduce_max<CE_THREADS>(mx, sh);
     float s = 0.f, a = 0.f;
     row_visit<CE_THREADS, true>(x, 0, V, [&](float z, int) {
-        const float d = z - mx;
-        s += __expf(d);
+        float d = z - mx;
+        if constexpr (Policy::TEMPERED) d = d * p.inv_T;    // subtract, then scale: d <= 0 whatever T is
+        const float e = __expf(d);
+        s += e;
         if constexpr (Policy::SUM_D) a += d;
+        if constexpr (Policy::SUM_ED) a += d == -INFINITY ? 0.f : e * d;      // a -inf logit: 0 log 0 = 0, never 0 * inf
     });
     s = block_reduce_sum<CE_THREADS>(s, sh);
-    if constexpr (Policy::SUM_D) a = block_reduce_sum<CE_THREADS>(a, sh);
+    if constexpr (Policy::SUM_D || Policy::SUM_ED) a = block_reduce_sum<CE_THREADS>(a, sh);
     if (threadIdx.x == 0) {
         const float ls = __logf(s);
         int64_t lab = labels[row];
         lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
+        if constexpr (Policy::TEMPERED) mx = mx / p.T;      // max of z / T
+        if constexpr (Policy::SUM_ED) a = a / s;            // sum q_v d_v: the entropy is log S - A / S
         lse[row] = mx + ls;
         out[row] = p.row_out(x, lab, V, mx, ls, a);
     }
@@ -49,7 +55,7 @@ __global__ __launch_bounds__(CE_THREADS) void dlogits_row_kernel(const f16* __re
     const int row = blockIdx.y;
     const f16* x = logits + (int64_t)row * ld;
     f16* d = dl + (int64_t)row * ldd;
-    const float c = p.row_const(rc, rc_scale, row);
+    const auto c = p.row_const(rc, rc_scale, row);          // a float, or the policy's struct of per-row values
     const float l = lse[row];
     int64_t lab = labels[row];
     lab = lab < 0 ? 0 : (lab >= V ? V - 1 : lab);
@@ -102,7 +108,7 @@ static int dlogits_row_launch(const char* who, int min_V, const void* logits, in
 
 // cross entropy: row_loss[row] = lse - logit[label];  d row_loss / d z[w] = p[w] - [w == label], times coef[row] * grad_scale
 struct CeRow {
-    static constexpr bool SUM_D = false;
+    static constexpr bool SUM_D = false, TEMPERED = false, SUM_ED = false;
     DEVFN float row_out(const f16* x, int64_t lab, int, float mx, float ls, float) const { return (mx + ls) - (float)x[lab]; }
 };
 struct CeGrad {
@@ -179,7 +185,7 @@ extern "C" int vlp_mlm_loss_bwd(const vlp_mlm_loss_bwd_args* a, void* stream) {
 // so the two passes of row_lse_kernel give the row's KL without a third one.
 // ---------------------------------------------------------------------------------------------
 struct CeLsRow {
-    static constexpr bool SUM_D = true;
+    static constexpr bool SUM_D = true, TEMPERED = false, SUM_ED = false;
     float smooth, confidence, q_log_q; int ignore;
     DEVFN float row_out(const f16* x, int64_t lab, int V, float mx, float ls, float a) const {
         float r = 0.f;
@@ -234,7 +240,7 @@ extern "C" int vlp_mlm_loss_ls_bwd(const vlp_mlm_loss_ls_bwd_args* a, void* stre
 // g is a per-row upstream gradient of either sign (it carries the loss scale).
 // ---------------------------------------------------------------------------------------------
 struct TokenLogpRow {
-    static constexpr bool SUM_D = false;
+    static constexpr bool SUM_D = false, TEMPERED = false, SUM_ED = false;
     DEVFN float row_out(const f16* x, int64_t id, int, float mx, float ls, float) const { return (float)x[id] - (mx + ls); }
 };
 struct TokenLogpGrad {
@@ -255,6 +261,69 @@ extern "C" int vlp_token_logprob_bwd(const vlp_token_logprob_bwd_args* a, void* 
     VLP_ENTER(a->logits, "vlp_token_logprob_bwd");
     return dlogits_row_launch("vlp_token_logprob_bwd", 1, a->logits, a->ld_logits, a->ids, a->lse, a->g, nullptr, a->dlogits, a->ld_dlogits, a->rows, a->V,
                               TokenLogpGrad{}, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The SCST policy pi_T = softmax(logits / T) of one chosen token per row, with its entropy (include/vlp_hip.h vlp_token_policy_fwd):
+//   z = l / T, lse = logsumexp(z), q = exp(z - lse), logp = z_id - lse, H = -sum q log q = log S - A / S with d = (l - max) / T,
+//   S = sum e^d, A = sum e^d d (row_lse_kernel's second pass);
+//   dlogits[v] = (g / T) ([v == id] - q_v) - (h / T) q_v (log q_v + H), the entropy term skipped where q_v == 0.
+// Elements and upstream gradients are scaled by 1 / T (one rounding, the host's); the forward's two per-row values are divided by T.  T == 1
+// without entropy / h computes TokenLogpRow's / TokenLogpGrad's expressions: 1 * d, 1 * z - l, 1 * g and x / 1 are exact.
+// ---------------------------------------------------------------------------------------------
+template <bool ENT>
+struct TokenPolicyRow {
+    static constexpr bool SUM_D = false, TEMPERED = true, SUM_ED = ENT;
+    float T, inv_T; float* entropy;
+    // mx: the max of z; a: sum q_v d_v.  One block per row (row_lse_kernel): the row is blockIdx.x
+    DEVFN float row_out(const f16* x, int64_t id, int, float mx, float ls, float a) const {
+        if constexpr (ENT) entropy[blockIdx.x] = ls - a;
+        return (float)x[id] / T - (mx + ls);
+    }
+};
+struct TokenPolicyRc { float c, ch, H; };          // g / T, h / T (as products with 1 / T) and the row's entropy
+template <bool ENT>
+struct TokenPolicyGrad {
+    float inv_T; const float* h; const float* entropy;
+    DEVFN bool zero_row(int64_t) const { return false; }
+    DEVFN auto row_const(const float* g, const float*, int row) const {
+        // products, not quotients: a thread of this grid handles one or two chunks, and a division ahead of them showed in the launch's time
+        if constexpr (ENT) return TokenPolicyRc{g[row] * inv_T, h[row] * inv_T, entropy[row]};
+        else return g[row] * inv_T;
+    }
+    DEVFN float elem(float c, float z, float l, int v, int64_t id) const { return c * ((v == id ? 1.f : 0.f) - __expf(z * inv_T - l)); }
+    DEVFN float elem(const TokenPolicyRc& r, float z, float l, int v, int64_t id) const {
+        const float lq = z * inv_T - l, q = __expf(lq);
+        const float gt = r.c * ((v == id ? 1.f : 0.f) - q);
+        return q > 0.f ? gt - r.ch * (q * (lq + r.H)) : gt;              // q == 0 (a -inf logit, or underflow): no 0 * inf
+    }
+};
+
+// finite and > 0 (false for a NaN); a subnormal T, whose reciprocal is inf, is refused with them
+static bool policy_temperature_ok(float T) { return T >= 1.17549435e-38f && T <= 3.402823466e+38f; }
+
+extern "C" int vlp_token_policy_fwd(const vlp_token_policy_fwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->ids && a->logp && a->lse, "vlp_token_policy_fwd: null operand");
+    VLP_ENTER(a->logits, "vlp_token_policy_fwd");
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 0, "vlp_token_policy_fwd: layout");
+    VLP_CHECK_ARG(policy_temperature_ok(a->temperature), "vlp_token_policy_fwd: temperature must be finite and > 0");
+    if (a->entropy)
+        return row_lse_launch("vlp_token_policy_fwd", "vlp_token_policy_fwd: layout", a->logits, a->ld_logits, a->ids, a->lse, a->logp, a->rows, a->V,
+                              TokenPolicyRow<true>{a->temperature, 1.f / a->temperature, a->entropy}, (hipStream_t)stream);
+    return row_lse_launch("vlp_token_policy_fwd", "vlp_token_policy_fwd: layout", a->logits, a->ld_logits, a->ids, a->lse, a->logp, a->rows, a->V,
+                          TokenPolicyRow<false>{a->temperature, 1.f / a->temperature, nullptr}, (hipStream_t)stream);
+}
+extern "C" int vlp_token_policy_bwd(const vlp_token_policy_bwd_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->ids && a->lse && a->g && a->dlogits, "vlp_token_policy_bwd: null operand");
+    VLP_ENTER(a->logits, "vlp_token_policy_bwd");
+    VLP_CHECK_ARG(policy_temperature_ok(a->temperature), "vlp_token_policy_bwd: temperature must be finite and > 0");
+    VLP_CHECK_ARG(!a->h || a->entropy, "vlp_token_policy_bwd: h needs the entropy the forward saved");
+    const float T = a->temperature;
+    if (a->h)
+        return dlogits_row_launch("vlp_token_policy_bwd", 1, a->logits, a->ld_logits, a->ids, a->lse, a->g, nullptr, a->dlogits, a->ld_dlogits, a->rows,
+                                  a->V, TokenPolicyGrad<true>{1.f / T, a->h, a->entropy}, stream);
+    return dlogits_row_launch("vlp_token_policy_bwd", 1, a->logits, a->ld_logits, a->ids, a->lse, a->g, nullptr, a->dlogits, a->ld_dlogits, a->rows,
+                              a->V, TokenPolicyGrad<false>{1.f / T, nullptr, nullptr}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -47,7 +47,7 @@ class VlpPerformanceWarning(UserWarning):
 
 class _State(object):
     """What one forward leaves behind for its backward."""
-    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids")
+    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids", "policy")
 
     def __init__(self):
         self.gen = self.B = self.L = self.P = 0      # engine generation, batch, sequence length, masked positions per sample
@@ -60,6 +60,7 @@ class _State(object):
         self.pretext = None          # (pretext workspace, vis_masked_pos) of a mask_image_regions forward
         self.task_labels = None      # set by the loss of this forward (mlm_loss / vqa_loss / score_samples), read by its backward
         self.mlm_smooth = None       # label-smoothed loss: the scalar arguments of the matching backward launch
+        self.policy = None           # score_samples with a temperature / entropy: (temperature, entropy rows or None) of vlp_token_policy_fwd
 
 
 class Engine(object):
@@ -1376,12 +1377,19 @@ class Engine(object):
     # ------------------------------------------------------------------------------------------
     # self-critical sequence training: the gradient of the sampled captions' log-probabilities
     # ------------------------------------------------------------------------------------------
-    def score_samples(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, sample_ids, mask_word_id):
+    def score_samples(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, sample_ids, mask_word_id,
+                      temperature=1.0, entropy=False):
         """Teacher-forced scoring of sampled captions (the gradient the reference gets by running its incremental decoder under autograd,
         modeling.py:1210-1251 / run_img2txt_dist.py:506-507).  Takes the decoder's inputs and its sampled ids [B, T]; builds the scoring
         sequence on the device (vlp_scst_layout: every sampled position sees exactly the hidden states the incremental decoder computed),
         runs the training forward on it densely and without dropout, the LM head over the T [MASK] slots and vlp_token_logprob_fwd.
-        Returns (state, logp [B, T] f32 -- a workspace view, overwritten by the next call); backward(state, None, "logprob", g_rows=...)."""
+        Returns (state, logp [B, T] f32 -- a workspace view, overwritten by the next call); backward(state, None, "logprob", g_rows=...).
+        temperature T != 1 or entropy=True score the policy softmax(logits / T) with vlp_token_policy_fwd instead: logp is that policy's, and
+        with entropy=True the return is (state, logp, entropy), entropy [B, T] f32 the policy's entropy at every position (a workspace view
+        next to logp; backward(..., h_rows=...) takes its upstream gradient).  (1.0, False) issues the launches of a call without them."""
+        temperature, entropy = float(temperature), bool(entropy)
+        if not (0.0 < temperature < float("inf")):
+            raise RuntimeError("vlp_amd: score_samples needs a finite temperature > 0 (got %r)" % temperature)
         self.pack()
         model = self._model()
         V = model.config.vocab_size
@@ -1411,8 +1419,15 @@ class Engine(object):
         st = self.forward(vis_feats, vis_pe, sw["ids"], sw["seg"], sw["mask"], sw["mpos"], True, True, False, position_ids=sw["pos"],
                           dropout=False, dense=True)
         st.task_labels = sw["labels"].view(-1)
-        K.token_logprob_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V)
-        return st, sw["logp"]
+        if temperature == 1.0 and not entropy:
+            K.token_logprob_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V)
+            return st, sw["logp"]
+        if entropy and "entropy" not in sw:
+            sw["entropy"] = torch.empty(B, T, device=self.device, dtype=torch.float32)
+        ent = sw["entropy"] if entropy else None
+        K.token_policy_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V, temperature=temperature, entropy=ent)
+        st.policy = (temperature, ent)
+        return (st, sw["logp"], ent) if entropy else (st, sw["logp"])
 
     # ------------------------------------------------------------------------------------------
     # backward
@@ -1504,11 +1519,12 @@ class Engine(object):
         on_side(last_wgrad)
         self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre1)
 
-    def backward(self, st, gscale, task, g_pretext=None, g_rows=None):
+    def backward(self, st, gscale, task, g_pretext=None, g_rows=None, h_rows=None):
         """gscale: device f32 tensor [1] = upstream gradient of the task loss (x loss scale); g_pretext: the same for the pretext loss of
         a mask_image_regions forward.  task="logprob" (a score_samples forward): g_rows = device f32 [B*T], the upstream gradient of every
-        sampled token's log-probability (x loss scale) in place of the masked-LM loss.  Writes every parameter gradient into the flat
-        gradient buffers."""
+        sampled token's log-probability (x loss scale) in place of the masked-LM loss; h_rows (optional, a score_samples(entropy=True)
+        forward): the same for every position's entropy.  A forward scored with a temperature or an entropy runs vlp_token_policy_bwd, any
+        other vlp_token_logprob_bwd.  Writes every parameter gradient into the flat gradient buffers."""
         if st.gen != self.gen:
             raise RuntimeError("vlp_amd: the activations of this forward were overwritten by a later forward "
                                "(one in-flight forward per model; run backward before the next forward)")
@@ -1603,7 +1619,13 @@ class Engine(object):
             if task == "logprob":
                 if g_rows is None or g_rows.numel() != R:
                     raise RuntimeError("vlp_amd: backward(task='logprob') needs g_rows with %d elements" % R)
-                K.token_logprob_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V)
+                if h_rows is not None and (st.policy is None or st.policy[1] is None or h_rows.numel() != R):
+                    raise RuntimeError("vlp_amd: backward(task='logprob', h_rows=...) needs a score_samples(entropy=True) forward and %d elements" % R)
+                if st.policy is None or (st.policy[0] == 1.0 and h_rows is None):
+                    K.token_logprob_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V)
+                else:
+                    K.token_policy_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], g_rows, ws["dlogits"], Vp, R, V, temperature=st.policy[0],
+                                       h=h_rows, entropy=None if h_rows is None else st.policy[1].view(-1))
             elif st.mlm_smooth is None:
                 K.mlm_loss_bwd(ws["logits"], Vp, st.task_labels, ws["lse_ce"], ws["coef"], gscale, ws["dlogits"], Vp, R, V)
             else:

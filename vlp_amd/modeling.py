@@ -462,18 +462,26 @@ class _LossFn(torch.autograd.Function):
 
 class _LogprobFn(torch.autograd.Function):
     """The sampled captions' log-probabilities [B, T] of a train-mode `sample_mode='sample'` forward as an autograd output: any torch loss
-    on them (RewardCriterion, scst_utils.py:66-78) reaches Engine.backward(task="logprob") with dL/dlogp, which carries the fp16 loss scale."""
+    on them (RewardCriterion, scst_utils.py:66-78) reaches Engine.backward(task="logprob") with dL/dlogp, which carries the fp16 loss scale.
+    With `entropy` (the policy's entropy rows of the same scoring pass, return_entropy=True) there is a second differentiable output, and
+    the backward hands dL/dlogp and dL/dentropy to the engine in one call."""
 
     @staticmethod
-    def forward(ctx, anchor, logp, engine, state):
-        ctx.engine, ctx.state = engine, state
-        return logp.clone()
+    def forward(ctx, anchor, logp, engine, state, entropy=None):
+        ctx.engine, ctx.state, ctx.has_entropy = engine, state, entropy is not None
+        if entropy is None:
+            return logp.clone()
+        return logp.clone(), entropy.clone()
 
     @staticmethod
-    def backward(ctx, grad):
+    def backward(ctx, grad, grad_h=None):
         g = grad.detach().to(torch.float32).contiguous().reshape(-1)
-        ctx.engine.backward(ctx.state, None, "logprob", g_rows=g)
-        return None, None, None, None
+        if not ctx.has_entropy:
+            ctx.engine.backward(ctx.state, None, "logprob", g_rows=g)
+            return None, None, None, None
+        h = grad_h.detach().to(torch.float32).contiguous().reshape(-1)
+        ctx.engine.backward(ctx.state, None, "logprob", g_rows=g, h_rows=h)
+        return None, None, None, None, None
 
 
 class BertForPreTrainingLossMask(PreTrainedBertModel):
@@ -629,16 +637,21 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         return self.__dict__["_engine"]
 
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy",
-                n_samples=1, temperature=1.0, top_k=0, top_p=1.0):
+                n_samples=1, temperature=1.0, top_k=0, top_p=1.0, return_entropy=False):
         """Returns (output_ids [B, n], output_probs [B, n]) with n = token_type_ids.shape[1] - input_ids.shape[1], as :1253.
         output_probs are the maximal prediction scores (logits), exactly what the reference returns in greedy mode (:1228).
         n_samples = K > 1 with sample_mode='sample' (not in the reference): K draws per image, returned sample-major as [K*B, n] ids and
         log-probabilities (row k*B + b is sample k of image b; Engine.decode_sample_group); in train() mode with gradients enabled the
         log-probabilities are differentiable, scored as K*B independent sequences.
-        temperature / top_k / top_p (not in the reference; sample_mode='sample' without beam search, eval or no_grad only): any value other
+        temperature / top_k / top_p (not in the reference; sample_mode='sample' without beam search): any value other
         than (1, 0, 1) draws every token from softmax(logits / temperature) restricted to the top_k largest logits (0 = all; ties kept) and
         then to the smallest set of largest logits holding a mass of top_p (vlp_sample_rows_filtered, Engine.decode_sample_group for every
-        n_samples >= 1); the second output is the log-probability under that distribution.  (1, 0, 1) changes nothing."""
+        n_samples >= 1); the second output is the log-probability under that distribution.  (1, 0, 1) changes nothing.  In train() mode
+        with gradients enabled a temperature alone (top_k 0, top_p 1) is the tempered policy of SCST: the ids are that decode's and the
+        log-probabilities are softmax(logits / temperature)'s, differentiable through the tempered scoring pass (vlp_token_policy_fwd /
+        _bwd); top_k / top_p stay refused there.
+        return_entropy=True (train() mode with gradients and sample_mode='sample' only): returns (ids, logp, entropy), all [rows, n]; entropy
+        is the sampled policy's entropy at every position, a second differentiable output of the same scoring pass."""
         if not input_ids.is_cuda:
             raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only (inputs must be on the GPU); there is no CPU path")
         n_samples = int(n_samples)
@@ -654,11 +667,24 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             if n_samples < 1:
                 raise ValueError("n_samples=%d: n_samples >= 1" % n_samples)
             if self.training and torch.is_grad_enabled():
-                raise ValueError("%s in train() mode with gradients enabled: the scoring pass differentiates the unfiltered log-softmax, a "
-                                 "policy gradient of the filtered draw would be wrong; call under eval() or torch.no_grad()" % what)
+                if (top_k, top_p) != (0, 1.0):
+                    raise ValueError("%s in train() mode with gradients enabled: the scoring pass differentiates the unfiltered log-softmax, a "
+                                     "policy gradient of the filtered draw would be wrong; call under eval() or torch.no_grad()" % what)
+                return self._sample_scored(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, n_samples, temperature,
+                                           return_entropy, group=True)
+            if return_entropy:
+                raise ValueError("return_entropy=True needs train() mode with gradients enabled (the entropy comes from the scoring pass)")
             with torch.no_grad():
                 return self.engine.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
                                                        n_samples, temperature=temperature, top_k=top_k, top_p=top_p)
+        if return_entropy:
+            if sample_mode != "sample" or self.search_beam_size > 1 or not (self.training and torch.is_grad_enabled()):
+                raise ValueError("return_entropy=True needs sample_mode='sample' without beam search in train() mode with gradients enabled (the "
+                                 "entropy is that of the sampled policy, computed by the scoring pass)")
+            if n_samples < 1:
+                raise ValueError("n_samples=%d: n_samples >= 1" % n_samples)
+            return self._sample_scored(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, n_samples, 1.0, True,
+                                       group=n_samples != 1)
         if n_samples != 1:
             if n_samples < 1 or sample_mode != "sample":
                 raise ValueError("n_samples=%d needs sample_mode='sample' and n_samples >= 1" % n_samples)
@@ -693,6 +719,27 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         with torch.no_grad():
             return self.engine.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
                                              sample=(sample_mode == "sample"))
+
+    def _sample_scored(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, n_samples, temperature, entropy, group):
+        """SCST with a tempered policy and / or the entropy output: draw n_samples captions per image from softmax(logits / temperature)
+        (group: Engine.decode_sample_group, the captured path; else decode_greedy(sample=True), the draw of a plain one-sample call), then
+        score them under the same policy.  Returns (ids, logp) or (ids, logp, entropy), the last two differentiable."""
+        eng = self.engine
+        with torch.no_grad():
+            if group:
+                ids, _ = eng.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
+                                                 n_samples, temperature=temperature)
+            else:
+                ids, _ = eng.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id, sample=True)
+
+        def tiled(t):                        # row k*B + b of the scoring batch is image b
+            return t if n_samples == 1 else t.repeat(n_samples, *([1] * (t.dim() - 1)))
+        out = eng.score_samples(tiled(vis_feats), tiled(vis_pe), tiled(input_ids), tiled(token_type_ids), tiled(position_ids),
+                                tiled(attention_mask), ids, self.mask_word_id, temperature=temperature, entropy=entropy)
+        if not entropy:
+            return ids, _LogprobFn.apply(eng._anchor, out[1], eng, out[0])
+        logp, ent = _LogprobFn.apply(eng._anchor, out[1], eng, out[0], out[2])
+        return ids, logp, ent
 
     # ---- beam search: host side (what the reference also does on the host) -------------------------------
     def _ngram_blocker(self, batch_size, vocab_size):

@@ -171,6 +171,15 @@ def build_parser():
                         "vlp_amd.scst.Bleu) in the reward; 0 = off.  Works with either --scst_reward (on the device one more kernel, vlp_bleu4, "
                         "scores, mixes and baselines), either --scst_refs, any --scst_df (which keeps applying to CIDEr-D only) and any "
                         "--scst_samples.  Weights must be finite and not negative, and not both 0")
+    p.add_argument("--scst_temperature", type=float, default=1.0, metavar="T",
+                   help="--scst: the sampled captions are drawn from softmax(logits / T) and the policy gradient differentiates that same "
+                        "tempered policy (vlp_token_policy_fwd / _bwd); the greedy baseline of --scst_samples 1 does not depend on it.  T must be "
+                        "finite and > 0; 1, the default, is the reference's policy")
+    p.add_argument("--scst_entropy_weight", type=float, default=0.0, metavar="W",
+                   help="--scst: subtracts W x the mean entropy of the sampled policy (over the positions RewardCriterion counts) from the loss, "
+                        "the usual remedy when the samples collapse onto the greedy caption; the entropy and its gradient come from the scoring "
+                        "pass's vocabulary-row kernels and the training log carries the mean entropy.  W must be finite and >= 0; 0 = off.  Both "
+                        "flags combine freely with --scst_samples, --scst_reward, --scst_refs, --scst_df and the reward weights")
     return p
 
 
@@ -217,6 +226,14 @@ def derive_args(args):
             check_reward_weights(args.scst_cider_weight, args.scst_bleu_weight)
         except ValueError as e:
             raise ValueError("--scst_cider_weight %r --scst_bleu_weight %r: %s" % (args.scst_cider_weight, args.scst_bleu_weight, e))
+    if not (0.0 < args.scst_temperature < float("inf")):
+        raise ValueError("--scst_temperature %r: the temperature of the sampled policy must be finite and > 0" % args.scst_temperature)
+    if not (0.0 <= args.scst_entropy_weight < float("inf")):
+        raise ValueError("--scst_entropy_weight %r: the weight of the entropy bonus must be finite and >= 0" % args.scst_entropy_weight)
+    if args.scst_temperature != 1.0 and not args.scst:
+        raise ValueError("--scst_temperature %r needs --scst (it is the temperature of the policy self-critical training samples)" % args.scst_temperature)
+    if args.scst_entropy_weight != 0.0 and not args.scst:
+        raise ValueError("--scst_entropy_weight %r needs --scst (it weighs the entropy bonus of the self-critical loss)" % args.scst_entropy_weight)
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -367,7 +384,7 @@ def scst_doc_freq(args):
 
 
 def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, accumulate=False, accum_steps=1, mark=None, reward_on="host", df=None,
-              samples=1, reward_weights=(1.0, 0.0)):
+              samples=1, reward_weights=(1.0, 0.0), temperature=1.0, entropy_weight=0.0, stats=None):
     """One self-critical step (run_img2txt_dist.py:486-523, then :567-585): a greedy decode in eval() mode as the baseline, a sampled decode in
     train() mode whose log-probabilities are differentiable (BertForSeq2SeqDecoder, Engine.score_samples), the CIDEr-D reward of sample minus
     baseline (vlp_amd.scst, on the host) and RewardCriterion.  Returns (loss, mean reward) as device tensors.  mark(phase), if given, is
@@ -381,7 +398,11 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     (self_critical_reward_group / _group_device).  There is no greedy decode and no "greedy_decode" phase; the log-probabilities, the reward
     and RewardCriterion run over the K*B rows (row k*B + b is sample k of image b).
     reward_weights (--scst_cider_weight, --scst_bleu_weight): the score of a caption is cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4,
-    in whichever of the five reward functions the step calls; (1, 0) calls them as before.  The phase marks do not change."""
+    in whichever of the five reward functions the step calls; (1, 0) calls them as before.  The phase marks do not change.
+    temperature (--scst_temperature) T != 1: the samples are drawn from softmax(logits / T) and the log-probabilities differentiated are that
+    policy's; the greedy baseline is unaffected (an argmax does not depend on T).  entropy_weight (--scst_entropy_weight) W > 0: the loss is
+    vlp_amd.scst.policy_loss, RewardCriterion - W x the masked mean entropy of the sampled policy; `stats`, if a dict, then receives that mean
+    as stats["entropy"] (a device tensor).  (1, 0) is the step without them, call for call."""
     if mark is None:
         def mark(phase):
             pass
@@ -397,17 +418,28 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
     samples = int(samples)
     if samples < 1:
         raise ValueError("scst_step: samples must be >= 1 (got %d)" % samples)
+    temperature, entropy_weight = float(temperature), float(entropy_weight)
+    if not (0.0 < temperature < float("inf")) or not (0.0 <= entropy_weight < float("inf")):
+        raise ValueError("scst_step: temperature must be finite and > 0, entropy_weight finite and >= 0 (got %r, %r)" % (temperature, entropy_weight))
+    pkw = {}                                              # the policy keywords: none at (1, 0), the call as it always was
+    if temperature != 1.0:
+        pkw["temperature"] = temperature
+    if entropy_weight > 0:
+        pkw["return_entropy"] = True
+    entropy = None
     if samples == 1:
         model.eval()
         with torch.no_grad():
             greedy_raw, _ = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="greedy")
         mark("greedy_decode")
         model.train()
-        gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample")
+        out = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample", **pkw)
     else:
         model.train()
-        gen_raw, sample_logprobs = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample",
-                                         n_samples=samples)
+        out = model(img, vis_pe, input_dummy, segment_ids, position_ids, input_mask, task_idx=task_idx, sample_mode="sample", n_samples=samples, **pkw)
+    gen_raw, sample_logprobs = out[0], out[1]
+    if entropy_weight > 0:
+        entropy = out[2]
     mark("sample_forward")
     gen_result = clean_captions(gen_raw, synthetic.SEP_ID, synthetic.PAD_ID)
     gt_ids = input_ids[:, len_vis_input + 2:]
@@ -437,7 +469,13 @@ def scst_step(model, optimizer, batch, lr_this_step, len_vis_input, rl_crit, acc
         reward = torch.from_numpy(reward).float().to(gen_result.device)
         mean_reward = reward.mean()
         mark("reward_host")
-    loss = rl_crit(sample_logprobs, gen_result, reward)
+    if entropy is None:
+        loss = rl_crit(sample_logprobs, gen_result, reward)
+    else:
+        from .scst import policy_loss
+        loss, mean_h = policy_loss(sample_logprobs, gen_result, reward, entropy=entropy, entropy_weight=entropy_weight, crit=rl_crit)
+        if isinstance(stats, dict):
+            stats["entropy"] = mean_h
     bwd = loss / accum_steps if accum_steps > 1 else loss
     if hasattr(optimizer, "backward"):
         optimizer.backward(bwd)
@@ -567,11 +605,16 @@ def main(argv=None):
             optimizer.dynamic_loss_scale = True
         global_step = math.floor(recover_step * t_total * 1. / args.num_train_epochs)      # :337-338
     logger.info("***** Running training *****  batch %d, steps %d", args.train_batch_size, t_total)
+    scst_policy = {}                     # scst_step's policy keywords: none at the defaults
+    if args.scst and args.scst_temperature != 1.0:
+        scst_policy["temperature"] = args.scst_temperature
+    if args.scst and args.scst_entropy_weight > 0:
+        scst_policy.update(entropy_weight=args.scst_entropy_weight, stats={})
     model.train()
     stop_after = args.stop_after_epoch if args.stop_after_epoch > 0 else args.num_train_epochs
     for i_epoch in range((recover_step or 0) + 1, min(args.num_train_epochs, stop_after) + 1):
         t0 = time.time()
-        losses, rewards = [], []
+        losses, rewards, entropies = [], [], []
         if loader is not None:
             loader.set_epoch(i_epoch - 1)                                                             # train_sampler.set_epoch(i_epoch-1), :455
         for step, batch in enumerate(loader if loader is not None else synthetic_batches(args, device, steps_per_epoch, args.global_rank)):
@@ -580,8 +623,11 @@ def main(argv=None):
             if args.scst:
                 loss, mean_r = scst_step(model, optimizer, batch, lr, args.len_vis_input, rl_crit, accumulate=acc,
                                          accum_steps=args.gradient_accumulation_steps, reward_on=args.scst_reward, df=scst_df,
-                                         samples=args.scst_samples, reward_weights=(args.scst_cider_weight, args.scst_bleu_weight))
+                                         samples=args.scst_samples, reward_weights=(args.scst_cider_weight, args.scst_bleu_weight),
+                                         **scst_policy)
                 rewards.append(mean_r.detach())
+                if "stats" in scst_policy:
+                    entropies.append(scst_policy["stats"]["entropy"])
             else:
                 lt = train_step(model, optimizer, batch, lr, mask_image_regions=args.mask_image_regions,
                                 drop_worst_ratio=args.max_drop_worst_ratio if i_epoch > args.drop_after else 0,
@@ -591,7 +637,11 @@ def main(argv=None):
             if step % args.log_every == 0:        # the only host read-back; the reference does 4 per step (:535-538)
                 if args.scst:                     # :540 adds the mean reward
                     losses.append(float(loss.detach()))
-                    logger.info("Epoch %d, Iter %d, Loss %.3f, Mean R %.3f", i_epoch, step, losses[-1], float(torch.stack(rewards).mean()))
+                    if entropies:
+                        logger.info("Epoch %d, Iter %d, Loss %.3f, Mean R %.3f, Mean H %.3f", i_epoch, step, losses[-1],
+                                    float(torch.stack(rewards).mean()), float(torch.stack(entropies).mean()))
+                    else:
+                        logger.info("Epoch %d, Iter %d, Loss %.3f, Mean R %.3f", i_epoch, step, losses[-1], float(torch.stack(rewards).mean()))
                 else:
                     losses.append(float((lt[0] + lt[1] + lt[2]).detach()))
                     logger.info("Epoch %d, Iter %d, Loss %.3f", i_epoch, step, losses[-1])

@@ -448,6 +448,31 @@ class RewardCriterion(nn.Module):
         return torch.sum(-input * reward * mask) / torch.sum(mask)
 
 
+def reward_mask(seq, dtype=torch.float32):
+    """RewardCriterion's mask [B, T]: [1, (seq > 0)[:, :-1]] -- every position up to and including the one right after the first 0."""
+    mask = (seq > 0).to(dtype)
+    return torch.cat([torch.ones_like(mask[:, :1]), mask[:, :-1]], 1)
+
+
+def policy_loss(logp, seq, reward, entropy=None, entropy_weight=0.0, crit=None):
+    """The SCST loss with an entropy bonus (--scst_entropy_weight): RewardCriterion(logp, seq, reward) - entropy_weight * sum(H * mask) /
+    sum(mask) over RewardCriterion's mask, H = `entropy` [B, T], the sampled policy's entropy at every position.  Returns (loss, masked mean
+    entropy or None).  entropy_weight 0 returns the criterion's own value (the mean entropy, detached, only when `entropy` is given)."""
+    w = float(entropy_weight)
+    if not (np.isfinite(w) and w >= 0):
+        raise ValueError("the entropy weight must be finite and not negative (got %r)" % (entropy_weight,))
+    loss = (crit if crit is not None else RewardCriterion())(logp, seq, reward)
+    if entropy is None:
+        if w > 0:
+            raise ValueError("an entropy weight of %r needs the policy's entropy" % w)
+        return loss, None
+    mask = reward_mask(seq, entropy.dtype)
+    mean_h = torch.sum(entropy * mask) / torch.sum(mask)
+    if w == 0:
+        return loss, mean_h.detach()
+    return loss - w * mean_h, mean_h.detach()
+
+
 def _refs_parts(refs, B):
     """refs -> (ids [B, R, T], count [B] or None): a CaptionRefs as it is, the [B, T] ground-truth ids as one reference per sample."""
     from .input_prep import CaptionRefs
