@@ -43,6 +43,8 @@ extern "C" {
  * additive as well. */
 /* + vlp_caption_eval / vlp_caption_eval_workspace_bytes (caption metrics of word strings: CIDEr-D, the BLEU integers, LCS for ROUGE-L) and
  * its argument struct: purely additive as well. */
+/* + vlp_cider_d_consensus / vlp_cider_d_consensus_workspace_bytes (the K samples of an image scored against each other, the pick) and its
+ * argument struct: purely additive as well. */
 /* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 
@@ -808,6 +810,41 @@ int64_t vlp_cider_d_multi_workspace_bytes(int32_t G, int32_t R, int32_t T, int32
 int vlp_cider_d_multi(const vlp_cider_d_args* a, void* stream);
 int64_t vlp_cider_d_multi_df_workspace_bytes(int32_t G, int32_t R, int32_t T, int32_t mult);
 int vlp_cider_d_multi_df(const vlp_cider_d_df_args* a, void* stream);
+
+/* Consensus selection among the K samples of an image (minimum-Bayes-risk decoding under CIDEr-D): every sample is scored against the
+ * image's other K - 1 samples as its references, and the sample with the largest score is picked.  No references are needed.  hyp is int64
+ * [K*G, T] in sample-major order: row k*G + g is sample k of image g.  Strings, the table (key packing, ids outside 0..65534 form no key, an
+ * empty table is legal, unsigned lower-bound search, read only) and idf = logf((float)n_docs) - logf(fmaxf(1.f, (float)df)) are
+ * vlp_cider_d_df's: a string is a row's ids up to AND INCLUDING the first 0, or all T ids without one; nothing behind the first 0 is read.
+ *   - utility [K*G] f32: utility[k*G + g] is what CiderD(df=<DocFreq>).compute_score gives for sample k of image g with the image's samples
+ *     j != k as its references, in ascending j.  The arithmetic and its order are vlp_cider_d_df's: per reference and order the clipped
+ *     product, divided by the two norms when both are non-zero, times the Gaussian penalty on the bigram-count lengths, accumulated per
+ *     order over the references, then (acc0 + acc1 + acc2 + acc3) / 4 / (K - 1) * 10;
+ *   - pick [G] int32: the lowest k whose stored fp32 utility[k*G + g] is the largest of image g;
+ *   - pair [G, K, K] f32, optional (NULL: not written): pair[g][k][j] is the same score of sample k with sample j as its only reference
+ *     (divisor 1); the diagonal is written as 0.  Not symmetric: the clipping uses the reference's weight.  utility and pick are the same
+ *     bits with and without pair.
+ * Two launches (cider_count_kernel over the K*G rows alone; one scoring block per image with 64 * K threads, the K rows staged once in LDS
+ * and serving both roles), no host involvement, capturable; no atomics, every sum in a fixed order: equal inputs give bit-equal outputs.
+ * Nothing is written outside utility[0, K*G), pick[0, G), pair[0, G*K*K) and the workspace.
+ * Accepted: 1 <= T <= 64, 2 <= K <= 16, 1 <= G <= 1024, hyp_ld >= T, sigma > 0, non-null hyp / utility / pick, vlp_cider_d_df's table
+ * conditions, a 16-byte aligned workspace of vlp_cider_d_consensus_workspace_bytes() bytes (0 for a refused shape).  Anything else returns
+ * VLP_ERR_BAD_ARG before a launch. */
+typedef struct {
+    const int64_t* hyp; int64_t hyp_ld;                        /* [K*G, T]; row k*G + g is sample k of image g */
+    int32_t G, K, T;
+    float sigma;                                               /* 6.0 */
+    const uint64_t* df_keys;                                   /* [df_n] strictly ascending (unsigned) */
+    const int32_t* df_vals;                                    /* [df_n] 1 <= df <= n_docs */
+    int64_t df_n;
+    int64_t n_docs;
+    float* utility;                                            /* [K*G] out */
+    int32_t* pick;                                             /* [G] out */
+    float* pair;                                               /* optional [G, K, K] out */
+    void* workspace; int64_t workspace_bytes;
+} vlp_cider_d_consensus_args;
+int64_t vlp_cider_d_consensus_workspace_bytes(int32_t G, int32_t K, int32_t T);
+int vlp_cider_d_consensus(const vlp_cider_d_consensus_args* a, void* stream);
 
 /* Sentence BLEU-4 of id strings, the weighted mix with the CIDEr-D scores of a preceding vlp_cider_d* launch and the baseline of the mixed
  * scores (SCST with the reward cider_weight * CIDEr-D + bleu_weight * BLEU-4).  The specification is vlp_amd/scst.py Bleu.compute_score

@@ -164,6 +164,11 @@ class CiderDDfArgs(C.Structure):
     _fields_ = [("s", CiderDArgs), ("df_keys", vp), ("df_vals", vp), ("df_n", i64), ("n_docs", i64)]
 
 
+class CiderDConsensusArgs(C.Structure):
+    _fields_ = [("hyp", vp), ("hyp_ld", i64), ("G", i32), ("K", i32), ("T", i32), ("sigma", f32), ("df_keys", vp), ("df_vals", vp), ("df_n", i64),
+                ("n_docs", i64), ("utility", vp), ("pick", vp), ("pair", vp), ("workspace", vp), ("workspace_bytes", i64)]
+
+
 class CaptionEvalArgs(C.Structure):
     _fields_ = [("d", CiderDDfArgs), ("bleu_stats", vp), ("lcs", vp)]
 
@@ -281,6 +286,8 @@ SYMBOLS = {
     "vlp_cider_d_multi": (C.c_int, [C.POINTER(CiderDArgs), vp]),
     "vlp_cider_d_multi_df_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vlp_cider_d_multi_df": (C.c_int, [C.POINTER(CiderDDfArgs), vp]),
+    "vlp_cider_d_consensus_workspace_bytes": (i64, [i32, i32, i32]),
+    "vlp_cider_d_consensus": (C.c_int, [C.POINTER(CiderDConsensusArgs), vp]),
     "vlp_bleu4": (C.c_int, [C.POINTER(Bleu4Args), vp]),
     "vlp_caption_eval_workspace_bytes": (i64, [i32, i32, i32]),
     "vlp_caption_eval": (C.c_int, [C.POINTER(CaptionEvalArgs), vp]),
@@ -889,6 +896,41 @@ def cider_d_multi_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs
     cider_d_multi_df_workspace_bytes() bytes."""
     a = _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, cider_d_multi_df_workspace_bytes, mult)
     _check(load().vlp_cider_d_multi_df(C.byref(a), stream_ptr()))
+
+
+def cider_d_consensus_workspace_bytes(G, K, T):
+    """0 for a shape vlp_cider_d_consensus refuses (2 <= K <= 16)."""
+    return int(load().vlp_cider_d_consensus_workspace_bytes(G, K, T))
+
+
+def cider_d_consensus(hyp, K, keys, vals, n_docs, utility, pick, pair=None, sigma=6.0, workspace=None):
+    """The K samples of every image scored against each other (include/vlp_hip.h vlp_cider_d_consensus): hyp int64 [K*G, T], row k*G + g
+    sample k of image g (rows may be strided); keys / vals / n_docs the table as for cider_d_df; utility f32 [K*G] (sample k against the
+    image's other K - 1), pick int32 [G] (the first largest utility), pair f32 [G, K, K] or None (sample k against sample j alone, 0 on the
+    diagonal).  workspace: cider_d_consensus_workspace_bytes() bytes or None (a fresh allocation).  Two launches on the current stream."""
+    _req_cuda(hyp, keys, vals, utility, pick, pair, workspace)
+    if hyp.dtype != torch.int64 or hyp.dim() != 2 or hyp.stride(1) != 1:
+        raise RuntimeError("vlp_amd.cider_d_consensus: hyp int64 [K*G, T] with contiguous rows")
+    KG, T = hyp.shape
+    K = int(K)
+    if K < 1 or KG % K:
+        raise RuntimeError("vlp_amd.cider_d_consensus: %d rows are not %d samples of every image" % (KG, K))
+    G = KG // K
+    if (keys.dtype not in (torch.int64, torch.uint64) or vals.dtype != torch.int32 or keys.dim() != 1 or vals.dim() != 1
+            or not keys.is_contiguous() or not vals.is_contiguous() or keys.numel() != vals.numel()):
+        raise RuntimeError("vlp_amd.cider_d_consensus: keys int64 [N] (the uint64 keys' bits) and vals int32 [N], contiguous")
+    if utility.dtype != torch.float32 or not utility.is_contiguous() or utility.numel() < KG:
+        raise RuntimeError("vlp_amd.cider_d_consensus: utility must be contiguous f32 [%d]" % KG)
+    if pick.dtype != torch.int32 or not pick.is_contiguous() or pick.numel() < G:
+        raise RuntimeError("vlp_amd.cider_d_consensus: pick must be contiguous int32 [%d]" % G)
+    if pair is not None and (pair.dtype != torch.float32 or not pair.is_contiguous() or pair.numel() < G * K * K):
+        raise RuntimeError("vlp_amd.cider_d_consensus: pair must be contiguous f32 [%d, %d, %d]" % (G, K, K))
+    if workspace is None:
+        workspace = torch.empty(max(cider_d_consensus_workspace_bytes(G, K, T), 1), device=hyp.device, dtype=torch.uint8)
+    n = keys.numel()
+    a = CiderDConsensusArgs(ptr(hyp), hyp.stride(0), G, K, T, sigma, ptr(keys) if n else None, ptr(vals) if n else None, n, int(n_docs), ptr(utility),
+                            ptr(pick), ptr(pair), ptr(workspace), _nbytes(workspace))
+    _check(load().vlp_cider_d_consensus(C.byref(a), stream_ptr()))   # (a fresh workspace lives until the launches have been enqueued)
 
 
 BLEU_REWARD_PAIR, BLEU_REWARD_LOO = 0, 1

@@ -19,6 +19,9 @@
 // vlp_cider_d_multi / vlp_cider_d_multi_df are the same two kernels with 2..16 hypotheses per group (64 * mult threads in the scoring block) and
 // the leave-one-out reward: every hypothesis against the mean of the group's other scores.
 //
+// vlp_cider_d_consensus scores the K samples of an image against each other (consensus selection): the counting kernel with TABLE = true over
+// the sample rows alone, and a scoring kernel of its own whose references are the block's own rows.
+//
 // vlp_bleu4 (at the end of this file) is a third kernel of the scoring kernel's shape: sentence BLEU-4 of the hypotheses, its weighted mix with the
 // CIDEr-D scores and the reward of the mixed scores, in one launch.
 //
@@ -312,6 +315,125 @@ extern "C" int vlp_cider_d_multi_df(const vlp_cider_d_df_args* d, void* stream) 
     CD_CHECK_ARGS(a, "vlp_cider_d_multi_df", need, true);
     CD_CHECK_TABLE(d, "vlp_cider_d_multi_df");
     return cd_run_df(d, stream, true, "vlp_cider_d_multi_df");
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// vlp_cider_d_consensus: the K samples of an image scored against each other (consensus selection: keep the sample that agrees most with the
+// others).  The counting pass is cider_count_kernel<true> over the K*G sample rows alone -- a sample's norms in the reference role are its own
+// --; the scoring block below is cider_score_kernel<true>'s with the references taken from the block's own rows: one block per image, one
+// wave per sample, one lane per position.  Every wave stages its row once in LDS with the reference's sentinel and keeps it in registers with
+// the hypothesis' sentinel (the two ends stay distinct: two string ends never match), then walks the other K - 1 rows in ascending j.
+// ------------------------------------------------------------------------------------------------------------------------------------------
+static inline bool cd_consensus_shape_ok(int32_t G, int32_t K, int32_t T) {
+    return T >= 1 && T <= 64 && K >= 2 && K <= CD_MAX_MULT && G >= 1 && G <= 1024;
+}
+
+__global__ __launch_bounds__(64 * CD_MAX_MULT) void consensus_score_kernel(vlp_cider_d_consensus_args a, const int* info, const float* norms, const float* idf_in) {
+    __shared__ int rows[CD_MAX_MULT][64 + CD_PAD];                     // the image's samples with a reference's sentinel
+    __shared__ int len_s[CD_MAX_MULT];
+    __shared__ float util[CD_MAX_MULT];
+    const int T = a.T, G = a.G, K = a.K;
+    const int g = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63, h = w * G + g;
+
+    const int tok = lane < T ? (int)a.hyp[(int64_t)h * a.hyp_ld + lane] : CD_HYP_END;
+    const unsigned long long zm = __ballot(lane < T && tok == 0);
+    const int len = zm ? (int)__builtin_ctzll(zm) + 1 : T;
+    int av[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = __shfl(tok, (lane + j) & 63, 64);
+        av[j] = lane + j < len ? t : CD_HYP_END;
+    }
+    rows[w][lane] = lane < len ? tok : CD_REF_END;
+    if (lane < CD_PAD) rows[w][64 + lane] = CD_REF_END;
+    if (lane == 0) len_s[w] = len;
+    __syncthreads();
+
+    float idf[4], hv[4], nh[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
+    bool first[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int pk = lane < T ? info[((int64_t)h * 4 + k) * T + lane] : 0;
+        idf[k] = lane < T ? idf_in[((int64_t)h * 4 + k) * T + lane] : 0.f;
+        hv[k] = (float)((pk >> 11) & 127) * idf[k];
+        first[k] = (pk >> 18) & 1;
+        nh[k] = norms[(int64_t)h * 4 + k];
+    }
+    const float two_sigma2 = 2.f * a.sigma * a.sigma;
+    for (int j = 0; j < K; ++j) {
+        if (j == w) continue;                                          // (wave-uniform)
+        const int* row = rows[j];
+        int t[4] = {0, 0, 0, 0};
+        int b0 = row[0], b1 = row[1], b2 = row[2];
+        for (int q = 0; q < T; ++q) {
+            const int b3 = row[q + 3];
+            const int m = cd_match(av[0], av[1], av[2], av[3], b0, b1, b2, b3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) t[k] += m > k;
+            b0 = b1; b1 = b2; b2 = b3;
+        }
+        const float delta = (float)(max(len - 1, 0) - max(len_s[j] - 1, 0));
+        const float penalty = expf(-(delta * delta) / two_sigma2);
+        float one[4];                                                  // this reference alone
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float rv = (float)t[k] * idf[k];
+            float val = wave_sum(first[k] ? fminf(hv[k], rv) * rv : 0.f);
+            const float nrk = norms[((int64_t)j * G + g) * 4 + k];
+            if (nh[k] != 0.f && nrk != 0.f) val /= nh[k] * nrk;
+            one[k] = val * penalty;
+            acc[k] += val * penalty;
+        }
+        const float single = (one[0] + one[1] + one[2] + one[3]) / 4.f * 10.f;
+        if (a.pair && lane == 0) a.pair[((int64_t)g * K + w) * K + j] = single;
+    }
+    const float score = (acc[0] + acc[1] + acc[2] + acc[3]) / 4.f / (float)(K - 1) * 10.f;
+    if (lane == 0) {
+        a.utility[h] = score;
+        util[w] = score;
+        if (a.pair) a.pair[((int64_t)g * K + w) * K + w] = 0.f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                            // the lowest k with the largest stored utility
+        int best = 0;
+        for (int k = 1; k < K; ++k)
+            if (util[k] > util[best]) best = k;
+        a.pick[g] = best;
+    }
+}
+
+// workspace: cider_count_kernel<true>'s for K*G hypotheses and no reference: int32 info[K*G][4][T], f32 idf[K*G][4][T], f32 norms[K*G][4]
+extern "C" int64_t vlp_cider_d_consensus_workspace_bytes(int32_t G, int32_t K, int32_t T) {
+    if (!cd_consensus_shape_ok(G, K, T)) return 0;
+    const int64_t bytes = 4 * (2 * cd_info_ints(G, T, K) + 4 * (int64_t)K * G);
+    return (bytes + 255) / 256 * 256;
+}
+
+extern "C" int vlp_cider_d_consensus(const vlp_cider_d_consensus_args* c, void* stream) {
+    VLP_CHECK_ARG(c, "vlp_cider_d_consensus: null args");
+    VLP_CHECK_ARG(cd_consensus_shape_ok(c->G, c->K, c->T), "vlp_cider_d_consensus: needs 1 <= T <= 64, 2 <= K <= 16, 1 <= G <= 1024 (G %d, K %d, T %d)", c->G,
+                  c->K, c->T);
+    VLP_CHECK_ARG(c->hyp && c->utility && c->pick && c->workspace, "vlp_cider_d_consensus: null operand");
+    VLP_CHECK_ARG(c->hyp_ld >= c->T, "vlp_cider_d_consensus: hyp_ld shorter than the rows");
+    VLP_CHECK_ARG(c->sigma > 0.f, "vlp_cider_d_consensus: sigma must be positive");
+    const int64_t need = vlp_cider_d_consensus_workspace_bytes(c->G, c->K, c->T);
+    VLP_CHECK_ARG(c->workspace_bytes >= need && (uintptr_t)c->workspace % 16 == 0, "vlp_cider_d_consensus: workspace of %lld bytes, needs %lld (16-byte aligned)",
+                  (long long)c->workspace_bytes, (long long)need);
+    CD_CHECK_TABLE(c, "vlp_cider_d_consensus");
+    VLP_ENTER(c->hyp, "vlp_cider_d_consensus");
+    vlp_cider_d_args a = {};                                           // the counting pass sees K*G hypotheses and no reference block
+    a.hyp = c->hyp; a.hyp_ld = c->hyp_ld;
+    a.G = c->G; a.R = 1; a.T = c->T; a.mult = c->K;
+    const int SH = c->K * c->G;
+    int* info = (int*)c->workspace;
+    float* idf = (float*)(info + cd_info_ints(c->G, c->T, c->K));
+    float* norms = idf + cd_info_ints(c->G, c->T, c->K);
+    const cd_table tab = {c->df_keys, c->df_vals, c->df_n, (float)c->n_docs};
+    hipLaunchKernelGGL(cider_count_kernel<true>, dim3(SH), dim3(CD_THREADS), 0, (hipStream_t)stream, a, 64, 0, info, norms, tab, idf);
+    VLP_CHECK_LAUNCH("vlp_cider_d_consensus");
+    hipLaunchKernelGGL(consensus_score_kernel, dim3(c->G), dim3(64 * c->K), 0, (hipStream_t)stream, *c, (const int*)info, (const float*)norms, (const float*)idf);
+    VLP_CHECK_LAUNCH("vlp_cider_d_consensus");
+    return VLP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
