@@ -599,6 +599,19 @@ int vlp_logsoftmax_topk_list(const void* logits, int64_t ld, int32_t rows, int32
                              const int32_t* cand_cnt, int32_t eos_id, int32_t block_eos, float* out_scores, int64_t* out_ids, void* stream);
 int vlp_kv_gather(const void* src, int64_t src_rows_per_batch, void* dst, int64_t dst_rows_per_batch, const int64_t* idx, int32_t R, int32_t lo,
                   int32_t hi, int32_t row_elems, void* stream);
+/* The N best hypotheses of a finished search, ranked and back-tracked on the device (:1446-1474 applied to every rank):
+ *   tot (f32) / wids / ptrs (int64): the frames [F, B, K] that vlp_beam_select wrote, contiguous.  Per sample b: last = the first frame whose K
+ *       words are all eos_id, else F - 1; candidate (f, k) exists when f <= last and (wids[f,b,k] == eos_id or f == last); its value is
+ *       (double)tot[f,b,k] + length_penalty * (f + 1) in fp64 (product rounded, then the sum); candidates are ordered by value descending, then
+ *       by f*K + k ascending.  Rank n of sample b goes to row n*B + b (sample-major):
+ *       seq [N*B, T] int64   the words along the back pointers from (f, k), zero padded (a pointer outside [0, K) counts as 0);
+ *       score [N*B] f32      tot[f,b,k];      value [N*B] f64   the ranking value;      len [N*B] int32   f + 1;
+ *       ok [N*B] uint8       1 when the value is finite and no position before the last one is eos_id (0: the continuation of a hypothesis
+ *                            that had ended, which the search keeps at -10000).
+ *       A rank whose value is not finite gets an all-zero row, len 0 and ok 0 (the reference's [0]).
+ *   1 <= N <= K <= 64, 1 <= F <= 256, T >= F, B > 0; anything else is VLP_ERR_BAD_ARG before the launch.  One launch, no synchronisation. */
+int vlp_beam_nbest(const float* tot, const int64_t* wids, const int64_t* ptrs, int32_t F, int32_t B, int32_t K, int64_t eos_id, double length_penalty,
+                   int32_t N, int32_t T, int64_t* seq, float* score, double* value, int32_t* len, uint8_t* ok, void* stream);
 /* VQA fusion (modeling.py:1044,1138): out[b,:] = h[b,0,:] * h[b,Nv+1,:]; backward adds into dh rows.  row_off ([B+1] or NULL, ABI 4):
  * packed rows, sample b starts at row row_off[b] instead of b*L. */
 int vlp_vqa_mul_fwd(const void* h, void* out, int32_t B, int32_t L, int32_t Nv, int32_t H, const int32_t* row_off, void* stream);

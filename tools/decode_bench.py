@@ -3,6 +3,12 @@
     MODES=greedy,beam3,beam5[,beam3_ngram,beam5_ngram]   the *_ngram modes search with forbid_duplicate_ngrams=True, ngram_size=3
     BLOCKING=device|host                                 where their n-gram blocking runs (BertForSeq2SeqDecoder.ngram_blocking); host mode
                                                          only needs interfaces older trees have, so this file also times those
+    BACKTRACK=host|device                                where beam_search turns the frames into hypotheses (BertForSeq2SeqDecoder.backtrack)
+    N_BEST=N                                             hypotheses kept per image in the beam modes (N > 1 back-tracks on the device)
+    BACKTRACK_AB=1                                       instead of the modes: beam 3 and beam 5, each as ONE model whose calls alternate between
+                                                         backtrack=host, backtrack=device and device with n_best = beam (same weights, workspace and
+                                                         captured token steps; ROUNDS rounds after 3 warm-up calls of each), plus the event time
+                                                         around vlp_beam_nbest alone -> profiles/beam_nbest.json
 """
 import json
 import os
@@ -34,6 +40,61 @@ am = am.to(dev)
 BLOCKING = os.environ.get("BLOCKING", "device")
 assert BLOCKING in ("device", "host")
 NGRAM = dict(forbid_duplicate_ngrams=True, ngram_size=3)
+BACKTRACK, N_BEST = os.environ.get("BACKTRACK", "host"), int(os.environ.get("N_BEST", 1))
+assert BACKTRACK in ("device", "host")
+
+
+def backtrack_ab():
+    """Host against device back-tracking inside a beam-search batch, same process, alternating calls; every call ends in a synchronise."""
+    import statistics
+    rounds = int(os.environ.get("ROUNDS", 12))
+    res = {"batch": B, "new_tokens": T, "layers": 12, "rounds": rounds, "warmup_calls_per_config": 3,
+           "timing": "host clock around one beam_search call, synchronised before and after; the three configurations alternate inside every round"}
+    for Kb in (3, 5):
+        m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=Nv, allow_random_fc7=True,
+                                  search_beam_size=Kb).half().to(dev).eval()
+        configs = (("host", "host", 1), ("device", "device", 1), ("device_n_best_%d" % Kb, "device", Kb))
+        times, preds = {c[0]: [] for c in configs}, {}
+
+        def call(name, where, n):
+            m.backtrack, m.n_best = where, n
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = m(img, vis_pe, input_ids, token_type, pos, am)
+            torch.cuda.synchronize()
+            preds[name] = r["pred_seq"]
+            return (time.perf_counter() - t0) * 1e3
+        for _ in range(3):
+            for c in configs:
+                call(*c)
+        for _ in range(rounds):
+            for c in configs:
+                times[c[0]].append(call(*c))
+        assert all(torch.equal(preds["host"], p) for p in preds.values()), "host and device back-tracking disagree"
+        entry = {name: {"ms_per_batch_median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3),
+                        "stdev": round(statistics.stdev(ts), 3)} for name, ts in times.items()}
+        # the kernel alone: device events around Engine.beam_nbest on the frames of the last search (launch overhead included)
+        tot, wids, ptrs = (t.clone() for t in (m.engine._ws[("dec", B, in_len + 1, out_len, Kb)][k][:T] for k in ("tot", "wids", "ptrs")))
+        for n in (1, Kb):
+            ev = []
+            for i in range(25):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                m.engine.beam_nbest(tot, wids, ptrs, n, S.SEP_ID, m.length_penalty, out_len)
+                b.record()
+                torch.cuda.synchronize()
+                if i >= 5:
+                    ev.append(a.elapsed_time(b) * 1e3)
+            entry["vlp_beam_nbest_n%d_event_us" % n] = {"median": round(statistics.median(ev), 1), "min": round(min(ev), 1), "max": round(max(ev), 1)}
+        res["beam%d" % Kb] = entry
+        del m
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if os.environ.get("BACKTRACK_AB") == "1":
+    backtrack_ab()
+    sys.exit(0)
 MODES = [m for m in (("greedy", dict(search_beam_size=1)), ("beam3", dict(search_beam_size=3)), ("beam5", dict(search_beam_size=5)),
                      ("beam3_ngram", dict(search_beam_size=3, **NGRAM)), ("beam5_ngram", dict(search_beam_size=5, **NGRAM)))
          if m[0] in os.environ.get("MODES", "greedy,beam3,beam5").split(",")]
@@ -41,6 +102,10 @@ for name, kw in MODES:
     m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=Nv, allow_random_fc7=True, **kw).half().to(dev).eval()
     if name.endswith("_ngram"):
         m.ngram_blocking = BLOCKING
+    if name != "greedy":
+        m.backtrack, m.n_best = BACKTRACK, N_BEST
+        out.setdefault("backtrack", BACKTRACK)
+        out.setdefault("n_best", N_BEST)
     for _ in range(2):
         m(img, vis_pe, input_ids, token_type, pos, am)
     torch.cuda.synchronize()
@@ -55,7 +120,7 @@ for name, kw in MODES:
                  "host_enqueue_ms": round(t_enq * 1e3, 2)}
     if name.endswith("_ngram"):
         out[name]["ngram_blocking"] = BLOCKING
-    if name != "greedy":
+    if name != "greedy" and BACKTRACK == "host" and N_BEST == 1:
         # beam_search() returns the best sequences, which needs one device -> host copy of the frames: the call itself waits for the GPU, so the
         # "enqueue" figure equals the wall time; the device work is enqueued in ~2 ms (Engine.decode_beam, hipGraph replays) -- decoding is not host-bound
         out[name]["host_enqueue_includes_final_device_to_host_copy"] = True

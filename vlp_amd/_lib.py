@@ -240,6 +240,7 @@ SYMBOLS = {
     "vlp_ngram_candidates": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp]),
     "vlp_logsoftmax_topk_list": (C.c_int, [vp, i64, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     "vlp_kv_gather": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]),
+    "vlp_beam_nbest": (C.c_int, [vp, vp, vp, i32, i32, i32, i64, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp]),
     "vlp_embed_bwd_workspace_floats": (C.c_int64, [i32, i32, i32, i32]),
     "vlp_mask_build": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
     "vlp_vis_pe_prep": (C.c_int, [C.POINTER(VisPePrepArgs), vp]),
@@ -625,6 +626,25 @@ def beam_select(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, ou
 def kv_gather(src, src_rows, dst, dst_rows, idx, R, lo, hi, row_elems):
     _req_cuda(src, dst, idx)
     _check(load().vlp_kv_gather(ptr(src), src_rows, ptr(dst), dst_rows, ptr(idx), R, lo, hi, row_elems, stream_ptr()))
+
+
+def beam_nbest(tot, wids, ptrs, n_best, eos_id, length_penalty, seq, score, value, length, ok):
+    """tot f32 / wids / ptrs int64: contiguous frames [F, B, K] (Engine.decode_beam).  Outputs, sample-major (rank n of sample b = row n*B + b):
+    seq int64 [n_best*B, T] (row stride = stride(0) = T >= F), score f32, value f64, length int32, ok uint8, each [n_best*B]."""
+    _req_cuda(tot, wids, ptrs, seq, score, value, length, ok)
+    shape = next((tuple(t.shape) for t in (tot, wids, ptrs) if t is not None), ())
+    F, B, K = (int(v) for v in shape) if len(shape) == 3 else (0, 0, 0)
+    for t, dt in ((tot, torch.float32), (wids, torch.int64), (ptrs, torch.int64)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (F, B, K))
+    rows = int(n_best) * B
+    T = 0
+    if seq is not None:
+        assert seq.dtype == torch.int64 and seq.dim() == 2 and seq.is_contiguous() and seq.shape[0] >= rows
+        T = int(seq.shape[1])
+    for t, dt in ((score, torch.float32), (value, torch.float64), (length, torch.int32), (ok, torch.uint8)):
+        assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() >= rows)
+    _check(load().vlp_beam_nbest(ptr(tot), ptr(wids), ptr(ptrs), F, B, K, int(eos_id), float(length_penalty), int(n_best), T, ptr(seq), ptr(score),
+                                 ptr(value), ptr(length), ptr(ok), stream_ptr()))
 
 
 def mask_build(second_st, second_end, is_s2s, out_u8, B, L, Lp, out_t=None, region_mask=None, Nv=0):

@@ -1111,6 +1111,97 @@ extern "C" int vlp_beam_select(const vlp_beam_select_args* a, void* stream) {
     return VLP_OK;
 }
 
+// The N best finished hypotheses of a search, ranked and back-tracked on the device (:1446-1474 for every rank, not only the best).  One wave
+// per sample.  last = the first frame whose K words are all eos, else F - 1; candidate i = f*K + k (f <= last) exists when its word is eos or
+// f == last; its value is (double)tot + length_penalty * (f + 1).  Rank n is the maximum among the candidates that come after rank n - 1 in
+// the (value descending, index ascending) order -- the scan of beam_select_kernel, strided over the lanes and finished by a wave reduction, so
+// nothing is sorted and no value is kept.  Then lane n walks the back pointers of rank n (bytes in LDS, as ngram_candidates_kernel keeps them).
+// pen[] goes through LDS on purpose: the product is rounded to fp64 before the sum, as on the host (the build contracts a * b + c otherwise).
+__global__ __launch_bounds__(64) void beam_nbest_kernel(const float* tot, const int64_t* wids, const int64_t* ptrs, int F, int B, int K, int64_t eos_id,
+                                                        double length_penalty, int N, int T, int64_t* seq, float* score, double* value, int32_t* len,
+                                                        uint8_t* ok) {
+    __shared__ unsigned char bp[NGRAM_MAX_FRAMES * 64];
+    __shared__ double pen[NGRAM_MAX_FRAMES];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int last = F - 1;
+    for (int f = lane; f < F; f += 64) {
+        bool all = true;
+        for (int k = 0; k < K; ++k) all &= wids[((int64_t)f * B + b) * K + k] == eos_id;
+        if (all) {
+            last = f;
+            break;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) last = min(last, __shfl_xor(last, o, 64));
+    const int ncand = (last + 1) * K;
+    for (int i = lane; i < ncand; i += 64) {
+        const int f = i / K, j = i - f * K;
+        const int64_t p = ptrs[((int64_t)f * B + b) * K + j];
+        bp[i] = (unsigned char)((p >= 0 && p < K) ? p : 0);
+    }
+    for (int f = lane; f <= last; f += 64) pen[f] = length_penalty * (double)(f + 1);
+    __syncthreads();
+    double pv = INFINITY, my_val = -INFINITY;
+    int pi = -1, my_idx = 0x7fffffff;
+    for (int n = 0; n < N; ++n) {
+        double best = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int i = lane; i < ncand; i += 64) {
+            const int f = i / K, k = i - f * K;
+            const int64_t g = ((int64_t)f * B + b) * K + k;
+            if (f != last && wids[g] != eos_id) continue;
+            const double val = (double)tot[g] + pen[f];
+            const bool after = (val < pv) || (val == pv && i > pi);
+            if (after && (val > best || (val == best && i < bi))) { best = val; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
+        pv = best;
+        pi = bi;
+        if (lane == n) { my_val = best; my_idx = bi; }
+    }
+    if (lane >= N) return;
+    const int64_t row = (int64_t)lane * B + b;
+    int64_t* out = seq + row * T;
+    const bool found = my_idx != 0x7fffffff;               // (N <= K candidates of frame `last` always exist)
+    const int f = found ? my_idx / K : 0, k = found ? my_idx - f * K : 0;
+    const bool live = found && isfinite(my_val);
+    bool clean = live;
+    int t0 = 0;
+    if (live) {
+        int j = k;
+        for (int t = f; t >= 0; --t) {
+            const int64_t w = wids[((int64_t)t * B + b) * K + j];
+            out[t] = w;
+            clean &= t == f || w != eos_id;
+            j = bp[t * K + j];
+        }
+        t0 = f + 1;
+    }
+    for (int t = t0; t < T; ++t) out[t] = 0;
+    score[row] = found ? tot[((int64_t)f * B + b) * K + k] : -INFINITY;
+    value[row] = my_val;
+    len[row] = live ? f + 1 : 0;
+    ok[row] = clean ? 1 : 0;
+}
+extern "C" int vlp_beam_nbest(const float* tot, const int64_t* wids, const int64_t* ptrs, int32_t F, int32_t B, int32_t K, int64_t eos_id,
+                              double length_penalty, int32_t N, int32_t T, int64_t* seq, float* score, double* value, int32_t* len, uint8_t* ok,
+                              void* stream) {
+    VLP_CHECK_ARG(tot && wids && ptrs && seq && score && value && len && ok, "vlp_beam_nbest: null operand");
+    VLP_CHECK_ARG(B > 0 && F >= 1 && F <= NGRAM_MAX_FRAMES && K >= 1 && K <= 64 && N >= 1 && N <= K && T >= F,
+                  "vlp_beam_nbest: needs B > 0, 1 <= N <= K <= 64, 1 <= F <= %d, T >= F (got F=%d B=%d K=%d N=%d T=%d)", NGRAM_MAX_FRAMES, F, B, K, N, T);
+    VLP_ENTER(tot, "vlp_beam_nbest");
+    hipLaunchKernelGGL(beam_nbest_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, tot, wids, ptrs, F, B, K, eos_id, length_penalty, N, T, seq, score,
+                       value, len, ok);
+    VLP_CHECK_LAUNCH("vlp_beam_nbest");
+    return VLP_OK;
+}
+
 // dst[r, pos, :] = src[idx[r], pos, :] for pos in [lo, hi): first_expand / select_beam_items (:1325-1349) on the K/V caches
 __global__ void kv_gather_kernel(const f16* src, int64_t src_rows, f16* dst, int64_t dst_rows, const int64_t* idx, int R, int lo, int hi, int E) {
     const int nch = E >> 3;

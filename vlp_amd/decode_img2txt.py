@@ -15,6 +15,15 @@ Every flag of the reference script keeps its name and default.  What differs:
 --do_lower_case, --image_root, --region_bbox_file and --region_det_file_prefix are accepted for the reference's command lines and not used: there is
 no tokenizer, and the features come from the packed store.
 A short last batch is filled up with its last image (and the extra rows dropped), so every batch runs the same launches.
+
+  --n_best N (1..--beam_size; default 1: the tool as above, byte for byte) keeps the N best finished hypotheses of every image's beam search,
+      ranked and back-tracked on the device (vlp_beam_nbest; vlp_amd.nbest.beam_nbest_host is the rule).  Rank 0 is the caption written without the flag
+  --nbest_file PATH receives every hypothesis, ordered by image and rank (rank 0 always; the others unless they went on after their [SEP]):
+      {"image_id": ..., "rank": n, "caption": "...", "logprob": cumulative log-probability, "value": logprob + length_penalty * length}
+  --select {none,consensus,logprob}, --consensus_df PATH and --samples_file (here an alias of --nbest_file) are vlp_amd.sample_img2txt's flags,
+      applied to the hypotheses of the beam instead of samples: none writes rank 0; logprob the hypothesis with the largest logprob; consensus
+      (2 <= N <= 16) the one with the largest CIDEr-D against the image's other hypotheses, scored on the device.  With a selection
+      --output_file receives {"image_id", "caption", "rank", "logprob", "utility"} per image, which python -m vlp_amd.eval_captions reads as it stands.
 """
 import argparse
 import glob
@@ -58,6 +67,40 @@ def build_parser():
     p.add_argument("--output_file", default=None, help="where the predictions go (default: next to the checkpoint, <checkpoint>-<split>-captions.json)")
     p.add_argument("--num_hidden_layers", type=int, default=None, help="override the config's depth (plumbing tests)")
     return p
+
+
+MAX_CONSENSUS = 16          # vlp_amd.consensus: a consensus is taken among 2..16 hypotheses of an image
+
+
+def parse_args(argv=None):
+    """The parsed command line of this tool, or the parser's error exit: build_parser()'s flags, the n-best list and the selection flags of
+    vlp_amd.sample_img2txt (here they choose among the hypotheses of the beam instead of samples)."""
+    from .sample_img2txt import add_selection_flags
+    p = build_parser()
+    p.add_argument("--n_best", type=int, default=1,
+                   help="keep the N best finished hypotheses of every image's beam search, 1..--beam_size (default 1: the best one only)")
+    p.add_argument("--nbest_file", default=None, metavar="PATH",
+                   help="with --n_best >= 2: write every hypothesis here as {image_id, rank, caption, logprob, value} (--samples_file is an alias)")
+    add_selection_flags(p)
+    a = p.parse_args(argv)
+    if a.n_best > 1 and a.beam_size < 2:
+        p.error("--n_best %d lists the hypotheses of a beam search: it needs --beam_size >= 2 (got %d)" % (a.n_best, a.beam_size))
+    if not (1 <= a.n_best <= max(a.beam_size, 1)):
+        p.error("--n_best must be in 1..--beam_size = 1..%d (got %d)" % (max(a.beam_size, 1), a.n_best))
+    if a.select != "none" and a.n_best < 2:
+        p.error("--select %s chooses among the hypotheses of an image: it needs --n_best >= 2 (got %d)" % (a.select, a.n_best))
+    if a.select == "consensus" and not a.consensus_df:
+        p.error("--select consensus needs --consensus_df PATH (a table written by python -m vlp_amd.cider_df)")
+    if a.select != "consensus" and a.consensus_df:
+        p.error("--consensus_df %s needs --select consensus (it holds the document frequencies of the consensus score)" % a.consensus_df)
+    if a.select == "consensus" and a.n_best > MAX_CONSENSUS:
+        p.error("--select consensus scores 2..%d hypotheses of an image against each other (got --n_best %d)" % (MAX_CONSENSUS, a.n_best))
+    if a.samples_file and a.nbest_file and a.samples_file != a.nbest_file:
+        p.error("--samples_file is an alias of --nbest_file here: give one of them (got %s and %s)" % (a.samples_file, a.nbest_file))
+    a.nbest_file = a.nbest_file or a.samples_file
+    if a.nbest_file and a.n_best < 2:
+        p.error("--nbest_file %s holds the hypotheses of an n-best list: it needs --n_best >= 2 (got %d)" % (a.nbest_file, a.n_best))
+    return a
 
 
 # ---- host-only pieces --------------------------------------------------------------------------------------------------
@@ -187,7 +230,7 @@ def build_decoder(args, vocab, state, device):
     model = BertForSeq2SeqDecoder(config, mask_word_id=mask_id, num_labels=2, search_beam_size=args.beam_size, length_penalty=args.length_penalty,
                                   eos_id=sep_id, forbid_duplicate_ngrams=args.forbid_duplicate_ngrams,
                                   forbid_ignore_set=forbid_ignore_set(args.forbid_ignore_word, vocab), ngram_size=args.ngram_size, min_len=args.min_len,
-                                  enable_butd=args.enable_butd, len_vis_input=args.len_vis_input)
+                                  enable_butd=args.enable_butd, len_vis_input=args.len_vis_input, n_best=getattr(args, "n_best", 1))
     load_checkpoint_state(model, state)
     model.half()
     model.to(device)
@@ -220,8 +263,70 @@ def decode_images(model, store, keys, args, vocab, device):
     return captions
 
 
+def decode_images_nbest(model, store, keys, args, vocab, device, df=None):
+    """--n_best N >= 2: per store row of `keys`, in order, (hypotheses, pick).  hypotheses: N dicts {rank, caption, logprob, value, ok[,
+    utility]} from the ranked list of the image's beam search (vlp_beam_nbest; nothing but the final read goes to the host); pick: the rank
+    --select keeps -- none: 0; logprob: the ok hypothesis with the largest logprob; consensus (df: the table): the hypothesis with the
+    largest CIDEr-D against the image's other hypotheses, scored on the device, the rows of rank > 0 that are not ok emptied first.
+    Ties go to the lowest rank."""
+    from . import consensus as CS
+    from .scst import clean_captions
+    cls_id, unk_id, sep_id, mask_id, pad_id = special_ids(vocab)
+    Nv, bs, N = args.len_vis_input, args.batch_size, args.n_best
+    if store.nv != Nv:
+        raise RuntimeError("the packed store holds %d regions per image, --len_vis_input is %d" % (store.nv, Nv))
+    feat = torch.empty(bs, Nv, FEAT_DIM, dtype=torch.float16).pin_memory()
+    cls = torch.empty(bs, Nv, N_CLS, dtype=torch.float16).pin_memory()
+    bbox = torch.empty(bs, Nv, BOX_DIM, dtype=torch.float32).pin_memory()
+    input_ids, seg, pos, mask = decoder_inputs(bs, Nv, args.max_tgt_length, args.new_segment_ids, cls_id, unk_id, sep_id, device)
+    rows = store.rows(keys)
+    out = []
+    with torch.no_grad():
+        for i in range(0, len(rows), bs):
+            chunk = rows[i:i + bs]
+            n = len(chunk)
+            chunk = chunk + [chunk[-1]] * (bs - n)                  # a short last batch runs at the full size
+            store.gather(chunk, feat.numpy(), cls.numpy(), bbox.numpy())
+            img = feat.to(device, non_blocking=True)
+            regions = RawRegions(bbox.to(device, non_blocking=True), cls.to(device, non_blocking=True))
+            tr = model(img, regions, input_ids, seg, pos, mask, task_idx=None)
+            if args.select == "consensus":                          # launched before the read below: no synchronisation of its own
+                ok_nb = tr["nbest_ok"].transpose(0, 1).reshape(N * bs).bool()          # sample-major again: rank k of image b = row k*bs + b
+                ok_nb[:bs] = True                                   # rank 0 stays as it is
+                ids_nb = tr["nbest_seq"].transpose(0, 1).reshape(N * bs, -1)[:, :args.max_tgt_length]
+                ids_nb = clean_captions(ids_nb, sep_id, pad_id).masked_fill_(~ok_nb.unsqueeze(1), 0)
+                pick, utility = CS.consensus_select_device(ids_nb, N, df)
+                pick, utility = pick.tolist(), utility.view(N, bs).tolist()
+            ids, logp, val, ok = tr["nbest_seq"].tolist(), tr["nbest_score"].tolist(), tr["nbest_value"].tolist(), tr["nbest_ok"].tolist()
+            for b in range(n):                                      # (the rows that pad a short last batch are dropped, their picks too)
+                hyps = [{"rank": k, "caption": caption_of(ids[b][k], vocab, sep_id, pad_id), "logprob": logp[b][k], "value": val[b][k],
+                         "ok": bool(ok[b][k])} for k in range(N)]
+                k_sel = 0
+                if args.select == "consensus":
+                    k_sel = pick[b]
+                    for k in range(N):
+                        hyps[k]["utility"] = utility[k][b]
+                elif args.select == "logprob":
+                    k_sel = int(CS.first_max([h["logprob"] if h["ok"] else -float("inf") for h in hyps], N)[0])
+                out.append((hyps, k_sel))
+    return out
+
+
+def nbest_path(args, ckpt, n_ckpts):
+    """--nbest_file, with the checkpoint's name in it when there are several (as output_path does for --output_file)."""
+    if n_ckpts == 1:
+        return args.nbest_file
+    root, ext = os.path.splitext(args.nbest_file)
+    return "%s.%s%s" % (root, os.path.splitext(os.path.basename(ckpt))[0], ext)
+
+
+def _finite(x):
+    """json has no -inf: the logprob / value of an empty hypothesis are written as null."""
+    return x if x == x and abs(x) != float("inf") else None
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     require_fp16(args)
     if args.enable_butd:
         assert args.len_vis_input == 100
@@ -250,6 +355,11 @@ def main(argv=None):
             valid_jpgs = set(json.load(f))
     images = select_images(img_dat, args.split, args.dataset, valid_jpgs)
     store = PackedRegionStore(args.packed_features)
+    df = None
+    if args.select == "consensus":
+        from .sample_img2txt import consensus_doc_freq
+        df = consensus_doc_freq(args.consensus_df, args.max_tgt_length, special_ids(vocab)[2])
+        logger.info("--consensus_df %s: %d n-grams over %d images", args.consensus_df, len(df), df.n_docs)
 
     ckpts = sorted(glob.glob(args.model_recover_path.strip()))
     if not ckpts:
@@ -258,8 +368,21 @@ def main(argv=None):
     for ckpt in ckpts:
         logger.info("***** Recover model: %s *****", ckpt)
         model = build_decoder(args, vocab, torch.load(ckpt, map_location="cpu"), device)
-        captions = decode_images(model, store, [key for _, key in images], args, vocab, device)
-        predictions = [{"image_id": imgid, "caption": cap} for (imgid, _), cap in zip(images, captions)]
+        if args.n_best > 1:
+            ranked = decode_images_nbest(model, store, [key for _, key in images], args, vocab, device, df=df)
+            if args.nbest_file:          # every hypothesis that is one: rank 0 always, the others when ok
+                with open(nbest_path(args, ckpt, len(ckpts)), "w") as f:
+                    json.dump([dict({"image_id": imgid, "rank": h["rank"], "caption": h["caption"], "logprob": _finite(h["logprob"]),
+                                     "value": _finite(h["value"])}, **({"utility": h["utility"]} if "utility" in h else {}))
+                               for (imgid, _), (hyps, _) in zip(images, ranked) for h in hyps if h["ok"] or h["rank"] == 0], f)
+            if args.select == "none":
+                predictions = [{"image_id": imgid, "caption": hyps[0]["caption"]} for (imgid, _), (hyps, _) in zip(images, ranked)]
+            else:
+                predictions = [{"image_id": imgid, "caption": hyps[k]["caption"], "rank": k, "logprob": _finite(hyps[k]["logprob"]),
+                                "utility": hyps[k].get("utility")} for (imgid, _), (hyps, k) in zip(images, ranked)]
+        else:
+            captions = decode_images(model, store, [key for _, key in images], args, vocab, device)
+            predictions = [{"image_id": imgid, "caption": cap} for (imgid, _), cap in zip(images, captions)]
         out = output_path(args, ckpt, len(ckpts))
         with open(out, "w") as f:
             json.dump(predictions, f)

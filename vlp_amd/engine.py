@@ -1374,6 +1374,30 @@ class Engine(object):
         ws["calls"] += 1
         return tot[:n_steps].clone(), wids[:n_steps].clone(), ptrs[:n_steps].clone()
 
+    def beam_nbest(self, tot, wids, ptrs, n_best, eos_id, length_penalty, out_len):
+        """The n_best best finished hypotheses of the frames decode_beam returned ([frames, B, K]), ranked and back-tracked on the device
+        (vlp_beam_nbest; the rule is vlp_amd.nbest.beam_nbest_host's): one launch on the current stream, nothing goes to the host.
+        Returns (seq int64 [n_best*B, out_len], score f32, value f64, len int32, ok uint8, each [n_best*B]), sample-major (rank n of image b
+        is row n*B + b).  The outputs belong to the decode workspace of that search: the next call with the same shapes overwrites them."""
+        from .nbest import check_limits
+        if tot.dim() != 3 or wids.shape != tot.shape or ptrs.shape != tot.shape:
+            raise ValueError("beam_nbest takes the three [frames, B, K] tensors of decode_beam")
+        F, B, Kb = (int(v) for v in tot.shape)
+        N, out_len = int(n_best), int(out_len)
+        check_limits(F, B, Kb, N, out_len)
+        ws = self._ws.get(("dec", B, out_len - F + 1, out_len, Kb))
+        if ws is None:
+            raise RuntimeError("vlp_amd: beam_nbest ranks the frames of a decode_beam call of this engine; there was none with batch %d, beam %d, "
+                               "%d frames and output length %d" % (B, Kb, F, out_len))
+        out = ws.setdefault("nbest", {}).get(N)
+        if out is None:
+            dev = self.device
+            out = ws["nbest"][N] = (torch.empty(N * B, out_len, device=dev, dtype=torch.long), torch.empty(N * B, device=dev, dtype=torch.float32),
+                                    torch.empty(N * B, device=dev, dtype=torch.float64), torch.empty(N * B, device=dev, dtype=torch.int32),
+                                    torch.empty(N * B, device=dev, dtype=torch.uint8))
+        K.beam_nbest(tot.contiguous(), wids.contiguous(), ptrs.contiguous(), N, int(eos_id), float(length_penalty), *out)
+        return out
+
     # ------------------------------------------------------------------------------------------
     # self-critical sequence training: the gradient of the sampled captions' log-probabilities
     # ------------------------------------------------------------------------------------------

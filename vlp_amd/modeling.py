@@ -616,10 +616,13 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     # forbid_duplicate_ngrams with ngram_size >= 2: "device" = Engine.decode_beam(ngram=...) (vlp_ngram_candidates / vlp_logsoftmax_topk_list, no
     # host round trip, token steps replayed from captured graphs); "host" = the _ngram_blocker closure (A/B and fallback).  Same results.
     ngram_blocking = "device"
+    # where beam_search turns the frames into hypotheses: "host" = _backtrack_batch (numpy, one device -> host copy of the frames, the best
+    # hypothesis only); "device" = Engine.beam_nbest (vlp_beam_nbest: ranked n-best list, no copy).  n_best > 1 always takes the device.
+    backtrack = "host"
 
     def __init__(self, config, mask_word_id=0, num_labels=2, search_beam_size=1, length_penalty=1.0, eos_id=0,
                  forbid_duplicate_ngrams=False, forbid_ignore_set=None, ngram_size=3, min_len=0, enable_butd=False, len_vis_input=49,
-                 allow_random_fc7=True):
+                 allow_random_fc7=True, n_best=1):
         super(BertForSeq2SeqDecoder, self).__init__(config)
         self.bert = BertModelIncr(config)
         self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight, num_labels=num_labels)
@@ -627,6 +630,9 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         self.mask_word_id, self.num_labels, self.len_vis_input = mask_word_id, num_labels, len_vis_input
         self.search_beam_size, self.length_penalty, self.eos_id = search_beam_size, length_penalty, eos_id
         self.forbid_duplicate_ngrams, self.forbid_ignore_set, self.ngram_size, self.min_len = forbid_duplicate_ngrams, forbid_ignore_set, ngram_size, min_len
+        self.n_best = int(n_best)
+        if self.n_best < 1 or self.n_best > max(int(search_beam_size), 1):
+            raise ValueError("n_best=%d: the n-best list of a beam search holds 1..search_beam_size (%d) hypotheses" % (self.n_best, search_beam_size))
         _region_embedders(self, config, enable_butd, allow_random_fc7)
         self.__dict__["_engine"] = Engine(self)
         for prm in self.parameters():
@@ -808,9 +814,17 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
 
     def beam_search(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None):
         """Returns the reference's traces dict (:1436-1494): 'pred_seq' [B, L] (0 padded), 'scores' f32 / 'wids' / 'ptrs' [B, L, K]
-        (frames padded with zeros to the output length L), on the input device."""
+        (frames padded with zeros to the output length L), on the input device.
+        With n_best = N > 1 or backtrack = "device" the hypotheses come from vlp_beam_nbest (Engine.beam_nbest; the rule is
+        vlp_amd.nbest.beam_nbest_host's, rank 0 the hypothesis of the host path) and nothing is copied to the host; the dict then also carries
+        the ranked list of every image: 'nbest_seq' [B, N, L], 'nbest_score' f32 (cumulative log-probability) / 'nbest_value' f64 (score +
+        length_penalty * length) / 'nbest_len' int32 / 'nbest_ok' uint8 [B, N] (0: a hypothesis that went on after its eos, or an empty one)."""
         B, out_len = input_ids.shape[0], token_type_ids.shape[1]
         K = self.search_beam_size
+        if self.backtrack not in ("device", "host"):
+            raise ValueError("backtrack must be 'device' or 'host', got %r" % (self.backtrack,))
+        if not 1 <= self.n_best <= K:
+            raise ValueError("n_best=%d: the n-best list of a beam search holds 1..search_beam_size (%d) hypotheses" % (self.n_best, K))
         forbid_fn = ngram = None
         if self.forbid_duplicate_ngrams:
             if self.ngram_blocking not in ("device", "host"):
@@ -830,6 +844,14 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         scores[:, :frames] = tot.permute(1, 0, 2)
         wid_o[:, :frames] = wids.permute(1, 0, 2)
         ptr_o[:, :frames] = ptrs.permute(1, 0, 2)
+        if self.n_best > 1 or self.backtrack == "device":
+            from .nbest import by_image
+            N = self.n_best
+            seq, score, value, length, ok = self.engine.beam_nbest(tot, wids, ptrs, N, self.eos_id, self.length_penalty, out_len)
+            out = {"pred_seq": seq[:B].clone(), "scores": scores, "wids": wid_o, "ptrs": ptr_o}     # (copies: the workspace keeps the kernel's rows)
+            for name, t in (("nbest_seq", seq), ("nbest_score", score), ("nbest_value", value), ("nbest_len", length), ("nbest_ok", ok)):
+                out[name] = by_image(t, N).clone(memory_format=torch.contiguous_format)
+            return out
         # best hypothesis of every sample (:1446-1474), vectorised over the batch on the host: ONE device -> host copy of the three frame tensors
         pred = self._backtrack_batch(tot.cpu().numpy(), wids.cpu().numpy(), ptrs.cpu().numpy(), out_len)
         return {"pred_seq": torch.from_numpy(pred).to(dev), "scores": scores, "wids": wid_o, "ptrs": ptr_o}
