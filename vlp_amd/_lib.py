@@ -858,16 +858,33 @@ def cider_d_multi(hyp, ref, ref_count, mult, scores, reward=None, sigma=6.0, wor
     _check(load().vlp_cider_d_multi(C.byref(a), stream_ptr()))
 
 
+def _req_strings(who, hyp, ref, ref_count, mult):
+    """The checks of hyp, ref and ref_count that the scoring entries share (`who` names the entry in the message); returns (G, R, T)."""
+    if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
+        raise RuntimeError("vlp_amd.%s: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows" % who)
+    G, R, T = ref.shape
+    if hyp.shape[0] != mult * G or hyp.shape[1] != T:
+        raise RuntimeError("vlp_amd.%s: hyp must be [%d, %d]" % (who, mult * G, T))
+    if ref_count is not None and (ref_count.dtype != torch.int32 or not ref_count.is_contiguous() or ref_count.numel() != G):
+        raise RuntimeError("vlp_amd.%s: ref_count must be contiguous int32 [%d]" % (who, G))
+    return G, R, T
+
+
+def _req_table(who, pre, keys, vals):
+    """The checks of a document-frequency table that the entries with one share (`pre`: "df_" where the arguments are df_keys / df_vals);
+    returns (keys pointer, vals pointer, N), the pointers None for an empty table."""
+    _req_cuda(keys, vals)
+    if (keys.dtype not in (torch.int64, torch.uint64) or vals.dtype != torch.int32 or keys.dim() != 1 or vals.dim() != 1
+            or not keys.is_contiguous() or not vals.is_contiguous() or keys.numel() != vals.numel()):
+        raise RuntimeError("vlp_amd.%s: %skeys int64 [N] (the uint64 keys' bits) and %svals int32 [N], contiguous" % (who, pre, pre))
+    n = keys.numel()
+    return (ptr(keys) if n else None), (ptr(vals) if n else None), n
+
+
 def _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes, reward_rows=1):
     """The operand checks and the argument struct the cider_d entries share (reward_rows: the reward holds reward_rows * G elements)."""
     _req_cuda(hyp, ref, ref_count, scores, reward, workspace)
-    if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
-        raise RuntimeError("vlp_amd.cider_d: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
-    G, R, T = ref.shape
-    if hyp.shape[0] != mult * G or hyp.shape[1] != T:
-        raise RuntimeError("vlp_amd.cider_d: hyp must be [%d, %d]" % (mult * G, T))
-    if ref_count is not None and (ref_count.dtype != torch.int32 or not ref_count.is_contiguous() or ref_count.numel() != G):
-        raise RuntimeError("vlp_amd.cider_d: ref_count must be contiguous int32 [%d]" % G)
+    G, R, T = _req_strings("cider_d", hyp, ref, ref_count, mult)
     if scores.dtype != torch.float32 or not scores.is_contiguous() or scores.numel() < mult * G:
         raise RuntimeError("vlp_amd.cider_d: scores must be contiguous f32 [%d]" % (mult * G))
     if reward is not None and (reward.dtype != torch.float32 or not reward.is_contiguous() or reward.numel() < reward_rows * G):
@@ -895,13 +912,9 @@ def cider_d_df(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, rewa
 
 def _cider_d_df_args(hyp, ref, ref_count, mult, scores, df_keys, df_vals, n_docs, reward, sigma, workspace, workspace_bytes, reward_rows):
     """The table checks and the argument struct cider_d_df and cider_d_multi_df share."""
-    _req_cuda(df_keys, df_vals)
-    if (df_keys.dtype not in (torch.int64, torch.uint64) or df_vals.dtype != torch.int32 or df_keys.dim() != 1 or df_vals.dim() != 1
-            or not df_keys.is_contiguous() or not df_vals.is_contiguous() or df_keys.numel() != df_vals.numel()):
-        raise RuntimeError("vlp_amd.cider_d_df: df_keys int64 [N] (the uint64 keys' bits) and df_vals int32 [N], contiguous")
+    table = _req_table("cider_d_df", "df_", df_keys, df_vals)
     s = _cider_d_args(hyp, ref, ref_count, mult, scores, reward, sigma, workspace, workspace_bytes, reward_rows=reward_rows)
-    n = df_keys.numel()
-    a = CiderDDfArgs(s, ptr(df_keys) if n else None, ptr(df_vals) if n else None, n, int(n_docs))
+    a = CiderDDfArgs(s, *table, int(n_docs))
     a._keep = s                              # (its workspace lives until the launch has been enqueued)
     return a
 
@@ -928,7 +941,7 @@ def cider_d_consensus(hyp, K, keys, vals, n_docs, utility, pick, pair=None, sigm
     sample k of image g (rows may be strided); keys / vals / n_docs the table as for cider_d_df; utility f32 [K*G] (sample k against the
     image's other K - 1), pick int32 [G] (the first largest utility), pair f32 [G, K, K] or None (sample k against sample j alone, 0 on the
     diagonal).  workspace: cider_d_consensus_workspace_bytes() bytes or None (a fresh allocation).  Two launches on the current stream."""
-    _req_cuda(hyp, keys, vals, utility, pick, pair, workspace)
+    _req_cuda(hyp, utility, pick, pair, workspace)
     if hyp.dtype != torch.int64 or hyp.dim() != 2 or hyp.stride(1) != 1:
         raise RuntimeError("vlp_amd.cider_d_consensus: hyp int64 [K*G, T] with contiguous rows")
     KG, T = hyp.shape
@@ -936,9 +949,7 @@ def cider_d_consensus(hyp, K, keys, vals, n_docs, utility, pick, pair=None, sigm
     if K < 1 or KG % K:
         raise RuntimeError("vlp_amd.cider_d_consensus: %d rows are not %d samples of every image" % (KG, K))
     G = KG // K
-    if (keys.dtype not in (torch.int64, torch.uint64) or vals.dtype != torch.int32 or keys.dim() != 1 or vals.dim() != 1
-            or not keys.is_contiguous() or not vals.is_contiguous() or keys.numel() != vals.numel()):
-        raise RuntimeError("vlp_amd.cider_d_consensus: keys int64 [N] (the uint64 keys' bits) and vals int32 [N], contiguous")
+    table = _req_table("cider_d_consensus", "", keys, vals)
     if utility.dtype != torch.float32 or not utility.is_contiguous() or utility.numel() < KG:
         raise RuntimeError("vlp_amd.cider_d_consensus: utility must be contiguous f32 [%d]" % KG)
     if pick.dtype != torch.int32 or not pick.is_contiguous() or pick.numel() < G:
@@ -947,9 +958,8 @@ def cider_d_consensus(hyp, K, keys, vals, n_docs, utility, pick, pair=None, sigm
         raise RuntimeError("vlp_amd.cider_d_consensus: pair must be contiguous f32 [%d, %d, %d]" % (G, K, K))
     if workspace is None:
         workspace = torch.empty(max(cider_d_consensus_workspace_bytes(G, K, T), 1), device=hyp.device, dtype=torch.uint8)
-    n = keys.numel()
-    a = CiderDConsensusArgs(ptr(hyp), hyp.stride(0), G, K, T, sigma, ptr(keys) if n else None, ptr(vals) if n else None, n, int(n_docs), ptr(utility),
-                            ptr(pick), ptr(pair), ptr(workspace), _nbytes(workspace))
+    a = CiderDConsensusArgs(ptr(hyp), hyp.stride(0), G, K, T, sigma, *table, int(n_docs), ptr(utility), ptr(pick), ptr(pair), ptr(workspace),
+                            _nbytes(workspace))
     _check(load().vlp_cider_d_consensus(C.byref(a), stream_ptr()))   # (a fresh workspace lives until the launches have been enqueued)
 
 
@@ -963,14 +973,8 @@ def bleu4(hyp, ref, ref_count, mult, bleu4, stats=None, base=None, w_base=1.0, w
     None: [G] = mixed[:G] - mixed[G:] (mult == 2), or with loo=True [mult*G], every mixed score minus the mean of its group's others.  One
     launch on the current stream, no workspace."""
     _req_cuda(hyp, ref, ref_count, bleu4, stats, base, mixed, reward)
-    if hyp.dtype != torch.int64 or ref.dtype != torch.int64 or hyp.dim() != 2 or ref.dim() != 3 or hyp.stride(1) != 1 or ref.stride(2) != 1:
-        raise RuntimeError("vlp_amd.bleu4: hyp int64 [mult*G, T] and ref int64 [G, R, T] with contiguous rows")
-    G, R, T = ref.shape
+    G, R, T = _req_strings("bleu4", hyp, ref, ref_count, mult)
     n = mult * G
-    if hyp.shape[0] != n or hyp.shape[1] != T:
-        raise RuntimeError("vlp_amd.bleu4: hyp must be [%d, %d]" % (n, T))
-    if ref_count is not None and (ref_count.dtype != torch.int32 or not ref_count.is_contiguous() or ref_count.numel() != G):
-        raise RuntimeError("vlp_amd.bleu4: ref_count must be contiguous int32 [%d]" % G)
     for name, t, need in (("bleu4", bleu4, n), ("base", base, n), ("mixed", mixed, n), ("reward", reward, n if loo else G)):
         if t is None and name != "bleu4":
             continue

@@ -2,15 +2,16 @@
 // the six integers corpus BLEU-1..4 is made of, and per reference the longest common subsequence ROUGE-L is made of.  The specifications are
 // vlp_amd/scst.py CiderD(df=<DocFreq>) and Bleu.sentence_stats and vlp_amd/caption_metrics.py Rouge, all on WORD STRINGS: the ids of a row
 // before its first 0 (the 0 is padding, never a token; an empty string is legal).  The reward kernels of reward.hip read a row up to and
-// including that 0; the staging and matching helpers of both files are reward_common.h's, instantiated here with END = 0.
+// including that 0; both files are composed of reward_common.h's pieces, instantiated here with END = 0.
 //
-//   ce_count_kernel   cider_count_kernel<true> of reward.hip for word strings and one hypothesis per group: one block per string (the G
-//                     hypotheses, then the G*R references), one lane per (position, order) looks the n-gram up in the table; wave 0 then
-//                     counts multiplicity and first occurrence inside the string and writes the four L2 norms, and for a hypothesis
-//                     (tf, first) and idf per position and order.
-//   ce_score_kernel   one wave per group, one lane per hypothesis position: the count of the n-grams that start there in every valid
-//                     reference.  The counts feed both cider_score_kernel<true>'s arithmetic (clipped products, norms, Gaussian penalty,
-//                     mean, x 10: the same operations in the same order) and bleu4_kernel's integers (correct_1..4, len_h, closest reflen).
+//   counting pass     cider_count_kernel<true, 0> (reward_common.h: the kernel vlp_cider_d_df launches as <true, 1>) with one hypothesis per
+//                     group: one block per string (the G hypotheses, then the G*R references), one lane per (position, order) looks the
+//                     n-gram up in the table; wave 0 then counts multiplicity and first occurrence inside the string and writes the four L2
+//                     norms, and for a hypothesis (tf, first) and idf per position and order.
+//   ce_score_kernel   one wave per group, one lane per hypothesis position: cd_count_row counts the n-grams that start there in every valid
+//                     reference once, and the counts feed both cd_cider_terms (cider_score_kernel<true>'s arithmetic: clipped products,
+//                     norms, Gaussian penalty; then the mean, x 10) and cd_bleu_update / cd_bleu_correct (bleu4_kernel's integers:
+//                     correct_1..4, len_h, closest reflen).
 //   ce_lcs_kernel     one wave per (hypothesis, reference) pair, lane q holding reference token q.  For hypothesis token j the ballot
 //                     M = (ref_q == h_j, q < len_r) is the match mask of the whole reference; the wave-uniform 64-bit recurrence
 //                     V = ~0;  u = V & M;  V = (V + u) | (V & ~M)  (the carry out of bit 63 dropped) keeps a 0 bit per step of the LCS
@@ -19,150 +20,32 @@
 // fp32 with the accurate logf / expf / sqrtf, every sum in a fixed order, no atomics: equal inputs give bit-equal outputs.
 #include "reward_common.h"
 
-__global__ __launch_bounds__(CD_THREADS) void ce_count_kernel(vlp_cider_d_args a, int* info, float* idf_out, float* norms, cd_table tab) {
-    __shared__ int qrow[64 + CD_PAD], srow[64 + CD_PAD];               // the block's string with the query's / a reference's sentinel
-    __shared__ int cnt[4][64];
-    const int T = a.T, R = a.R, G = a.G;
-    const int s = blockIdx.x, tid = threadIdx.x, k = tid >> 6, q = tid & 63;
-    const bool is_hyp = s < G;
-    const int64_t* src;
-    if (is_hyp) {
-        src = a.hyp + (int64_t)s * a.hyp_ld;
-    } else {
-        const int row = s - G, g = row / R, r = row - g * R;
-        if (r >= cd_ref_count(a.ref_count, g, R)) return;              // not a reference of its group: nobody reads its norms (block-uniform)
-        src = a.ref + (int64_t)g * a.ref_group_stride + (int64_t)r * a.ref_ld;
-    }
-    if (tid < 64) {                                                    // wave 0: the block's own string
-        const int tok = tid < T ? (int)src[tid] : CD_HYP_END;
-        const int len = cd_len_of<0>(__ballot(tid < T && tok == 0), T);
-        if (tid < T) {
-            qrow[tid] = tid < len ? tok : CD_HYP_END;
-            srow[tid] = tid < len ? tok : CD_REF_END;
-        }
-        if (tid < CD_PAD) {
-            qrow[T + tid] = CD_HYP_END;
-            srow[T + tid] = CD_REF_END;
-        }
-    }
-    __syncthreads();
-    // lane (order k, position q): the table df of the k+1-gram that starts there.  A sentinel (the string ends inside the n-gram) or an id
-    // outside [0, 65535) forms no key: df 0
-    int df = 0;
-    if (q < T) {
-        uint64_t key = 0;
-        bool ok = true;
-        for (int j = 0; j <= k; ++j) {
-            const int t = qrow[q + j];
-            ok = ok && t >= 0 && t < 65535;
-            key |= (uint64_t)(((unsigned)t + 1u) & 0xffffu) << (48 - 16 * j);   // (used only when every id is in range)
-        }
-        if (ok) df = cd_table_df(tab, key);
-    }
-    cnt[k][q] = df;
-    __syncthreads();
-    if (tid >= 64) return;
-
-    // wave 0, lane = position: multiplicity and first occurrence inside the own string, then weights and norms
-    int tf[4] = {0, 0, 0, 0}, first[4] = {1, 1, 1, 1};
-    if (tid < T) {
-        const int a0 = qrow[tid], a1 = qrow[tid + 1], a2 = qrow[tid + 2], a3 = qrow[tid + 3];
-        int b0 = srow[0], b1 = srow[1], b2 = srow[2];
-        for (int p = 0; p < T; ++p) {
-            const int b3 = srow[p + 3];
-            const int m = cd_match(a0, a1, a2, a3, b0, b1, b2, b3);
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                tf[o] += m > o;
-                first[o] &= !(m > o && p < tid);
-            }
-            b0 = b1; b1 = b2; b2 = b3;
-        }
-    }
-    const float ref_len = logf(tab.n_docs);
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        const float idf = ref_len - logf(fmaxf(1.f, (float)(tid < T ? cnt[o][tid] : 0)));
-        float v = 0.f;
-        if (tid < T && tf[o] > 0 && first[o]) v = (float)tf[o] * idf;
-        const float n2 = wave_sum(v * v);
-        if (tid == 0) norms[(int64_t)s * 4 + o] = sqrtf(n2);
-        if (is_hyp && tid < T) {
-            info[((int64_t)s * 4 + o) * T + tid] = cd_pack(0, tf[o], tf[o] > 0 && first[o]);
-            idf_out[((int64_t)s * 4 + o) * T + tid] = idf;
-        }
-    }
-}
-
 __global__ __launch_bounds__(64) void ce_score_kernel(vlp_cider_d_args a, const int* info, const float* idf_in, const float* norms, int32_t* stats) {
     __shared__ int cd_refs[8 * (64 + CD_PAD)];                         // [R][T + CD_PAD]
     __shared__ int ref_len_s[8];
     const int T = a.T, R = a.R, G = a.G, ldr = T + CD_PAD;
     const int g = blockIdx.x, lane = threadIdx.x;
     cd_stage_refs<0>(a, g * R, R, cd_refs, ref_len_s, 64, 64);
-
-    const int tok = lane < T ? (int)a.hyp[(int64_t)g * a.hyp_ld + lane] : CD_HYP_END;
-    const int len = cd_len_of<0>(__ballot(lane < T && tok == 0), T);
-    int av[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int t = __shfl(tok, (lane + j) & 63, 64);
-        av[j] = lane + j < len ? t : CD_HYP_END;
-    }
+    int tok, av[4];
+    const int len = cd_load_hyp<0>(a.hyp + (int64_t)g * a.hyp_ld, T, lane, tok, av);
     __syncthreads();
 
     float idf[4], hv[4], nh[4], acc[4] = {0.f, 0.f, 0.f, 0.f};
-    int tf[4], best[4] = {0, 0, 0, 0};
-    bool first[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int pk = lane < T ? info[((int64_t)g * 4 + k) * T + lane] : 0;
-        idf[k] = lane < T ? idf_in[((int64_t)g * 4 + k) * T + lane] : 0.f;
-        tf[k] = (pk >> 11) & 127;
-        hv[k] = (float)tf[k] * idf[k];
-        first[k] = (pk >> 18) & 1;
-        nh[k] = norms[(int64_t)g * 4 + k];
-    }
+    int tf[4], first[4], t[4], best[4] = {0, 0, 0, 0}, correct[4];
+    cd_load_weights<true>(info, idf_in, norms, g, T, lane, 1, 1, idf, tf, hv, first, nh);
     const int nr = cd_ref_count(a.ref_count, g, R);
     const float two_sigma2 = 2.f * a.sigma * a.sigma;
     int reflen = 0, refdist = 1 << 30;
     for (int r = 0; r < nr; ++r) {
-        const int* row = cd_refs + r * ldr;
-        int t[4] = {0, 0, 0, 0};
-        int b0 = row[0], b1 = row[1], b2 = row[2];
-        for (int q = 0; q < T; ++q) {
-            const int b3 = row[q + 3];
-            const int m = cd_match(av[0], av[1], av[2], av[3], b0, b1, b2, b3);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] += m > k;
-            b0 = b1; b1 = b2; b2 = b3;
-        }
-        // CIDEr-D: the clipped products of this reference
-        const int lr = ref_len_s[r];
-        const float delta = (float)(max(len - 1, 0) - max(lr - 1, 0));
-        const float penalty = expf(-(delta * delta) / two_sigma2);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float rv = (float)t[k] * idf[k];
-            float val = wave_sum(first[k] ? fminf(hv[k], rv) * rv : 0.f);
-            const float nrk = norms[((int64_t)G + (int64_t)g * R + r) * 4 + k];
-            if (nh[k] != 0.f && nrk != 0.f) val /= nh[k] * nrk;
-            acc[k] += val * penalty;
-        }
-        // BLEU: the largest count over the references; the closest reference length, the shorter on a tie
-#pragma unroll
-        for (int k = 0; k < 4; ++k) best[k] = max(best[k], t[k]);
-        const int d = abs(lr - len);
-        if (d < refdist || (d == refdist && lr < reflen)) { refdist = d; reflen = lr; }
+        cd_count_row(av, cd_refs + r * ldr, T, t);
+        cd_cider_terms(t, idf, hv, first, nh, norms + ((int64_t)G + (int64_t)g * R + r) * 4, len, ref_len_s[r], two_sigma2, acc, nullptr);
+        cd_bleu_update(t, ref_len_s[r], len, best, reflen, refdist);
     }
     const float score = (acc[0] + acc[1] + acc[2] + acc[3]) / 4.f / (float)nr * 10.f;
-    int correct[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) correct[k] = wave_sum_int(first[k] ? min(tf[k], best[k]) : 0);
+    cd_bleu_correct(tf, first, best, correct);
     if (lane == 0) {
         a.scores[g] = score;
-        int32_t* st = stats + (int64_t)g * 6;
-        st[0] = correct[0]; st[1] = correct[1]; st[2] = correct[2]; st[3] = correct[3]; st[4] = len; st[5] = reflen;
+        cd_bleu_stats(stats + (int64_t)g * 6, correct, len, reflen);
     }
 }
 
@@ -206,13 +89,11 @@ extern "C" int vlp_caption_eval(const vlp_caption_eval_args* e, void* stream) {
     VLP_CHECK_ARG(e->bleu_stats && e->lcs, "vlp_caption_eval: null bleu_stats or lcs");
     VLP_ENTER(a->ref, "vlp_caption_eval");
     const int G = a->G, SR = a->G * a->R;
-    int* info = (int*)a->workspace;                                    // the layout of vlp_cider_d_df's workspace with mult = 1
-    float* idf = (float*)(info + cd_info_ints(G, a->T, 1));
-    float* norms = idf + cd_info_ints(G, a->T, 1);
-    const cd_table tab = {d->df_keys, d->df_vals, d->df_n, (float)d->n_docs};
-    hipLaunchKernelGGL(ce_count_kernel, dim3(G + SR), dim3(CD_THREADS), 0, (hipStream_t)stream, *a, info, idf, norms, tab);
+    const cd_workspace ws = cd_carve(a->workspace, G, a->T, 1, true);  // the layout of vlp_cider_d_df's workspace with mult = 1
+    cd_launch_count_table<0>(*a, G + SR, ws, cd_table_of(d), stream);
     VLP_CHECK_LAUNCH("vlp_caption_eval");
-    hipLaunchKernelGGL(ce_score_kernel, dim3(G), dim3(64), 0, (hipStream_t)stream, *a, (const int*)info, (const float*)idf, (const float*)norms, e->bleu_stats);
+    hipLaunchKernelGGL(ce_score_kernel, dim3(G), dim3(64), 0, (hipStream_t)stream, *a, (const int*)ws.info, (const float*)ws.idf, (const float*)ws.norms,
+                       e->bleu_stats);
     VLP_CHECK_LAUNCH("vlp_caption_eval");
     hipLaunchKernelGGL(ce_lcs_kernel, dim3(cdiv(SR, CE_LCS_WAVES)), dim3(64 * CE_LCS_WAVES), 0, (hipStream_t)stream, *a, e->lcs);
     VLP_CHECK_LAUNCH("vlp_caption_eval");

@@ -413,15 +413,17 @@ def _mixed_scores(gts, res, scorer, cider_weight, bleu_weight):
     return scores
 
 
+def _host(x):
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
 def self_critical_reward(greedy_res, gt_ids, gen_result, batch_size, scorer=None, df=None, cider_weight=1.0, bleu_weight=0.0):
     """scst_utils.py:36-63: CIDEr-D of the B samples and the B greedy captions (2B hypotheses), each against its own ground truth (so the 2B
     reference sets are the ground truths twice); reward[b, :] = score(sample_b) - score(greedy_b) repeated over the T columns.  Arguments are
     id tensors or arrays [B, T]; returns (reward [B, T] float64 ndarray, scores [2B]).  df: a DocFreq whose document frequencies replace the
     call's own (ignored when a scorer is given).  cider_weight / bleu_weight: the score of a hypothesis is cider_weight * CIDEr-D +
     bleu_weight * sentence BLEU-4 (Bleu); (1, 0) is the CIDEr-D reward as it always was."""
-    def host(x):
-        return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    greedy_res, gt_ids, gen_result = host(greedy_res), host(gt_ids), host(gen_result)
+    greedy_res, gt_ids, gen_result = _host(greedy_res), _host(gt_ids), _host(gen_result)
     B = batch_size
     res, gts = OrderedDict(), OrderedDict()
     gen_s = [array_to_str(r) for r in gen_result[:B].tolist()]
@@ -481,21 +483,53 @@ def _refs_parts(refs, B):
     return refs[:B].unsqueeze(1), None
 
 
+def _ref_strings(refs, B):
+    """The reference strings of B samples, a list per sample: of a CaptionRefs the first count[b] rows (clamped to 1..R) of sample b, of [B, T]
+    ground-truth ids the one row."""
+    from .input_prep import CaptionRefs
+    if not isinstance(refs, CaptionRefs):
+        return [[array_to_str(r)] for r in _host(refs)[:B].tolist()]
+    ids, count = _host(refs.ids), _host(refs.count)
+    R = ids.shape[1]
+    return [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
+
+
+def _device_reward(hyp, ids, count, mult, loo, weights, scores_out, workspace, df):
+    """The launch sequence of the two device rewards on hyp [mult*B, T] against ids [B, R, T] / count: the CIDEr-D entry (its df form with a
+    DocFreq; its multi form with loo; only with a CIDEr-D weight > 0), then for weights other than (1, 0) vlp_bleu4, which mixes the scores
+    and writes the reward.  loo: the leave-one-out reward [mult*B], else scores[:B] - scores[B:] (mult == 2).  Returns (reward, scores)."""
+    from . import _lib as K
+    cw, bw = weights
+    n = hyp.shape[0]
+    nr = n if loo else n // mult
+    scores = scores_out if scores_out is not None else torch.empty(n, dtype=torch.float32, device=hyp.device)
+    mix = not (cw == 1 and bw == 0)
+    out = torch.empty(nr + n if mix else nr, dtype=torch.float32, device=hyp.device)      # the reward, then the BLEU-4 of the hypotheses
+    reward = out[:nr]
+    if cw > 0:
+        first = None if mix else reward                 # mixed: the reward is the vlp_bleu4 launch's
+        if df is None:
+            (K.cider_d_multi if loo else K.cider_d)(hyp, ids, count, mult, scores, reward=first, sigma=_scorer.sigma, workspace=workspace)
+        else:
+            keys, vals = df.to(hyp.device)
+            (K.cider_d_multi_df if loo else K.cider_d_df)(hyp, ids, count, mult, scores, keys, vals, df.n_docs, reward=first,
+                                                          sigma=_table_scorer(df).sigma, workspace=workspace)
+    if mix:
+        K.bleu4(hyp, ids, count, mult, out[nr:], base=scores if cw > 0 else None, w_base=cw, w_bleu=bw, mixed=scores, reward=reward, loo=loo)
+    return reward, scores
+
+
 def self_critical_reward_refs(greedy_res, refs, gen_result, df=None, cider_weight=1.0, bleu_weight=0.0):
     """self_critical_reward against one OR several references per sample, on the host with CiderD: `refs` is the [B, T] ground-truth ids
     (then this is self_critical_reward itself) or a CaptionRefs (ids [B, R, T], count [B]: sample b is scored against the first count[b]
     rows).  Returns (reward [B, T] float64 ndarray, scores [2B]).  The oracle of self_critical_reward_device, and the host path of
     multi-reference training.  df: a DocFreq whose document frequencies replace the call's own.  cider_weight / bleu_weight: as in
     self_critical_reward."""
-    def host(x):
-        return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
     from .input_prep import CaptionRefs
     B = len(gen_result)
     if not isinstance(refs, CaptionRefs):
         return self_critical_reward(greedy_res, refs, gen_result, B, df=df, cider_weight=cider_weight, bleu_weight=bleu_weight)
-    greedy_res, gen_result, ids, count = host(greedy_res), host(gen_result), host(refs.ids), host(refs.count)
-    R = ids.shape[1]
-    gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
+    greedy_res, gen_result, gt_s = _host(greedy_res), _host(gen_result), _ref_strings(refs, B)
     res, gts = OrderedDict(), OrderedDict()
     for i in range(B):
         res[i], gts[i] = [array_to_str(gen_result[i].tolist())], gt_s[i]
@@ -517,8 +551,7 @@ def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, w
     cider_weight / bleu_weight other than (1, 0): the CIDEr-D launches (only with cider_weight > 0) write their scores, then one vlp_bleu4
     launch scores sentence BLEU-4, replaces the scores by cider_weight * CIDEr-D + bleu_weight * BLEU-4 and writes the reward of those
     mixed scores: the returned scores are the mixed ones; df applies to the CIDEr-D part only.  Still no host work and capturable."""
-    from . import _lib as K
-    cw, bw = check_reward_weights(cider_weight, bleu_weight)
+    weights = check_reward_weights(cider_weight, bleu_weight)
     from .input_prep import CaptionRefs
     B, T = gen_result.shape
     if isinstance(refs, CaptionRefs):
@@ -526,20 +559,7 @@ def self_critical_reward_device(greedy_res, refs, gen_result, scores_out=None, w
     ids, count = _refs_parts(refs, B)
     if tuple(greedy_res.shape) != (B, T) or ids.shape[0] != B or ids.shape[2] != T:
         raise RuntimeError("self_critical_reward_device: samples, greedy captions and references must share [B, T] = [%d, %d]" % (B, T))
-    hyp = torch.cat([gen_result, greedy_res], 0)
-    scores = scores_out if scores_out is not None else torch.empty(2 * B, dtype=torch.float32, device=hyp.device)
-    mix = not (cw == 1 and bw == 0)
-    out = torch.empty(3 * B if mix else B, dtype=torch.float32, device=hyp.device)      # the reward, then the BLEU-4 of the 2B hypotheses
-    diff = out[:B]
-    if cw > 0:
-        first = None if mix else diff                   # mixed: the reward is the vlp_bleu4 launch's
-        if df is None:
-            K.cider_d(hyp, ids, count, 2, scores, reward=first, sigma=_scorer.sigma, workspace=workspace)
-        else:
-            keys, vals = df.to(hyp.device)
-            K.cider_d_df(hyp, ids, count, 2, scores, keys, vals, df.n_docs, reward=first, sigma=_table_scorer(df).sigma, workspace=workspace)
-    if mix:
-        K.bleu4(hyp, ids, count, 2, out[B:], base=scores if cw > 0 else None, w_base=cw, w_bleu=bw, mixed=scores, reward=diff)
+    diff, scores = _device_reward(torch.cat([gen_result, greedy_res], 0), ids, count, 2, False, weights, scores_out, workspace, df)
     return diff.unsqueeze(1).expand(B, T), scores
 
 
@@ -568,17 +588,9 @@ def self_critical_reward_group(gen_result, refs, n_samples, df=None, cider_weigh
     DocFreq `df` replaces both, without a K anywhere.  reward[k*B + b] = s[k*B + b] - (sum of s[j*B + b] over j != k, ascending j) / (K - 1).
     Returns (reward [K*B, T] float64 ndarray -- the [K*B] rewards repeated over the columns --, scores [K*B]).  cider_weight / bleu_weight:
     s is cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4, as in self_critical_reward."""
-    def host(x):
-        return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    from .input_prep import CaptionRefs
-    gen_result = host(gen_result)
+    gen_result = _host(gen_result)
     K, B = _check_samples(len(gen_result), n_samples)
-    if isinstance(refs, CaptionRefs):
-        ids, count = host(refs.ids), host(refs.count)
-        R = ids.shape[1]
-        gt_s = [[array_to_str(r) for r in ids[b, :min(max(int(count[b]), 1), R)].tolist()] for b in range(B)]
-    else:
-        gt_s = [[array_to_str(r)] for r in host(refs)[:B].tolist()]
+    gt_s = _ref_strings(refs, B)
     res, gts = OrderedDict(), OrderedDict()
     for i, row in enumerate(gen_result.tolist()):
         res[i], gts[i] = [array_to_str(row)], gt_s[i % B]
@@ -601,8 +613,7 @@ def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=No
     (_lib.cider_d_multi_workspace_bytes(B, R, T, K) or ..._multi_df_... bytes, uint8), else allocated per call.  No device -> host transfer,
     no synchronisation: two launches on the current stream, capturable.  df, cider_weight, bleu_weight: as in self_critical_reward_device
     (the vlp_bleu4 launch then writes the leave-one-out reward of the mixed scores)."""
-    from . import _lib as K_
-    cw, bw = check_reward_weights(cider_weight, bleu_weight)
+    weights = check_reward_weights(cider_weight, bleu_weight)
     from .input_prep import CaptionRefs
     KB, T = gen_result.shape
     K, B = _check_samples(KB, n_samples)
@@ -611,17 +622,5 @@ def self_critical_reward_group_device(gen_result, refs, n_samples, scores_out=No
     ids, count = _refs_parts(refs, B)
     if ids.shape[0] != B or ids.shape[2] != T:
         raise RuntimeError("self_critical_reward_group_device: %d samples of %d images need references [%d, R, %d]" % (K, B, B, T))
-    scores = scores_out if scores_out is not None else torch.empty(KB, dtype=torch.float32, device=gen_result.device)
-    mix = not (cw == 1 and bw == 0)
-    out = torch.empty(2 * KB if mix else KB, dtype=torch.float32, device=gen_result.device)      # the reward, then the BLEU-4 of the hypotheses
-    reward = out[:KB]
-    if cw > 0:
-        first = None if mix else reward                 # mixed: the reward is the vlp_bleu4 launch's
-        if df is None:
-            K_.cider_d_multi(gen_result, ids, count, K, scores, reward=first, sigma=_scorer.sigma, workspace=workspace)
-        else:
-            keys, vals = df.to(gen_result.device)
-            K_.cider_d_multi_df(gen_result, ids, count, K, scores, keys, vals, df.n_docs, reward=first, sigma=_table_scorer(df).sigma, workspace=workspace)
-    if mix:
-        K_.bleu4(gen_result, ids, count, K, out[KB:], base=scores if cw > 0 else None, w_base=cw, w_bleu=bw, mixed=scores, reward=reward, loo=True)
+    reward, scores = _device_reward(gen_result, ids, count, K, True, weights, scores_out, workspace, df)
     return reward.unsqueeze(1).expand(KB, T), scores
