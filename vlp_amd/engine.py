@@ -41,6 +41,12 @@ def is_no_decay(name):
     return any(nd in name for nd in NO_DECAY)
 
 
+def sample_major(t, B, Ks, n):
+    """Rows of a grouped sampled decode, [B*Ks, >= n] with row b*Ks + k, as a NEW [Ks*B, n] tensor with row k*B + b: one permuted copy
+    for every Ks.  (At Ks == 1 the permutation is the identity, and a reshape alone would hand the caller the workspace's own rows.)"""
+    return t[:, :n].view(B, Ks, n).transpose(0, 1).clone(memory_format=torch.contiguous_format).view(Ks * B, n)
+
+
 class VlpPerformanceWarning(UserWarning):
     """A correct but avoidably slow way of driving the engine (issued once per engine)."""
 
@@ -944,7 +950,7 @@ class Engine(object):
                   last_first=torch.full((R, 1), T0 - 1, device=dev, dtype=torch.long), last_step=torch.full((R, 1), 1, device=dev, dtype=torch.long),
                   # static copies of the caller's per-position inputs, so that the launches of a token step have call-invariant arguments
                   mask_static=i64(R, Lcap, Lcap), tt_steps=i64(Lcap, R, 2), pid_steps=i64(Lcap, R, 2),
-                  out_ids=i64(B, Lcap), out_val=f(B, Lcap), plans={}, calls=0, plan_stream=None,
+                  out_ids=i64(B, Lcap), out_val=f(B, Lcap), plans={}, calls=0, plan_stream=None, plans_aside={},
                   slab=f(self.DEC_SPLITS, R * 2, H),      # fp32 split-K partial sums of the token-step out-projection / FFN-down (vlp_dec_gemm -> vlp_dec_reduce_ln)
                   sk_ws=torch.empty(K.gemm_nt_splitk_workspace_bytes(min(M, 1024), max(I, 3 * H), max(tuning.SKINNY_SPLITS)), device=dev,
                                     dtype=torch.uint8))
@@ -1120,8 +1126,15 @@ class Engine(object):
         (torch.cuda.CUDAGraph over the launches our C ABI puts on the capture stream) and replays it; later calls only replay.
         If capture is unavailable the recorded ctypes plan (no Python argument marshalling) is the fallback."""
         stream = torch.cuda.current_stream().cuda_stream
+        if ws["plan_stream"] != stream:
+            # the plans of a workspace belong to ONE stream (a recorded ctypes plan carries it in the arguments of every launch): on another
+            # stream ALL of them are set aside, not only the one that meets the change, and they come back with their stream
+            aside = ws["plans_aside"]
+            if ws["plan_stream"] is not None:
+                aside[ws["plan_stream"]] = ws["plans"]
+            ws["plans"], ws["plan_stream"] = aside.pop(stream, {}), stream
         item = ws["plans"].get(key)
-        if item is not None and ws["plan_stream"] == stream:
+        if item is not None:
             if isinstance(item, list):
                 K.replay(item)
             else:
@@ -1130,7 +1143,6 @@ class Engine(object):
         if ws["calls"] == 0:
             fn()
             return
-        ws["plan_stream"] = stream
         if self.DECODE_GRAPHS:
             try:
                 g = torch.cuda.CUDAGraph()
@@ -1207,7 +1219,9 @@ class Engine(object):
         (_run_planned).  temperature / top_k / top_p other than (1, 0, 1) draw from the tempered, truncated distribution instead
         (vlp_sample_rows_filtered: same seed cell, seed_add and RNG stream; logp is the log-probability under that distribution); the
         values (1, 0, 1) issue the launches of a call without them.
-        Returns (ids [K*B, n] int64, logp [K*B, n] f32) sample-major: row k*B + b is sample k of image b."""
+        Returns (ids [K*B, n] int64, logp [K*B, n] f32) sample-major: row k*B + b is sample k of image b.  Both are copies the caller owns,
+        for every K (one copy each after the last token step, outside the captured steps): the next call at the same shapes overwrites the
+        workspace's rows, not a result somebody still holds -- as decode_greedy and decode_beam clone theirs."""
         self.pack()
         self.wait_params()
         V = self._model().config.vocab_size
@@ -1273,9 +1287,7 @@ class Engine(object):
             self._run_planned(ws, ("sample_group", s) + (() if plain else filt), step)
         ws["calls"] += 1
 
-        def sample_major(t):             # decode row b*K + k -> row k*B + b, one permuted copy
-            return t[:, :n_steps].view(B, Ks, n_steps).transpose(0, 1).reshape(R, n_steps)
-        return sample_major(out_ids), sample_major(out_val)
+        return sample_major(out_ids, B, Ks, n_steps), sample_major(out_val, B, Ks, n_steps)
 
     NGRAM_MAX_FRAMES = 256       # csrc/elementwise.hip: NGRAM_MAX_FRAMES frames per hypothesis (and <= TOPK_LIST_MAX = 1024 ids per list)
 
