@@ -47,6 +47,8 @@ extern "C" {
  * argument struct: purely additive as well. */
 /* + vlp_live_rows_build, vlp_gemm_nt_rows, vlp_gemm_tn_grouped_rows, vlp_layernorm_bwd_rows (listed-row backward of the last encoder layer):
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
+/* + vlp_beam_select_groups (diverse beam search: the selection step with the beams in groups): it takes vlp_beam_select_args as it is plus two
+ * scalars; purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -584,6 +586,22 @@ typedef struct {
     int64_t eos_id;
 } vlp_beam_select_args;
 int vlp_beam_select(const vlp_beam_select_args* a, void* stream);
+/* Diverse (group) beam search (Vijayakumar et al. 2016; not in the reference): vlp_beam_select with the K beams of a sample split into
+ * `groups` = G groups of Kg = K / G, extended one after another inside the step.  Per sample b, for g = 0 .. G-1:
+ *   candidates: the continuations of the group's own rows r in [g*Kg, (g+1)*Kg), index i = r*K + j, v0 = vlp_beam_select's value
+ *       kk + last_eos * -10000 + last_total (same expression and order); in the first step every group sees the single row (i = j, v0 = kk);
+ *   key = v0 - fl32(penalty * c), c = the number of picks of the groups < g of this step and sample whose word id is the candidate's (eos and
+ *       the picks of ended parents count); the product is rounded to fp32 before the subtraction; a NaN key orders as -inf;
+ *   Kg successive picks, each the maximum among the candidates after the previous pick in the (key descending, i ascending) order;
+ *   pick n of group g goes to slot b*K + g*Kg + n of the six outputs, which have vlp_beam_select's meaning; out_scores holds v0, the
+ *       unpenalised cumulative log-probability (the penalty steers the selection only).
+ * Back pointers stay inside their group (out_ptrs / Kg == slot / Kg).  groups = 1 gives vlp_beam_select's bits for any penalty when no v0 is NaN
+ * (vlp_beam_select has no NaN rule: it never picks a NaN candidate).  The per-row
+ * top-K lists suffice: a word outside a row's top K has K words above it, at most K - Kg of them penalised.
+ * One launch (one wave per sample, the earlier groups' picks and the group's keys in LDS), no synchronisation, capturable; equal inputs give
+ * bit-equal outputs.  VLP_ERR_BAD_ARG before any launch: a null operand, B <= 0, K outside 1..64, groups < 1, K % groups != 0, a penalty that
+ * is NaN, negative or infinite, first == 0 without last_total / last_eos. */
+int vlp_beam_select_groups(const vlp_beam_select_args* a, int32_t groups, float penalty, void* stream);
 /* Duplicate n-gram blocking on the device (get_dup_ngram_candidates, modeling.py:1391-1406), for a search that never leaves the GPU:
  *   vlp_ngram_candidates: wids / ptrs are the frames [frames, B, K] that vlp_beam_select writes (int64, contiguous).  Row r = b*K + k:
  *       the hypothesis that ends in beam k of frame s is rebuilt by following ptrs back from frame s (length s + 1 <= 256); the words that

@@ -9,13 +9,27 @@
                                                          backtrack=host, backtrack=device and device with n_best = beam (same weights, workspace and
                                                          captured token steps; ROUNDS rounds after 3 warm-up calls of each), plus the event time
                                                          around vlp_beam_nbest alone -> profiles/beam_nbest.json
+    --beam_groups G[,G..] [--diversity_penalty L] [--beam_size K]
+                                                         instead of the modes: diverse beam search (BertForSeq2SeqDecoder(beam_groups=G,
+                                                         diversity_penalty=L); default L 0.5, K 6) against the plain search, as ONE model whose
+                                                         calls alternate between G = 1 and every G given (ROUNDS rounds after 3 warm-up calls of
+                                                         each), plus the event time of one vlp_beam_select_groups launch against one
+                                                         vlp_beam_select launch at K = 6 and K = 64 -> profiles/diverse_beam.json
 """
+import argparse
 import json
 import os
 import sys
 import time
 
 import torch
+
+# the command line is read before anything touches a device (--help needs none); the older modes are chosen by the environment variables above
+_p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+_p.add_argument("--beam_groups", default=None, help="comma-separated group counts of the diverse A/B, each dividing --beam_size")
+_p.add_argument("--diversity_penalty", type=float, default=0.5)
+_p.add_argument("--beam_size", type=int, default=6)
+_a = _p.parse_args()
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from vlp_amd import synthetic as S  # noqa: E402
@@ -92,8 +106,70 @@ def backtrack_ab():
     print(json.dumps(res))
 
 
+def diverse_ab(Kb, group_list, lam):
+    """Plain against diverse beam search inside one process, alternating calls of one model; every call ends in a synchronise."""
+    import statistics
+    from vlp_amd import _lib as K
+    rounds = int(os.environ.get("ROUNDS", 12))
+    res = {"batch": B, "new_tokens": T, "layers": 12, "beam": Kb, "diversity_penalty": lam, "rounds": rounds, "warmup_calls_per_config": 3,
+           "timing": "host clock around one beam_search call, synchronised before and after; the configurations alternate inside every round"}
+    m = BertForSeq2SeqDecoder(cfg, mask_word_id=S.MASK_ID, eos_id=S.SEP_ID, enable_butd=True, len_vis_input=Nv, allow_random_fc7=True,
+                              search_beam_size=Kb).half().to(dev).eval()
+    configs = [("groups_1", 1, 0.0)] + [("groups_%d" % G, G, lam) for G in group_list]
+    times, distinct = {c[0]: [] for c in configs}, {}
+
+    def call(name, G, L):
+        m.beam_groups, m.diversity_penalty = G, L
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = m(img, vis_pe, input_ids, token_type, pos, am)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        distinct[name] = round(float(sum(len(set(row)) for row in r["wids"][:, T - 1].tolist())) / B, 2)
+        return dt
+    for _ in range(3):
+        for c in configs:
+            call(*c)
+    for _ in range(rounds):
+        for c in configs:
+            times[c[0]].append(call(*c))
+    for name, ts in times.items():
+        res[name] = {"ms_per_batch_median": round(statistics.median(ts), 3), "min": round(min(ts), 3), "max": round(max(ts), 3),
+                     "stdev": round(statistics.stdev(ts), 3), "distinct_words_in_last_frame_per_image": distinct[name]}
+    del m
+    torch.cuda.empty_cache()
+    # one launch alone: device events around the selection of a later frame (launch overhead included), the two entries alternating
+    res["launch_timing"] = "device events around one launch of a later frame, B = %d; 40 alternating launches of each after 10 warm-up" % B
+    for Ks, G in ((6, 3), (64, 4)):
+        gen = torch.Generator().manual_seed(Ks)
+        kk_s = torch.randn(B, Ks, Ks, generator=gen).sort(dim=-1, descending=True)[0].to(dev)
+        kk_i = torch.randint(0, 28996, (B, Ks, Ks), generator=gen).to(dev)
+        lt, le = torch.randn(B, Ks, generator=gen).to(dev), torch.zeros(B, Ks, device=dev)
+        o = [torch.empty(B, Ks, device=dev, dtype=dt) for dt in (torch.float32, torch.long, torch.long, torch.float32)]
+        src, nxt = torch.empty(B * Ks, device=dev, dtype=torch.long), torch.empty(B * Ks, 2, device=dev, dtype=torch.long)
+        ev = {"vlp_beam_select": [], "vlp_beam_select_groups": []}
+        for i in range(50):
+            for name in ev:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                if name == "vlp_beam_select":
+                    K.beam_select(kk_s, kk_i, lt, le, o[0], o[1], o[2], o[3], src, nxt[:, 0], B, Ks, False, S.SEP_ID)
+                else:
+                    K.beam_select_groups(kk_s, kk_i, lt, le, o[0], o[1], o[2], o[3], src, nxt[:, 0], B, Ks, False, S.SEP_ID, G, lam)
+                b.record()
+                torch.cuda.synchronize()
+                if i >= 10:
+                    ev[name].append(a.elapsed_time(b) * 1e3)
+        res["launch_K%d" % Ks] = dict({name + "_event_us": {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+                                       for name, v in ev.items()}, groups=G)
+    print(json.dumps(res))
+
+
 if os.environ.get("BACKTRACK_AB") == "1":
     backtrack_ab()
+    sys.exit(0)
+if _a.beam_groups:
+    diverse_ab(_a.beam_size, [int(v) for v in _a.beam_groups.split(",")], _a.diversity_penalty)
     sys.exit(0)
 MODES = [m for m in (("greedy", dict(search_beam_size=1)), ("beam3", dict(search_beam_size=3)), ("beam5", dict(search_beam_size=5)),
                      ("beam3_ngram", dict(search_beam_size=3, **NGRAM)), ("beam5_ngram", dict(search_beam_size=5, **NGRAM)))

@@ -237,6 +237,7 @@ SYMBOLS = {
     "vlp_argmax_rows2": (C.c_int, [vp, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp]),
     "vlp_logsoftmax_topk": (C.c_int, [vp, i64, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "vlp_beam_select": (C.c_int, [C.POINTER(BeamSelectArgs), vp]),
+    "vlp_beam_select_groups": (C.c_int, [C.POINTER(BeamSelectArgs), i32, C.c_float, vp]),
     "vlp_ngram_candidates": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp]),
     "vlp_logsoftmax_topk_list": (C.c_int, [vp, i64, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     "vlp_kv_gather": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]),
@@ -621,6 +622,15 @@ def beam_select(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, ou
     a = BeamSelectArgs(ptr(kk_scores), ptr(kk_ids), ptr(last_total), ptr(last_eos), ptr(out_scores), ptr(out_ids), ptr(out_ptrs), ptr(out_eos),
                        ptr(src_rows), ptr(next_ids), next_ids.stride(0), B, K, 1 if first else 0, eos_id)
     _check(load().vlp_beam_select(C.byref(a), stream_ptr()))
+
+
+def beam_select_groups(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, out_ptrs, out_eos, src_rows, next_ids, B, K, first, eos_id,
+                       groups, penalty):
+    """beam_select with the K beams in `groups` groups and a penalty per earlier pick of the same word (vlp_amd.diverse is the rule)."""
+    _req_cuda(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, out_ptrs, out_eos, src_rows, next_ids)
+    a = BeamSelectArgs(ptr(kk_scores), ptr(kk_ids), ptr(last_total), ptr(last_eos), ptr(out_scores), ptr(out_ids), ptr(out_ptrs), ptr(out_eos),
+                       ptr(src_rows), ptr(next_ids), next_ids.stride(0) if next_ids is not None else 0, B, K, 1 if first else 0, eos_id)
+    _check(load().vlp_beam_select_groups(C.byref(a), int(groups), float(penalty), stream_ptr()))
 
 
 def kv_gather(src, src_rows, dst, dst_rows, idx, R, lo, hi, row_elems):

@@ -1111,6 +1111,91 @@ extern "C" int vlp_beam_select(const vlp_beam_select_args* a, void* stream) {
     return VLP_OK;
 }
 
+// Diverse (group) beam search: beam_select_kernel's step with the K beams split into G groups of Kg = K / G (the rule: vlp_amd/diverse.py).  One
+// wave per sample, the groups one after another inside it.  Group g sees the continuations of its own rows (index i = r*K + j as above; the
+// single row in the first step) with the key v0 - fl32(penalty * c), c = how many picks of the groups < g of this step carry the candidate's
+// word; those picks (<= 64 ids) sit in LDS.  The keys of a group are formed once (<= 64 * 64 floats in LDS), then each of the Kg picks is the
+// maximum among the candidates after the previous pick in the (key descending, index ascending) order: the scan of beam_select_kernel strided
+// over the lanes and finished by a wave reduction, as beam_nbest_kernel ranks -- nothing is sorted.  Lane n keeps pick n and writes its slot.
+// The product is rounded before the subtraction: beam_group_key pins the rounded product in a register with an empty asm statement, so the
+// subtraction cannot be fused with it.  (The build contracts a * b + c in the back end; HIP's __fmul_rn / __fsub_rn are plain operators there
+// and `#pragma clang fp contract(off)` does not stop it: both still gave one v_fma_f32.)  A NaN key orders as -inf, so with ncand >= Kg every
+// pick finds a candidate and bi stays inside [0, ncand).  The outputs carry v0, the unpenalised score.
+__device__ __forceinline__ float beam_group_key(float v0, float penalty, int cnt) {
+    float pen = penalty * (float)cnt;
+    asm volatile("" : "+v"(pen));
+    return v0 - pen;
+}
+__device__ __forceinline__ float beam_group_value(const vlp_beam_select_args& a, int b, int K, int i) {
+    if (a.first) return a.kk_scores[(int64_t)b * K + i];
+    const int src = i / K;
+    return a.kk_scores[((int64_t)b * K + src) * K + (i % K)] + a.last_eos[(int64_t)b * K + src] * -10000.0f + a.last_total[(int64_t)b * K + src];
+}
+__global__ __launch_bounds__(64) void beam_select_groups_kernel(vlp_beam_select_args a, int G, float penalty) {
+    __shared__ float keys[64 * 64];
+    __shared__ int64_t picked[64];
+    const int b = blockIdx.x, lane = threadIdx.x, K = a.K, Kg = K / G;
+    const int ncand = a.first ? K : Kg * K;
+    for (int g = 0; g < G; ++g) {
+        const int base = a.first ? 0 : g * Kg * K, npicked = g * Kg;
+        for (int c = lane; c < ncand; c += 64) {
+            const int i = base + c;
+            const int64_t id = a.first ? a.kk_ids[(int64_t)b * K + i] : a.kk_ids[((int64_t)b * K + i / K) * K + (i % K)];
+            int cnt = 0;
+            for (int p = 0; p < npicked; ++p) cnt += picked[p] == id ? 1 : 0;
+            const float key = beam_group_key(beam_group_value(a, b, K, i), penalty, cnt);
+            keys[c] = key != key ? -INFINITY : key;
+        }
+        __syncthreads();
+        float pv = INFINITY;
+        int pi = -1, my_c = 0;
+        for (int n = 0; n < Kg; ++n) {
+            float best = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int c = lane; c < ncand; c += 64) {
+                const float val = keys[c];
+                const bool after = (val < pv) || (val == pv && c > pi);
+                if (after && (val > best || (val == best && c < bi))) { best = val; bi = c; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(best, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+            }
+            pv = best;
+            pi = bi;
+            if (lane == n) my_c = bi;
+        }
+        if (lane < Kg) {
+            const int i = base + (my_c < ncand ? my_c : 0);
+            const int ptr = a.first ? 0 : i / K;
+            const int64_t id = a.first ? a.kk_ids[(int64_t)b * K + i] : a.kk_ids[((int64_t)b * K + ptr) * K + (i % K)];
+            const int64_t o = (int64_t)b * K + npicked + lane;
+            a.out_scores[o] = beam_group_value(a, b, K, i);
+            a.out_ids[o] = id;
+            a.out_ptrs[o] = ptr;
+            a.out_eos[o] = id == a.eos_id ? 1.0f : 0.0f;
+            a.src_rows[o] = a.first ? (int64_t)b : (int64_t)b * K + ptr;
+            a.next_ids[o * a.next_ids_stride] = id;
+            picked[npicked + lane] = id;
+        }
+        __syncthreads();
+    }
+}
+extern "C" int vlp_beam_select_groups(const vlp_beam_select_args* a, int32_t groups, float penalty, void* stream) {
+    VLP_CHECK_ARG(a && a->kk_scores && a->kk_ids && a->out_scores && a->out_ids && a->out_ptrs && a->out_eos && a->src_rows && a->next_ids,
+                  "vlp_beam_select_groups: null operand");
+    VLP_CHECK_ARG(a->B > 0 && a->K >= 1 && a->K <= 64 && groups >= 1 && a->K % groups == 0,
+                  "vlp_beam_select_groups: needs B > 0, 1 <= K <= 64, groups >= 1 and K %% groups == 0 (got B=%d K=%d groups=%d)", a->B, a->K, groups);
+    VLP_CHECK_ARG(penalty >= 0.0f && penalty < INFINITY, "vlp_beam_select_groups: the penalty must be finite and >= 0 (got %g)", (double)penalty);
+    VLP_CHECK_ARG(a->first || (a->last_total && a->last_eos), "vlp_beam_select_groups: a later step needs last_total and last_eos");
+    VLP_ENTER(a->kk_scores, "vlp_beam_select_groups");
+    hipLaunchKernelGGL(beam_select_groups_kernel, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a, groups, penalty);
+    VLP_CHECK_LAUNCH("vlp_beam_select_groups");
+    return VLP_OK;
+}
+
 // The N best finished hypotheses of a search, ranked and back-tracked on the device (:1446-1474 for every rank, not only the best).  One wave
 // per sample.  last = the first frame whose K words are all eos, else F - 1; candidate i = f*K + k (f <= last) exists when its word is eos or
 // f == last; its value is (double)tot + length_penalty * (f + 1).  Rank n is the maximum among the candidates that come after rank n - 1 in

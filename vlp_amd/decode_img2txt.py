@@ -24,6 +24,10 @@ A short last batch is filled up with its last image (and the extra rows dropped)
       applied to the hypotheses of the beam instead of samples: none writes rank 0; logprob the hypothesis with the largest logprob; consensus
       (2 <= N <= 16) the one with the largest CIDEr-D against the image's other hypotheses, scored on the device.  With a selection
       --output_file receives {"image_id", "caption", "rank", "logprob", "utility"} per image, which python -m vlp_amd.eval_captions reads as it stands.
+  --beam_groups G (1..--beam_size, dividing it; default 1: the tool as above, byte for byte) with --diversity_penalty L (finite, >= 0) runs a
+      diverse beam search (vlp_amd.diverse; vlp_beam_select_groups on the device): the beams in G groups, a word penalised by L for every
+      earlier group that chose it in the same step.  logprob / value stay unpenalised, so --n_best, --nbest_file and --select work on the
+      diverse beam unchanged -- and have hypotheses that differ to choose from.
 """
 import argparse
 import glob
@@ -81,8 +85,20 @@ def parse_args(argv=None):
                    help="keep the N best finished hypotheses of every image's beam search, 1..--beam_size (default 1: the best one only)")
     p.add_argument("--nbest_file", default=None, metavar="PATH",
                    help="with --n_best >= 2: write every hypothesis here as {image_id, rank, caption, logprob, value} (--samples_file is an alias)")
+    p.add_argument("--beam_groups", type=int, default=1, metavar="G",
+                   help="diverse beam search: split the --beam_size beams into G groups, 1..--beam_size and dividing it (default 1: the plain search)")
+    p.add_argument("--diversity_penalty", type=float, default=0.0, metavar="L",
+                   help="with --beam_groups >= 2: subtract L from a word's score for every earlier group that chose it in the same step (default 0)")
     add_selection_flags(p)
     a = p.parse_args(argv)
+    if not (1 <= a.beam_groups <= max(a.beam_size, 1)):
+        p.error("--beam_groups must be in 1..--beam_size = 1..%d (got %d)" % (max(a.beam_size, 1), a.beam_groups))
+    if a.beam_size % a.beam_groups != 0:
+        p.error("--beam_groups %d must divide --beam_size %d: the groups have equal size" % (a.beam_groups, a.beam_size))
+    if not (a.diversity_penalty == a.diversity_penalty and 0.0 <= a.diversity_penalty < float("inf")):
+        p.error("--diversity_penalty must be finite and >= 0 (got %r)" % (a.diversity_penalty,))
+    if a.diversity_penalty != 0.0 and a.beam_groups == 1:
+        p.error("--diversity_penalty %r penalises the words of earlier groups: it needs --beam_groups >= 2" % (a.diversity_penalty,))
     if a.n_best > 1 and a.beam_size < 2:
         p.error("--n_best %d lists the hypotheses of a beam search: it needs --beam_size >= 2 (got %d)" % (a.n_best, a.beam_size))
     if not (1 <= a.n_best <= max(a.beam_size, 1)):
@@ -230,7 +246,8 @@ def build_decoder(args, vocab, state, device):
     model = BertForSeq2SeqDecoder(config, mask_word_id=mask_id, num_labels=2, search_beam_size=args.beam_size, length_penalty=args.length_penalty,
                                   eos_id=sep_id, forbid_duplicate_ngrams=args.forbid_duplicate_ngrams,
                                   forbid_ignore_set=forbid_ignore_set(args.forbid_ignore_word, vocab), ngram_size=args.ngram_size, min_len=args.min_len,
-                                  enable_butd=args.enable_butd, len_vis_input=args.len_vis_input, n_best=getattr(args, "n_best", 1))
+                                  enable_butd=args.enable_butd, len_vis_input=args.len_vis_input, n_best=getattr(args, "n_best", 1),
+                                  beam_groups=getattr(args, "beam_groups", 1), diversity_penalty=getattr(args, "diversity_penalty", 0.0))
     load_checkpoint_state(model, state)
     model.half()
     model.to(device)

@@ -1292,7 +1292,7 @@ class Engine(object):
     NGRAM_MAX_FRAMES = 256       # csrc/elementwise.hip: NGRAM_MAX_FRAMES frames per hypothesis (and <= TOPK_LIST_MAX = 1024 ids per list)
 
     def decode_beam(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, beam_size, eos_id,
-                    min_len=0, forbid_fn=None, ngram=None):
+                    min_len=0, forbid_fn=None, ngram=None, groups=1, diversity=0.0, group_select="device"):
         """Beam search frames (modeling.py:1255-1430) on the K/V-cache decoder.  The first step runs B sequences; its cache rows are
         replicated to the B*K beams (first_expand), afterwards every step decodes B*K sequences and the caches follow the back
         pointers (select_beam_items) -- only the generated positions; the prefix is identical for all beams of a sample and is kept,
@@ -1302,13 +1302,28 @@ class Engine(object):
         `ngram=(n, ignore_ids)` (n >= 2; ignore_ids: token ids or None) is the same blocking on the device: after frame s vlp_ngram_candidates
         lists every hypothesis's forbidden words from the resident frames, step s+1 selects with vlp_logsoftmax_topk_list; nothing goes to
         the host before the frames are returned and the token steps are captured / replayed like those of an unblocked search.
+        `groups=G > 1` (G divides K) with `diversity=lambda >= 0` is a diverse (group) beam search (vlp_amd.diverse is the rule; not in the
+        reference): every frame selects with vlp_beam_select_groups where vlp_beam_select stands otherwise -- one launch for one launch, so the
+        steps are captured / replayed as well, lambda baked into the captured launch and (G, lambda) part of the plan key.  The frames keep the
+        unpenalised scores; back pointers stay inside their group.  groups=1 is the search as it is and refuses a diversity.
+        `group_select="host"` is the A/B and fallback path of G > 1: every frame copies the top-K lists and the last frame's totals / eos flags
+        to the host, runs diverse.beam_select_groups_host and uploads the frame; those steps are run, not planned.
         Returns (total_scores, step_ids, back_ptrs) as [frames, B, K] tensors on the device."""
+        Kb = int(beam_size)
+        G, lam = int(groups), float(diversity)
+        if group_select not in ("device", "host"):
+            raise ValueError("group_select must be 'device' or 'host', got %r" % (group_select,))
+        if G == 1:
+            if lam != 0.0:
+                raise ValueError("vlp_amd: diversity=%r needs groups > 1 (groups=1 is the plain beam search)" % (diversity,))
+        else:
+            from .diverse import check_limits as check_groups
+            check_groups(Kb, G, lam)
         self.pack()
         self.wait_params()
         model = self._model()
         cfg = model.config
         H, NL, V = cfg.hidden_size, cfg.num_hidden_layers, cfg.vocab_size
-        Kb = int(beam_size)
         B, in_len, out_len = self._decode_check(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask)
         if Kb < 2 or Kb > 64:
             raise RuntimeError("vlp_amd: beam size must be in [2, 64]")
@@ -1344,6 +1359,17 @@ class Engine(object):
                 if ng_ignore is None:
                     ng_ignore = ws["ngram_ignore"][ign] = torch.tensor(ign, device=dev, dtype=torch.long)
             plan_tag = ("ngram", ng_n, ign)
+        if G > 1:
+            plan_tag += ("groups", G, lam)
+
+        def select_on_host(s, first):
+            from .diverse import beam_select_groups_host
+            kk_s, kk_i = (ws["kk_s"][:B], ws["kk_i"][:B]) if first else (ws["kk_s"].view(B, Kb, Kb), ws["kk_i"].view(B, Kb, Kb))
+            o_tot, o_ids, o_ptr, o_eos, o_src, _ = beam_select_groups_host(kk_s, kk_i, None if first else tot[s - 1], None if first else eos[s - 1],
+                                                                           first, int(eos_id), G, lam)
+            for dst, src in ((tot[s], o_tot), (wids[s], o_ids), (ptrs[s], o_ptr), (eos[s], o_eos), (ws["src_rows"], o_src),
+                             (ws["xids"][:, 0], o_ids.reshape(-1))):
+                dst.copy_(torch.from_numpy(src))
 
         def frame(s, rows, first, forbid, block_eos):
             if ngram is not None and not first:
@@ -1351,8 +1377,14 @@ class Engine(object):
                                        block_eos=block_eos)
             else:
                 K.logsoftmax_topk(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], forbid=forbid, eos_id=int(eos_id), block_eos=block_eos)
-            K.beam_select(ws["kk_s"], ws["kk_i"], None if first else tot[s - 1], None if first else eos[s - 1], tot[s], wids[s], ptrs[s], eos[s],
-                          ws["src_rows"], ws["xids"][:, 0], B, Kb, first, int(eos_id))
+            if G == 1:
+                K.beam_select(ws["kk_s"], ws["kk_i"], None if first else tot[s - 1], None if first else eos[s - 1], tot[s], wids[s], ptrs[s], eos[s],
+                              ws["src_rows"], ws["xids"][:, 0], B, Kb, first, int(eos_id))
+            elif group_select == "device":
+                K.beam_select_groups(ws["kk_s"], ws["kk_i"], None if first else tot[s - 1], None if first else eos[s - 1], tot[s], wids[s], ptrs[s],
+                                     eos[s], ws["src_rows"], ws["xids"][:, 0], B, Kb, first, int(eos_id), G, lam)
+            else:
+                select_on_host(s, first)
             if ngram is not None and s + 1 < n_steps:        # the next step's forbidden words (frame 0: s + 1 < n, every count becomes 0)
                 K.ngram_candidates(wids, ptrs, B, Kb, s, ng_n, ws["cand_ids"], ws["cand_cnt"], ignore_ids=ng_ignore)
 
@@ -1381,6 +1413,8 @@ class Engine(object):
                 step()                   # the forbid mask is a fresh tensor every step: not plannable
                 fm = forbid_fn(wids[s].tolist(), ptrs[s].tolist(), False)
                 forbid = None if fm is None else torch.from_numpy(fm).to(dev)
+            elif G > 1 and group_select == "host":
+                step()                   # the selection runs on the host every step: not plannable
             else:
                 self._run_planned(ws, ("beam", s, int(eos_id), block_eos) + plan_tag, step)
         ws["calls"] += 1

@@ -619,10 +619,13 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     # where beam_search turns the frames into hypotheses: "host" = _backtrack_batch (numpy, one device -> host copy of the frames, the best
     # hypothesis only); "device" = Engine.beam_nbest (vlp_beam_nbest: ranked n-best list, no copy).  n_best > 1 always takes the device.
     backtrack = "host"
+    # beam_groups > 1 (diverse beam search): "device" = vlp_beam_select_groups in every frame, steps captured / replayed; "host" =
+    # vlp_amd.diverse.beam_select_groups_host with a round trip per frame (A/B and fallback).  Same results.
+    group_select = "device"
 
     def __init__(self, config, mask_word_id=0, num_labels=2, search_beam_size=1, length_penalty=1.0, eos_id=0,
                  forbid_duplicate_ngrams=False, forbid_ignore_set=None, ngram_size=3, min_len=0, enable_butd=False, len_vis_input=49,
-                 allow_random_fc7=True, n_best=1):
+                 allow_random_fc7=True, n_best=1, beam_groups=1, diversity_penalty=0.0):
         super(BertForSeq2SeqDecoder, self).__init__(config)
         self.bert = BertModelIncr(config)
         self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight, num_labels=num_labels)
@@ -633,6 +636,8 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         self.n_best = int(n_best)
         if self.n_best < 1 or self.n_best > max(int(search_beam_size), 1):
             raise ValueError("n_best=%d: the n-best list of a beam search holds 1..search_beam_size (%d) hypotheses" % (self.n_best, search_beam_size))
+        self.beam_groups, self.diversity_penalty = int(beam_groups), float(diversity_penalty)
+        self._check_groups(int(search_beam_size))
         _region_embedders(self, config, enable_butd, allow_random_fc7)
         self.__dict__["_engine"] = Engine(self)
         for prm in self.parameters():
@@ -641,6 +646,17 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     @property
     def engine(self):
         return self.__dict__["_engine"]
+
+    def _check_groups(self, K):
+        """beam_groups = G / diversity_penalty = lambda of a diverse beam search (vlp_amd.diverse): G = 1 with lambda = 0 is the plain search of
+        any beam size; G > 1 needs a beam search whose size G divides, and a finite lambda >= 0."""
+        G, lam = self.beam_groups, self.diversity_penalty
+        ok = lam == lam and 0.0 <= lam < float("inf") and G >= 1
+        if ok and G == 1 and lam == 0.0:
+            return
+        if not ok or G == 1 or K < 2 or G > K or K % G != 0:
+            raise ValueError("beam_groups=%d, diversity_penalty=%r: a diverse beam search needs search_beam_size (%d) >= 2, beam_groups in "
+                             "1..search_beam_size and dividing it, and a finite diversity_penalty >= 0 that is 0 unless beam_groups >= 2" % (G, lam, K))
 
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy",
                 n_samples=1, temperature=1.0, top_k=0, top_p=1.0, return_entropy=False):
@@ -818,13 +834,18 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         With n_best = N > 1 or backtrack = "device" the hypotheses come from vlp_beam_nbest (Engine.beam_nbest; the rule is
         vlp_amd.nbest.beam_nbest_host's, rank 0 the hypothesis of the host path) and nothing is copied to the host; the dict then also carries
         the ranked list of every image: 'nbest_seq' [B, N, L], 'nbest_score' f32 (cumulative log-probability) / 'nbest_value' f64 (score +
-        length_penalty * length) / 'nbest_len' int32 / 'nbest_ok' uint8 [B, N] (0: a hypothesis that went on after its eos, or an empty one)."""
+        length_penalty * length) / 'nbest_len' int32 / 'nbest_ok' uint8 [B, N] (0: a hypothesis that went on after its eos, or an empty one).
+        With beam_groups = G > 1 the frames are those of a diverse beam search (vlp_amd.diverse: G groups of K / G beams, diversity_penalty per
+        earlier pick of the same word in a frame); the scores stay unpenalised log-probabilities, so everything above keeps its meaning."""
         B, out_len = input_ids.shape[0], token_type_ids.shape[1]
         K = self.search_beam_size
         if self.backtrack not in ("device", "host"):
             raise ValueError("backtrack must be 'device' or 'host', got %r" % (self.backtrack,))
         if not 1 <= self.n_best <= K:
             raise ValueError("n_best=%d: the n-best list of a beam search holds 1..search_beam_size (%d) hypotheses" % (self.n_best, K))
+        self._check_groups(K)
+        if self.group_select not in ("device", "host"):
+            raise ValueError("group_select must be 'device' or 'host', got %r" % (self.group_select,))
         forbid_fn = ngram = None
         if self.forbid_duplicate_ngrams:
             if self.ngram_blocking not in ("device", "host"):
@@ -834,7 +855,9 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             else:                    # ngram_size == 1 (the reference's seq[-0:] quirk) stays on the host
                 forbid_fn = self._ngram_blocker(B, self.config.vocab_size)
         tot, wids, ptrs = self.engine.decode_beam(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
-                                                  K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn, ngram=ngram)
+                                                  K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn, ngram=ngram,
+                                                  **(dict(groups=self.beam_groups, diversity=self.diversity_penalty, group_select=self.group_select)
+                                                     if self.beam_groups > 1 else {}))
         frames = tot.shape[0]
         dev = input_ids.device
         # frames stay on the device: [frames, B, K] -> [B, out_len, K], zero padded (three small launches; no per-sample host loop)
