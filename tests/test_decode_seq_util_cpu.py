@@ -27,6 +27,53 @@ def test_sample_major_permutes_and_owns_its_memory_for_every_k():
     assert src[:, :n].view(B, 1, n).transpose(0, 1).reshape(B, n).data_ptr() == src.data_ptr()
 
 
+def test_decoder_names_resolve_on_the_engine():
+    """The decoders are a base class of Engine (vlp_amd/decoder.py); what tests, tools and modeling.py use stays on Engine, and a switch
+    assigned on Engine is the one the decoders read."""
+    import vlp_amd.engine as E
+    from vlp_amd.decoder import Decoder
+    assert issubclass(E.Engine, Decoder) and E.sample_major is sample_major
+    for name in ("decode_greedy", "decode_sample_group", "decode_beam", "beam_nbest", "_run_planned", "_decode_static_inputs", "score_samples"):
+        assert callable(getattr(E.Engine, name)), name
+    assert E.Engine.DEC_SPLITS == 4 and E.Engine.NGRAM_MAX_FRAMES == 256
+    assert isinstance(E.Engine.DECODE_FUSED, bool) and isinstance(E.Engine.DECODE_GRAPHS, bool)
+
+
+def test_decode_steps_runs_or_plans_every_step_once():
+    """The token-step loop with the model step and the planner replaced by recorders: step 0 and its selection are run; a step whose
+    plan_key is None is run, any other goes to _run_planned under that key; the host hook follows every step; the workspace counts
+    the call once, at the end."""
+    from vlp_amd.decoder import Decoder, _Call
+
+    class Rec(Decoder):
+        def __init__(self):
+            self.log = []
+
+        def _decode_model_step(self, ws, caches, Lcap, xids, tt, pid, mask_view, R, T, st, first, prefix=None):
+            self.log.append(("model", caches, R, T, st, first, prefix, tuple(mask_view.shape), ws["calls"]))
+
+        def _run_planned(self, ws, key, fn):
+            self.log.append(("planned", key))
+            fn()
+
+    B, Kb, in_len, n = 2, 3, 5, 4
+    out_len = in_len + n
+    ws = dict(kv="kv", xids=None, tt_steps=[None] * out_len, pid_steps=[None] * out_len, calls=0)
+    ids = torch.zeros(B, out_len, dtype=torch.long)
+    call = _Call(ws, B, B * Kb, in_len, out_len, n, in_len + 1, 11, torch.zeros(B * Kb, out_len, out_len), ids, ids, torch.zeros(B, out_len, out_len),
+                 None)
+    d = Rec()
+    d._decode_steps(call, lambda s, first: d.log.append(("select", s, first)), lambda s: "cache%d" % (s & 1), "prefix",
+                    lambda s: None if s == 2 else ("kind", s), between=lambda s: d.log.append(("between", s)))
+    assert d.log == [("model", "kv", B, in_len + 1, 0, True, None, (B, in_len + 1, in_len + 1), 0), ("select", 0, True), ("between", 0),
+                     ("planned", ("kind", 1)), ("model", "cache1", B * Kb, 2, in_len, False, "prefix", (B * Kb, 2, in_len + 2), 0),
+                     ("select", 1, False), ("between", 1),
+                     ("model", "cache0", B * Kb, 2, in_len + 1, False, "prefix", (B * Kb, 2, in_len + 3), 0), ("select", 2, False), ("between", 2),
+                     ("planned", ("kind", 3)), ("model", "cache1", B * Kb, 2, in_len + 2, False, "prefix", (B * Kb, 2, in_len + 4), 0),
+                     ("select", 3, False), ("between", 3)]
+    assert ws["calls"] == 1
+
+
 def test_varied_inputs_vary_every_per_call_input():
     a, b = varied_inputs(3, 6, 101), varied_inputs(3, 6, 102)
     plain = decode_inputs(3, 6, 101)

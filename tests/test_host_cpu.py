@@ -241,6 +241,32 @@ def test_header_is_plain_c_and_the_c_consumer_compiles():
     assert r.returncode == 0, r.stderr
 
 
+def _backtrack(self, scores, words, back):
+    """The per-sample rule _backtrack_batch is checked against.  One sample's frames (lists [frames][K]) -> best hypothesis
+    (:1446-1474): candidates are the hypotheses that emitted eos, or any hypothesis of the last valid frame (the first frame whose words
+    are all eos, else the final one); rank by cumulative log-probability + length_penalty * length; follow the back pointers."""
+    import math
+    eos, lp = self.eos_id, self.length_penalty
+    last = next((i for i, w in enumerate(words) if all(x == eos for x in w)), len(scores) - 1)
+    best = None
+    for f in range(last + 1):
+        for k, w in enumerate(words[f]):
+            if w == eos or f == last:
+                val = scores[f][k] + lp * (f + 1)
+                if best is None or val > best[0]:
+                    best = (val, f, k)
+    if best is None or best[0] == -math.inf:
+        return [0]
+    _, f, k = best
+    out = [words[f][k]]
+    while f > 0:
+        k = back[f][k]
+        f -= 1
+        out.append(words[f][k])
+    out.reverse()
+    return out
+
+
 def test_beam_backtrack_batch_equals_the_per_sample_rule():
     """BertForSeq2SeqDecoder.beam_search picks every sample's best hypothesis on the host in ONE vectorised pass (round 6: the per-sample Python loop with
     its tensor constructions caused 30 - 110 ms stalls at 320 hypotheses); it must follow the reference's rule (modeling.py:1446-1474) exactly as the
@@ -264,8 +290,7 @@ def test_beam_backtrack_batch_equals_the_per_sample_rule():
             sc[:] = -np.inf                            # nothing finite: the reference returns [0]
         out = BertForSeq2SeqDecoder._backtrack_batch(d, sc, ww, pp, F + 2)
         for b in range(B):
-            seq = BertForSeq2SeqDecoder._backtrack(d, [sc[f, b].tolist() for f in range(F)], [ww[f, b].tolist() for f in range(F)],
-                                                   [pp[f, b].tolist() for f in range(F)])
+            seq = _backtrack(d, [sc[f, b].tolist() for f in range(F)], [ww[f, b].tolist() for f in range(F)], [pp[f, b].tolist() for f in range(F)])
             exp = np.zeros(F + 2, dtype=np.int64)
             exp[:len(seq)] = seq
             assert np.array_equal(out[b], exp), (trial, b, out[b], exp)

@@ -713,18 +713,12 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             if self.search_beam_size > 1:
                 raise ValueError("n_samples=%d with search_beam_size=%d: several samples per image are drawn, not searched" %
                                  (n_samples, self.search_beam_size))
-            eng = self.engine
+            if self.training and torch.is_grad_enabled():
+                return self._sample_scored(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, n_samples, 1.0, False,
+                                           group=True)
             with torch.no_grad():
-                ids, logp = eng.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
-                                                    n_samples)
-            if not (self.training and torch.is_grad_enabled()):
-                return ids, logp
-
-            def tiled(t):                    # row k*B + b of the scoring batch is image b
-                return t.repeat(n_samples, *([1] * (t.dim() - 1)))
-            st, logp = eng.score_samples(tiled(vis_feats), tiled(vis_pe), tiled(input_ids), tiled(token_type_ids), tiled(position_ids),
-                                         tiled(attention_mask), ids, self.mask_word_id)
-            return ids, _LogprobFn.apply(eng._anchor, logp, eng, st)
+                return self.engine.decode_sample_group(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask,
+                                                       self.mask_word_id, n_samples)
         if self.search_beam_size > 1:
             with torch.no_grad():
                 return self.beam_search(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=task_idx)
@@ -733,17 +727,13 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         if sample_mode == "sample" and self.training and torch.is_grad_enabled():
             # SCST (run_img2txt_dist.py:505-507): draw on the K/V-cache decoder, then score the drawn ids with one training forward whose
             # [MASK] slots see exactly the decoder's hidden states; the log-probs' backward is that forward's backward
-            eng = self.engine
-            with torch.no_grad():
-                ids, _ = eng.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id, sample=True)
-            st, logp = eng.score_samples(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, ids, self.mask_word_id)
-            return ids, _LogprobFn.apply(eng._anchor, logp, eng, st)
+            return self._sample_scored(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, 1, 1.0, False, group=False)
         with torch.no_grad():
             return self.engine.decode_greedy(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
                                              sample=(sample_mode == "sample"))
 
     def _sample_scored(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, n_samples, temperature, entropy, group):
-        """SCST with a tempered policy and / or the entropy output: draw n_samples captions per image from softmax(logits / temperature)
+        """SCST, every form of it (temperature 1 and entropy False: the plain one): draw n_samples captions per image from softmax(logits / temperature)
         (group: Engine.decode_sample_group, the captured path; else decode_greedy(sample=True), the draw of a plain one-sample call), then
         score them under the same policy.  Returns (ids, logp) or (ids, logp, entropy), the last two differentiable."""
         eng = self.engine
@@ -804,30 +794,6 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             return mask
         return step
 
-    def _backtrack(self, scores, words, back):
-        """One sample's frames (lists [frames][K]) -> best hypothesis (:1446-1474): candidates are the hypotheses that emitted eos, or
-        any hypothesis of the last valid frame (the first frame whose words are all eos, else the final one); rank by cumulative
-        log-probability + length_penalty * length; follow the back pointers."""
-        eos, lp = self.eos_id, self.length_penalty
-        last = next((i for i, w in enumerate(words) if all(x == eos for x in w)), len(scores) - 1)
-        best = None
-        for f in range(last + 1):
-            for k, w in enumerate(words[f]):
-                if w == eos or f == last:
-                    val = scores[f][k] + lp * (f + 1)
-                    if best is None or val > best[0]:
-                        best = (val, f, k)
-        if best is None or best[0] == -math.inf:
-            return [0]
-        _, f, k = best
-        out = [words[f][k]]
-        while f > 0:
-            k = back[f][k]
-            f -= 1
-            out.append(words[f][k])
-        out.reverse()
-        return out
-
     def beam_search(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None):
         """Returns the reference's traces dict (:1436-1494): 'pred_seq' [B, L] (0 padded), 'scores' f32 / 'wids' / 'ptrs' [B, L, K]
         (frames padded with zeros to the output length L), on the input device.
@@ -880,7 +846,7 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         return {"pred_seq": torch.from_numpy(pred).to(dev), "scores": scores, "wids": wid_o, "ptrs": ptr_o}
 
     def _backtrack_batch(self, scores, words, back, out_len):
-        """_backtrack for all samples at once (numpy; arrays [frames, B, K]) -> int64 [B, out_len], 0 padded.  Same rules: candidates are the
+        """The best hypothesis (:1446-1474) of all samples at once (numpy; arrays [frames, B, K]) -> int64 [B, out_len], 0 padded: candidates are the
         hypotheses that emitted eos, or any hypothesis of the last valid frame (the first frame whose K words are all eos, else the final one);
         rank by cumulative log-probability + length_penalty * (frame + 1), first maximum in (frame, beam) order; follow the back pointers."""
         import numpy as np
