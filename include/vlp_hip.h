@@ -49,6 +49,8 @@ extern "C" {
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 /* + vlp_beam_select_groups (diverse beam search: the selection step with the beams in groups): it takes vlp_beam_select_args as it is plus two
  * scalars; purely additive as well. */
+/* + vlp_kept_rows_build, vlp_gemm_tn_grouped_mapped (the dense step's grouped wgrad over a device map of the kept rows): they take
+ * vlp_gemm_tn_args as it is plus the map and its device count; purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -179,6 +181,19 @@ int64_t vlp_gemm_tn_grouped_workspace_bytes(int32_t tiles);
  * lists the contraction rows of problem i, M = entries of the list.  B row m is read at live[i][m]; A row m at live[i][m] when flags[i]
  * has VLP_ROWS_X, else at row m (compact dY).  Pad entries (-1) add nothing.  Rows are summed in list order. */
 int vlp_gemm_tn_grouped_rows(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* flags, int32_t count, void* stream);
+/* The same launch contracting over a device row map shared by all `n` problems (one M for all of them): the contraction is
+ * sum over j < M' of A[map[j], :]^T . B[map[j], :] with M' = *count read on the device (clamped to [0, M]; map has M int32 entries, each
+ * clamped to [0, M - 1]: a bad map gives wrong numbers, never a fault).  Rows the map does not name are never read.  Grid and tiles are those
+ * of vlp_gemm_tn_grouped; a workgroup walks ceil(M' / 64) stages; with the identity map and M' = M the bits are those of
+ * vlp_gemm_tn_grouped.  M' = 0 gives zeros at beta = 0 and leaves C at beta = 1.  Nothing on the host depends on M'. */
+int vlp_gemm_tn_grouped_mapped(const vlp_gemm_tn_args* list, const int32_t* map, const int32_t* count, int32_t n, void* stream);
+/* The map of the dense training step's kept rows: sample b keeps positions 0 .. n_b - 1 with n_b = 1 + the last key column any query of
+ * the sample attends (maskb: the packed mask [B, L, Lp] of vlp_mask_pack / vlp_mask_build, byte 1 = attended) or lens_in[b] (exactly one of
+ * maskb / lens_in is given), at least Nv + 2, at least max_j clamp(pos[b, j], 0, L - 1) + 1 (pos [B, P] or NULL), at most L.  Writes
+ * lens[B] = n_b, map[0 .. M') = the dense rows b * L + l of the kept positions in ascending order (map[M' .. B * L) = B * L - 1) and
+ * *count = M'.  B <= 8192. */
+int vlp_kept_rows_build(const uint8_t* maskb, const int32_t* lens_in, const int64_t* pos, int32_t B, int32_t P, int32_t L, int32_t Lp,
+                        int32_t Nv, int32_t* lens, int32_t* map, int32_t* count, void* stream);
 
 /* out[n] (+)= sum_m A[m,n]  -- bias gradients (autograd SumBackward of the broadcast bias add). */
 typedef struct {

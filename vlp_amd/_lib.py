@@ -225,6 +225,8 @@ SYMBOLS = {
     "vlp_gemm_tn_grouped": (C.c_int, [C.POINTER(GemmTnArgs), i32, vp]),
     "vlp_gemm_tn_grouped_rows": (C.c_int, [C.POINTER(GemmTnArgs), C.POINTER(vp), C.POINTER(i32), i32, vp]),
     "vlp_gemm_tn_grouped_workspace_bytes": (i64, [i32]),
+    "vlp_gemm_tn_grouped_mapped": (C.c_int, [C.POINTER(GemmTnArgs), vp, vp, i32, vp]),
+    "vlp_kept_rows_build": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "vlp_colsum_workspace_bytes": (i64, [i32, i32]),
     "vlp_colsum": (C.c_int, [C.POINTER(ColsumArgs), vp]),
     "vlp_attn_fwd": (C.c_int, [C.POINTER(AttnFwdArgs), vp]),
@@ -490,6 +492,18 @@ def gemm_tn_grouped(problems, workspace=None):
         arr[i] = GemmTnArgs(ptr(a_), a_.stride(0), ptr(b_), b_.stride(0), ptr(c_), c_.stride(0), M, N, K, beta, ptr(w),
                             _nbytes(w), 0, 0, ptr(bias_out))
     _check(load().vlp_gemm_tn_grouped(arr, len(problems), stream_ptr()))
+
+
+def gemm_tn_grouped_mapped(problems, row_map, count):
+    """gemm_tn_grouped contracting over the rows row_map[0 .. count[0]) of both operands (device int32 [M] and [1]; one M for all problems)."""
+    _req_cuda(row_map, count)
+    arr = (GemmTnArgs * len(problems))()
+    for i, (a_, b_, c_, M, N, K, beta, bias_out) in enumerate(problems):
+        _req_cuda(a_, b_, c_, bias_out)
+        if row_map.numel() < M:
+            raise RuntimeError("gemm_tn_grouped_mapped: the map has %d entries, the problem %d rows" % (row_map.numel(), M))
+        arr[i] = GemmTnArgs(ptr(a_), a_.stride(0), ptr(b_), b_.stride(0), ptr(c_), c_.stride(0), M, N, K, beta, None, 0, 0, 0, ptr(bias_out))
+    _check(load().vlp_gemm_tn_grouped_mapped(arr, ptr(row_map), ptr(count), len(problems), stream_ptr()))
 
 
 def gemm_tn_grouped_rows(problems):
@@ -1080,6 +1094,16 @@ def gather_rows(src, lds, pos, out, ldo, B, P, L, H, row_off=None):
 def scatter_add_rows(src, lds, pos, dst, ldd, B, P, L, H, row_off=None):
     _req_cuda(src, pos, dst, row_off)
     _check(load().vlp_scatter_add_rows(ptr(src), lds, ptr(pos), ptr(dst), ldd, B, P, L, H, ptr(row_off), stream_ptr()))
+
+
+def kept_rows_build(B, L, Nv, lens, row_map, count, maskb=None, Lp=0, lens_in=None, pos=None):
+    """Kept rows of the dense step (vlp_kept_rows_build): from the packed mask `maskb` [B, L, Lp] or the per-sample lengths `lens_in` (int32
+    [B]), and the masked positions `pos` (int64 [B, P]); writes lens [B], row_map [B * L] and count [1] (int32, device)."""
+    _req_cuda(lens, row_map, count, maskb, lens_in, pos)
+    if lens.numel() < B or row_map.numel() < B * L or (pos is not None and (pos.dtype != torch.int64 or not pos.is_contiguous())):
+        raise RuntimeError("kept_rows_build: lens [B], row_map [B * L], pos contiguous int64")
+    P = pos.shape[1] if pos is not None else 0
+    _check(load().vlp_kept_rows_build(ptr(maskb), ptr(lens_in), ptr(pos), B, P, L, Lp, Nv, ptr(lens), ptr(row_map), ptr(count), stream_ptr()))
 
 
 def live_rows_build(pos, B, P, L, live, count, row_off=None):

@@ -529,6 +529,70 @@ extern "C" int vlp_live_rows_build(const int64_t* pos, int32_t B, int32_t P, int
     return VLP_OK;
 }
 
+// Kept rows of the dense step (vlp_gemm_tn_grouped_mapped): sample b keeps its first n_b positions, n_b = 1 + the last key column ANY query of the
+// sample attends (byte 1 of the packed mask [B, L, Lp]) -- or lens_in[b] where the caller knows it (MaskSpec: second_end) --, at least Nv + 2 and
+// at least max(pos[b, :]) + 1 (the rows the heads read), at most L.  One workgroup per sample reduces the mask, a second launch of one workgroup
+// writes the compact map (dense row indices, ascending, sample by sample), fills the entries past the count with M - 1 and stores the count.
+__global__ __launch_bounds__(256) void kept_lens_kernel(const uint8_t* __restrict__ maskb, const int32_t* __restrict__ lens_in, const int64_t* __restrict__ pos,
+                                                        int P, int L, int Lp, int Nv, int32_t* __restrict__ lens) {
+    __shared__ int kl_max;
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) kl_max = 0;
+    __syncthreads();
+    int n = 0;
+    if (maskb) {
+        const uint32_t* rows = reinterpret_cast<const uint32_t*>(maskb + (int64_t)b * L * Lp);      // Lp % 32 == 0: rows are whole words
+        const int wpr = Lp / 4, words = L * wpr;
+        for (int i = threadIdx.x; i < words; i += blockDim.x) {
+            const uint32_t w = rows[i];
+            const int k = (i % wpr) * 4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (((w >> (8 * e)) & 0xffu) == 1u && k + e < L) n = max(n, k + e + 1);
+        }
+    } else if (threadIdx.x == 0) {
+        n = lens_in[b];
+    }
+    if (pos) {
+        for (int t = threadIdx.x; t < P; t += blockDim.x) {
+            const int64_t ps = pos[(int64_t)b * P + t];
+            n = max(n, (int)(ps < 0 ? 0 : (ps >= L ? L - 1 : ps)) + 1);
+        }
+    }
+    atomicMax(&kl_max, n);
+    __syncthreads();
+    if (threadIdx.x == 0) lens[b] = min(max(kl_max, Nv + 2), L);
+}
+__global__ __launch_bounds__(256) void kept_map_kernel(const int32_t* __restrict__ lens, int B, int L, int32_t* __restrict__ map, int32_t* __restrict__ count) {
+    extern __shared__ int32_t km_off[];      // [B + 1]
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int b = 0; b < B; ++b) { km_off[b] = s; s += min(max(lens[b], 0), L); }
+        km_off[B] = s;
+    }
+    __syncthreads();
+    const int M = B * L, kept = km_off[B];
+    for (int i = threadIdx.x; i < M; i += blockDim.x) {
+        const int b = i / L, l = i - b * L;
+        if (l < km_off[b + 1] - km_off[b]) map[km_off[b] + l] = i;
+    }
+    for (int i = kept + threadIdx.x; i < M; i += blockDim.x) map[i] = M - 1;
+    if (threadIdx.x == 0) *count = kept;
+}
+extern "C" int vlp_kept_rows_build(const uint8_t* maskb, const int32_t* lens_in, const int64_t* pos, int32_t B, int32_t P, int32_t L, int32_t Lp,
+                                   int32_t Nv, int32_t* lens, int32_t* map, int32_t* count, void* stream) {
+    VLP_CHECK_ARG((maskb != nullptr) != (lens_in != nullptr), "vlp_kept_rows_build: the packed mask OR the per-sample lengths");
+    VLP_CHECK_ARG(lens && map && count && B > 0 && B <= 8192 && L > 0 && (int64_t)B * L < 0x7fffffff && Nv >= 0 && (pos == nullptr || P > 0),
+                  "vlp_kept_rows_build: bad args (B <= 8192)");
+    VLP_CHECK_ARG(maskb == nullptr || Lp == (L + 31) / 32 * 32, "vlp_kept_rows_build: Lp must be roundup32(L)");
+    VLP_ENTER(lens, "vlp_kept_rows_build");
+    hipLaunchKernelGGL(kept_lens_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, maskb, lens_in, pos, P, L, Lp, Nv, lens);
+    VLP_CHECK_LAUNCH("vlp_kept_rows_build");
+    hipLaunchKernelGGL(kept_map_kernel, dim3(1), dim3(256), (size_t)(B + 1) * sizeof(int32_t), (hipStream_t)stream, lens, B, L, map, count);
+    VLP_CHECK_LAUNCH("vlp_kept_rows_build");
+    return VLP_OK;
+}
+
 __global__ void vqa_mul_fwd_kernel(const f16* h, f16* out, int B, int L, int Nv, int H, const int32_t* row_off) {
     const int64_t total = (int64_t)B * H;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {

@@ -34,6 +34,8 @@ struct GemmTnParams {
     int tiles_k, tiles_n, xcd_remap, split_major;
     const int32_t* live;         // listed contraction rows (vlp_gemm_tn_grouped_rows): B row m is read at live[m], < 0 = pad (adds nothing); or nullptr
     int a_listed;                // with live: A row m is read at live[m] too (else A is compact: row m)
+    const int32_t* map;          // mapped contraction (vlp_gemm_tn_grouped_mapped): contraction row m of BOTH operands is read at map[m], m < *mcount; or nullptr
+    const int32_t* mcount;       // with map: device count of mapped rows, clamped to [0, M]
 };
 
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
@@ -227,7 +229,11 @@ DEVFN int tn_swz(int r) { return ((r & 3) | (((r >> 3) & 1) << 2)) << 1; }
 #define TN_SK_FINAL 2
 #define TN_SK_SLOTS 20       // f32x4 per thread in a partial: 16 accumulator tiles + 4 bias tiles
 // LISTED: the problem walks a row list (p.live, vlp_gemm_tn_grouped_rows); compiled out of every other caller
-template <int BN_T, int BK_T, int NS = 2, int BM_T = TN_BM, bool SK = false, bool LISTED = false>
+// MAPPED: the problem contracts over the rows map[0 .. *mcount) of both operands (p.map / p.mcount, vlp_gemm_tn_grouped_mapped): the walk is
+// ceil(count / BM_T) stages long, full stages stay on the LDS-DMA path with the per-thread source row taken from the map, the last partial stage
+// goes through registers with zero fill.  No dependent load sits in front of a DMA issue: the map entries of the NEXT stage are loaded right
+// behind a stage's DMAs, so they land under the wait the ring has anyway.  The LDS image is that of the unmapped walk.  Compiled out of every other caller
+template <int BN_T, int BK_T, int NS = 2, int BM_T = TN_BM, bool SK = false, bool LISTED = false, bool MAPPED = false>
 DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begin = 0, int sk_m_end = 0, int sk_role = 0, float* sk_part = nullptr,
                         int* sk_flag = nullptr) {
     constexpr int WK_ = BK_T / 64;
@@ -254,8 +260,12 @@ DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begi
     }
     const int n0 = ntile * BN_T;
     const int k0 = ktile * BK_T;
-    const int m_begin = SK ? sk_m_begin : split * p.rows_per_split;
-    const int m_end = SK ? sk_m_end : min(p.M, m_begin + p.rows_per_split);
+    static_assert(!MAPPED || (!SK && !LISTED && BN_T == BK_T && NS == 2),
+                  "mapped walk: plain grouped launch, square tiles (one map entry serves both operands' staging rows), two-stage ring (vmcnt(0) per stage)");
+    const int m_begin = MAPPED ? 0 : SK ? sk_m_begin : split * p.rows_per_split;
+    int m_end_ = SK ? sk_m_end : min(p.M, m_begin + p.rows_per_split);
+    if (MAPPED) m_end_ = min(max(__builtin_amdgcn_readfirstlane(*p.mcount), 0), p.M);      // read once; a bad count walks fewer / at most M rows
+    const int m_end = m_end_;
     const int nstages = (m_end - m_begin + BM_T - 1) / BM_T;
 
     // staging: pass i covers tile rows ARP*i .. ; thread -> (row = ARP*i + tid/ACH, physical chunk = tid%ACH).  The swizzle acts on
@@ -287,11 +297,45 @@ DEVFN void tn_glds_tile(const GemmTnParams& p, int bid, f16* smem, int sk_m_begi
     for (int i = 0; i < AP; ++i) asrc[i] = p.A + (int64_t)(m_begin + arow + ARP * i) * p.lda + acol[i];
 #pragma unroll
     for (int i = 0; i < BP; ++i) bsrc[i] = p.B + (int64_t)(m_begin + brow + BRP * i) * p.ldb + bcol[i];
+    // mapped walk: mraw = the loads of the map entries of this thread's AP staging rows of the stage that stage() issues next (stages are issued
+    // in order 0, 1, 2, ...).  map_fetch only issues the loads; the entries are first touched (clamped) where the next stage() builds its addresses,
+    // behind the ring's wait.  The map index is clamped to the map's M entries and the entry to [0, M - 1]: a bad map gives wrong numbers, never
+    // an address outside the operands
+    int mraw[AP];
+    auto map_fetch = [&](int st) {
+#pragma unroll
+        for (int i = 0; i < AP; ++i) mraw[i] = p.map[min(st * BM_T + arow + ARP * i, p.M - 1)];
+    };
+    if (MAPPED) map_fetch(0);
     auto stage = [&](int st, int buf) {
         f16* as = smem + buf * (ATILE + BTILE);
         f16* bs = as + ATILE;
         const int mbase = m_begin + st * BM_T;
-        if (LISTED) {                             // listed rows: every stage through registers, row m fetched at live[m], pads zero-filled
+        if (MAPPED) {
+            int mrow[AP];
+#pragma unroll
+            for (int i = 0; i < AP; ++i) mrow[i] = min(max(mraw[i], 0), p.M - 1);
+            if (mbase + BM_T <= m_end) {              // full stage (wave-uniform): LDS-DMA from the mapped rows, same LDS image
+                const uint32_t as_l = smem_lds + (uint32_t)(buf * (ATILE + BTILE)) * 2u, bs_l = as_l + (uint32_t)ATILE * 2u;
+#pragma unroll
+                for (int i = 0; i < AP; ++i) glds16(p.A + (int64_t)mrow[i] * p.lda + acol[i], as_l + (uint32_t)((ARP * i) * BN_T + wid * 512) * 2u);
+#pragma unroll
+                for (int i = 0; i < BP; ++i) glds16(p.B + (int64_t)mrow[i] * p.ldb + bcol[i], bs_l + (uint32_t)((BRP * i) * BK_T + wid * 512) * 2u);
+            } else {                                  // the last partial stage: through registers, rows past the count zero-filled (never read)
+#pragma unroll
+                for (int i = 0; i < AP; ++i) {
+                    const int r = arow + ARP * i;
+                    u32x4 va = (u32x4){0, 0, 0, 0}, vb = (u32x4){0, 0, 0, 0};
+                    if (mbase + r < m_end) {
+                        va = *reinterpret_cast<const u32x4*>(p.A + (int64_t)mrow[i] * p.lda + acol[i]);
+                        vb = *reinterpret_cast<const u32x4*>(p.B + (int64_t)mrow[i] * p.ldb + bcol[i]);
+                    }
+                    *reinterpret_cast<u32x4*>(as + r * BN_T + apc * 8) = va;
+                    *reinterpret_cast<u32x4*>(bs + r * BK_T + bpc * 8) = vb;
+                }
+            }
+            if ((st + 1) * BM_T < m_end) map_fetch(st + 1);      // lands under the ring's wait for this stage
+        } else if (LISTED) {                             // listed rows: every stage through registers, row m fetched at live[m], pads zero-filled
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
                 const int r = arow + ARP * i, m = mbase + r;
@@ -488,10 +532,11 @@ struct TnGroupEntry {
 struct TnGroupParams {
     TnGroupEntry e[TN_GROUP_MAX];
     int count, total_tiles, xcd_remap;
+    const int32_t* map; const int32_t* mcount;      // vlp_gemm_tn_grouped_mapped: every problem contracts over the rows map[0 .. *mcount), or nullptr
     int nst, tail;           // balanced form: contraction stages (of 64 rows) per tile, the same for every problem of the group; stages of the tail cohort
 };
 
-template <int BN_T, int BK_T, int NS, int BM_T>
+template <int BN_T, int BK_T, int NS, int BM_T, bool MAPPED = false>
 __global__ __launch_bounds__((BN_T / 64) * (BK_T / 64) * 64, 2) void gemm_tn_grouped_kernel(TnGroupParams gp) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     int bid = blockIdx.x;
@@ -507,7 +552,9 @@ __global__ __launch_bounds__((BN_T / 64) * (BK_T / 64) * 64, 2) void gemm_tn_gro
     p.M = e.M; p.N = e.N; p.K = e.K; p.beta = e.beta; p.splits = 1; p.rows_per_split = (e.M + TN_BM - 1) / TN_BM * TN_BM;
     p.tiles_k = e.tiles_k; p.tiles_n = 0; p.xcd_remap = 0; p.split_major = 0;
     p.live = e.live; p.a_listed = e.a_listed;
-    if (e.live) tn_glds_tile<BN_T, BK_T, NS, BM_T, false, true>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
+    p.map = MAPPED ? gp.map : nullptr; p.mcount = MAPPED ? gp.mcount : nullptr;
+    if (MAPPED) tn_glds_tile<BN_T, BK_T, NS, BM_T, false, false, MAPPED>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
+    else if (e.live) tn_glds_tile<BN_T, BK_T, NS, BM_T, false, true>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
     else tn_glds_tile<BN_T, BK_T, NS, BM_T>(p, bid - e.tile_begin, reinterpret_cast<f16*>(smem_raw));
 }
 
@@ -541,7 +588,7 @@ __global__ __launch_bounds__((BN_T / 64) * (BK_T / 64) * 64, 2) void gemm_tn_gro
         p.slab = nullptr; p.bias_slab = nullptr; p.bias_out = e.bias_out;
         p.M = e.M; p.N = e.N; p.K = e.K; p.beta = e.beta; p.splits = 1; p.rows_per_split = 0;
         p.tiles_k = e.tiles_k; p.tiles_n = 0; p.xcd_remap = 0; p.split_major = 0;
-        p.live = nullptr; p.a_listed = 0;
+        p.live = nullptr; p.a_listed = 0; p.map = nullptr; p.mcount = nullptr;
         if (j < 6)
             tn_glds_tile<BN_T, BK_T, NS, BM_T, true>(p, tile - e.tile_begin, reinterpret_cast<f16*>(smem_raw), 0, cut * BM_T, TN_SK_FINAL,
                                                        part + (int64_t)tile * (TN_SK_SLOTS * T * 4), flags + grp);
@@ -645,7 +692,7 @@ extern "C" int vlp_gemm_tn(const vlp_gemm_tn_args* a, void* stream) {
     p.tiles_n = cdiv(a->N, TN_BN);
     p.xcd_remap = (a->variant & 8) ? 1 : 0;
     p.split_major = (a->variant & 16) ? 1 : 0;
-    p.live = nullptr; p.a_listed = 0;
+    p.live = nullptr; p.a_listed = 0; p.map = nullptr; p.mcount = nullptr;
     if (splits > 1) {
         const int64_t need = (int64_t)splits * a->N * a->K * (int64_t)sizeof(float) + (a->bias_out ? (int64_t)splits * a->N * (int64_t)sizeof(float) : 0);
         if (!a->workspace || a->workspace_bytes < need)
@@ -709,13 +756,15 @@ static int tn_check_one(const vlp_gemm_tn_args* a) {
     return VLP_OK;
 }
 
-static int tn_grouped_launch(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* lflags, int32_t count, void* stream) {
+static int tn_grouped_launch(const vlp_gemm_tn_args* list, const int32_t* const* live, const int32_t* lflags, int32_t count, void* stream,
+                             const int32_t* map = nullptr, const int32_t* mcount = nullptr) {
     // tile shape / ring depth of the grouped launch: 0 = 128x128 tiles, 2 stages (two 4-wave workgroups per CU); 1 = 256x128, 2 stages;
     // 2 = 256x128, 3 stages; 3 = 128x256, 3 stages (8-wave workgroups, one per CU); 4 = 128x128, FOUR stages of 32 contraction rows (same 64 KiB:
     // two workgroups per CU, three stages in flight).  VLP_TN_GROUP_MODE overrides (A/B runs).
     int mode = TN_GROUP_DEFAULT_MODE;      // the product library carries mode 0 only; 1 .. 5 were measured in round 4 and lose (-DVLP_LAB_BUILD)
 #ifdef VLP_LAB_BUILD
-    if (const char* e = getenv("VLP_TN_GROUP_MODE")) { mode = atoi(e); if (mode < 0 || mode > 5) mode = 0; }      // read per launch: A/B runs switch it inside one process
+    if (map) mode = 0;                     // the mapped walk exists for mode 0 only
+    else if (const char* e = getenv("VLP_TN_GROUP_MODE")) { mode = atoi(e); if (mode < 0 || mode > 5) mode = 0; }      // read per launch: A/B runs switch it inside one process
 #endif
     // 5 = stream-K form of mode 0 (gemm_tn_grouped_sk_kernel): needs list[0].workspace (vlp_gemm_tn_grouped_workspace_bytes), a tile count that is a
     // multiple of 6, one M for all problems and >= 14 stages; otherwise the launch runs as mode 0
@@ -738,6 +787,14 @@ static int tn_grouped_launch(const vlp_gemm_tn_args* list, const int32_t* const*
     }
     for (int i = count; i < TN_GROUP_MAX; ++i) { gp.e[i] = gp.e[0]; gp.e[i].tile_begin = 0x7fffffff; }
     gp.count = count; gp.total_tiles = tiles; gp.xcd_remap = 1;
+    gp.map = map; gp.mcount = mcount;
+    if (map) {
+        const size_t smem = (size_t)2 * 64 * (128 + 128) * sizeof(f16);
+        VLP_ONCE_PER_DEVICE((void)hipFuncSetAttribute((const void*)gemm_tn_grouped_kernel<128, 128, 2, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL((gemm_tn_grouped_kernel<128, 128, 2, 64, true>), dim3(tiles), dim3(256), smem, (hipStream_t)stream, gp);
+        VLP_CHECK_LAUNCH("vlp_gemm_tn_grouped_mapped");
+        return VLP_OK;
+    }
 #define LAUNCH_TN_GROUP(BNT, BKT, NSV, BMV)                                                                                             \
     do {                                                                                                                                \
         const size_t smem = (size_t)(NSV) * (BMV) * ((BNT) + (BKT)) * sizeof(f16);                                                      \
@@ -786,4 +843,11 @@ extern "C" int vlp_gemm_tn_grouped_rows(const vlp_gemm_tn_args* list, const int3
     VLP_CHECK_ARG(list != nullptr && live != nullptr && count >= 1 && count <= TN_GROUP_MAX, "vlp_gemm_tn_grouped_rows: 1..%d problems and their row lists", TN_GROUP_MAX);
     VLP_ENTER(list[0].A, "vlp_gemm_tn_grouped_rows");
     return tn_grouped_launch(list, live, flags, count, stream);
+}
+
+extern "C" int vlp_gemm_tn_grouped_mapped(const vlp_gemm_tn_args* list, const int32_t* map, const int32_t* count, int32_t n, void* stream) {
+    VLP_CHECK_ARG(list != nullptr && map != nullptr && count != nullptr && n >= 1 && n <= TN_GROUP_MAX, "vlp_gemm_tn_grouped_mapped: 1..%d problems, a row map and its count", TN_GROUP_MAX);
+    VLP_ENTER(list[0].A, "vlp_gemm_tn_grouped_mapped");
+    for (int i = 1; i < n; ++i) VLP_CHECK_ARG(list[i].M == list[0].M, "vlp_gemm_tn_grouped_mapped: one M (the map's length) for all problems");
+    return tn_grouped_launch(list, nullptr, nullptr, n, stream, map, count);
 }

@@ -39,7 +39,7 @@ def is_no_decay(name):
 
 class _State(object):
     """What one forward leaves behind for its backward."""
-    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids", "policy")
+    __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids", "policy", "kept")
 
     def __init__(self):
         self.gen = self.B = self.L = self.P = 0      # engine generation, batch, sequence length, masked positions per sample
@@ -49,6 +49,7 @@ class _State(object):
         self.has_mlm = False         # P > 0: the masked-LM head ran
         self.pos_ids = None          # explicit position ids ([B, L] int64) or None = 0..L-1
         self.pk = None               # (row_off, row_map, M') of a packed forward
+        self.kept = None             # (map, count) on the device: the kept rows of a dense training forward (the mapped grouped wgrad walks them)
         self.pretext = None          # (pretext workspace, vis_masked_pos) of a mask_image_regions forward
         self.task_labels = None      # set by the loss of this forward (mlm_loss / vqa_loss / score_samples), read by its backward
         self.mlm_smooth = None       # label-smoothed loss: the scalar arguments of the matching backward launch
@@ -146,6 +147,7 @@ class Engine(Decoder):
         self._pk_cache = {}               # kept-length tuple -> (row_off, row_map device tensors, M'): batches repeat in bench / epochs
         self._pk_lens = {}                # id(mask tensor) -> (weakref, version, ..., lens): lengths derived from a dense mask, once per tensor
         self.last_packed_rows = None      # M' of the latest packed forward (None: dense) -- bench.py / tests read it
+        self.last_wgrad_mapped = False    # the latest backward's layer wgrads walked the map of kept rows (dense step, VLP_WGRAD_KEPT) -- tests read it
         self._live_n = None               # device int32 [1]: rows the latest backward's listed-row path walked (None: the full path ran)
 
     # ------------------------------------------------------------------------------------------
@@ -361,6 +363,8 @@ class Engine(Decoder):
         ws = {"Lp": _ru(L, 32)}
         ws["maskb"] = torch.empty(B, L, ws["Lp"], device=dev, dtype=torch.uint8)
         ws["maskt"] = torch.empty(B, ws["Lp"], ws["Lp"], device=dev, dtype=torch.uint8)
+        # kept rows of the dense step (vlp_kept_rows_build): per-sample lengths, the compact map of dense row indices, its length M'
+        ws["kept_lens"], ws["kept_map"], ws["kept_n"] = (torch.empty(n, device=dev, dtype=torch.int32) for n in (B, M, 1))
         ws["img16"], ws["vpe_in"], ws["wpe_pad"] = h(Mv, 2048), h(Mv, PE_PAD), h(H, PE_PAD)
         ws["h1"], ws["vis_h"], ws["vispe_h"] = h(Mv, 2048), h(Mv, H), h(Mv, H)
         ws["emb_pre"], ws["x0"] = h(M, H), h(M, H)
@@ -733,6 +737,11 @@ class Engine(Decoder):
         st.batch = (img, input_ids.contiguous(), token_type_ids.contiguous(), masked_pos)
         st.pk = (ro, rm, M) if ro is not None else None
         st.pretext = (pt, st_vmp) if pt is not None else None
+        # dense training step with a grouped wgrad (backward: M >= 2048): the map of its kept rows rides along (VLP_WGRAD_KEPT=0: off).
+        # dense=True (score_samples) stays unmapped by contract: its head reads sampled rows the rule does not cover
+        if (ro is None and not dense and (train or torch.is_grad_enabled()) and M >= 2048
+                and os.environ.get("VLP_WGRAD_KEPT", "1") != "0"):
+            st.kept = (ws["kept_map"], ws["kept_n"])
 
         def prep_mask(am):
             if mask_spec:                       # per-sample lengths -> packed masks on the device (seq2seq_loader.py:292-301)
@@ -747,6 +756,12 @@ class Engine(Decoder):
                     am = am[:, None, :].expand(B, L, L)
                 am = am.to(torch.long).contiguous()
                 K.mask_pack(am, ws["maskb"], B, L, ws["Lp"], out_t=want_t)
+            if st.kept is not None:
+                # the rows whose gradient can be non-zero in this dense step, by the rule of _kept_lengths, on the device (no read-back: the
+                # host never learns M'): every later position is attended by no query and read by no head, so its dY is an exact zero in
+                # every weight gradient of every layer, and the grouped wgrad (backward) contracts over the mapped rows only
+                K.kept_rows_build(B, L, Nv, ws["kept_lens"], ws["kept_map"], ws["kept_n"], maskb=None if mask_spec else ws["maskb"], Lp=ws["Lp"],
+                                  lens_in=am.second_end if mask_spec else None, pos=masked_pos.to(torch.long).contiguous() if P > 0 else None)
 
         # ---- side stream underneath the forward (training): (1) the K-padded box / class operand of the third region GEMM, (2) the packed
         # attention masks (first read by layer 0's attention, ~190 us into the forward), (3) the W^T shadows of this step's dgrad GEMMs (the
@@ -1215,6 +1230,9 @@ class Engine(Decoder):
         # one vlp_gemm_tn_grouped launch per layer instead of 4 split-M wgrads + 4 reduces where there are enough rows for a long contraction
         # per workgroup; tiny batches keep split-M
         grouped = M >= 2048
+        # the forward's map of kept rows (dense training steps only; never a score_samples forward); VLP_WGRAD_KEPT=0 read per call
+        kept = st.kept if (grouped and st.pk is None and task != "logprob" and os.environ.get("VLP_WGRAD_KEPT", "1") != "0") else None
+        self.last_wgrad_mapped = kept is not None
         for i in reversed(range(NL)):
             Ln = "bert.encoder.layer.%d." % i
             a = ws["layers"][i]
@@ -1261,11 +1279,16 @@ class Engine(Decoder):
                 if grouped:
                     # the layer's four weight gradients (+ bias gradients) as ONE grid of 36 + 108 + 144 + 144 output tiles, every
                     # workgroup walking the whole contraction: no split-M slabs, no reduce launches (csrc/gemm_tn.hip)
-                    K.gemm_tn_grouped([
+                    problems = [
                         (dy2, a["g"], self.G(Ln + "output.dense.weight"), M, H, I, beta, self.G(Ln + "output.dense.bias")),
                         (ds["dz"], a["x1"], self.G(Ln + "intermediate.dense.weight"), M, I, H, beta, self.G(Ln + "intermediate.dense.bias")),
                         (dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, beta, self.G(Ln + "attention.self.query.bias")),
-                        (dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), M, H, H, beta, self.G(Ln + "attention.output.dense.bias"))])
+                        (dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), M, H, H, beta, self.G(Ln + "attention.output.dense.bias"))]
+                    if kept is not None:
+                        # dense step: rows past a sample's kept length have dY == 0 in all four problems; the walk skips them (device map)
+                        K.gemm_tn_grouped_mapped(problems, kept[0], kept[1])
+                    else:
+                        K.gemm_tn_grouped(problems)
                 else:
                     self._tn(dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, ws, beta,
                              bias=self.G(Ln + "attention.self.query.bias"))     # packed [3H, H] gradient
