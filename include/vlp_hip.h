@@ -51,6 +51,8 @@ extern "C" {
  * scalars; purely additive as well. */
 /* + vlp_kept_rows_build, vlp_gemm_tn_grouped_mapped (the dense step's grouped wgrad over a device map of the kept rows): they take
  * vlp_gemm_tn_args as it is plus the map and its device count; purely additive as well. */
+/* + vlp_token_score (log-probability, entropy, rank and arg-max of a given token per logits row: scoring given captions) and its argument
+ * struct: purely additive as well. */
 
 typedef enum {
     VLP_OK = 0,
@@ -782,6 +784,28 @@ typedef struct {
     float temperature;
 } vlp_token_policy_bwd_args;
 int vlp_token_policy_bwd(const vlp_token_policy_bwd_args* a, void* stream);
+
+/* Scoring a given token per row (Engine.score_captions: log-likelihood, token accuracy and entropy of given captions).  For one row with
+ * id = ids[r] >= 0 (clamped to V - 1 from above), l_v the fp16 logit of column v < V as fp32 (columns >= V are never read):
+ *   lse = log sum_v exp(l_v);  logp = l_id - lse;  entropy = -sum_v q_v log q_v with q_v = exp(l_v - lse) and 0 log 0 = 0 -- on a 16-byte
+ *     aligned row with ld_logits % 8 == 0 bit for bit what vlp_token_policy_fwd writes at temperature 1 with entropy (the same expressions,
+ *     the same summation order); any other row is walked column by column, in another summation order;
+ *   rank = #{v : l_v > l_id} + #{v < id : l_v == l_id}: the token's place, from 0, when the columns are sorted by falling logit with
+ *     equal logits in rising column order.  Comparisons of the fp16 values, exact;
+ *   top_id / top_logit: the row's largest logit and its column, the SMALLEST column on ties (vlp_argmax_rows's first maximum).
+ * The two tie rules agree: rank == 0 exactly when top_id == id.  A row without a column above -inf has top_id 0.
+ * A row with ids[r] < 0 is not counted and not read: logp = lse = entropy = top_logit = 0, rank = top_id = -1.
+ * One launch, one workgroup per row, the two passes of vlp_token_logprob_fwd.  VLP_ERR_BAD_ARG before the launch: a null operand, rows or
+ * V < 1, V > 2^24, ld_logits < V. */
+typedef struct {
+    const void* logits; int64_t ld_logits;    /* [rows, V] fp16 */
+    const int64_t* ids;                       /* [rows]; < 0: the row is not counted */
+    float* logp; float* lse; float* entropy;  /* [rows] out */
+    int32_t* rank;                            /* [rows] out */
+    int64_t* top_id; float* top_logit;        /* [rows] out */
+    int32_t rows, V;
+} vlp_token_score_args;
+int vlp_token_score(const vlp_token_score_args* a, void* stream);
 
 /* CIDEr-D of id strings (SCST, the reward the reference computes on the host: scst_utils.py:36-63 with pycocoevalcap's Cider(df='corpus')).
  * The specification is vlp_amd/scst.py CiderD.compute_score on the strings array_to_str makes:

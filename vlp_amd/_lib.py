@@ -134,6 +134,11 @@ class TokenPolicyFwdArgs(C.Structure):
                 ("temperature", f32)]
 
 
+class TokenScoreArgs(C.Structure):
+    _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("logp", vp), ("lse", vp), ("entropy", vp), ("rank", vp), ("top_id", vp),
+                ("top_logit", vp), ("rows", i32), ("V", i32)]
+
+
 class TokenPolicyBwdArgs(C.Structure):
     _fields_ = [("logits", vp), ("ld_logits", i64), ("ids", vp), ("lse", vp), ("entropy", vp), ("g", vp), ("h", vp), ("dlogits", vp),
                 ("ld_dlogits", i64), ("rows", i32), ("V", i32), ("temperature", f32)]
@@ -266,6 +271,7 @@ SYMBOLS = {
     "vlp_token_logprob_bwd": (C.c_int, [C.POINTER(TokenLogprobBwdArgs), vp]),
     "vlp_token_policy_fwd": (C.c_int, [C.POINTER(TokenPolicyFwdArgs), vp]),
     "vlp_token_policy_bwd": (C.c_int, [C.POINTER(TokenPolicyBwdArgs), vp]),
+    "vlp_token_score": (C.c_int, [C.POINTER(TokenScoreArgs), vp]),
     "vlp_region_mask_build": (C.c_int, [vp, i32, i32, i32, vp, vp]),
     "vlp_pretext_fwd": (C.c_int, [C.POINTER(PretextFwdArgs), vp]),
     "vlp_pretext_bwd": (C.c_int, [C.POINTER(PretextBwdArgs), vp]),
@@ -853,6 +859,14 @@ def token_policy_bwd(logits, ld, ids, lse, g, dlogits, ldd, rows, V, temperature
     _req_cuda(logits, ids, lse, g, dlogits, h, entropy)
     a = TokenPolicyBwdArgs(ptr(logits), ld, ptr(ids), ptr(lse), ptr(entropy), ptr(g), ptr(h), ptr(dlogits), ldd, rows, V, float(temperature))
     _check(load().vlp_token_policy_bwd(C.byref(a), stream_ptr()))
+
+
+def token_score(logits, ld, ids, logp, lse, entropy, rank, top_id, top_logit, rows, V):
+    """Per row of fp16 logits and its id (int64; < 0: not counted, the row is not read): logp / lse / entropy f32 (vlp_token_policy_fwd's bits at
+    temperature 1), rank int32, top_id int64 and top_logit f32 (include/vlp_hip.h vlp_token_score)."""
+    _req_cuda(logits, ids, logp, lse, entropy, rank, top_id, top_logit)
+    a = TokenScoreArgs(ptr(logits), ld, ptr(ids), ptr(logp), ptr(lse), ptr(entropy), ptr(rank), ptr(top_id), ptr(top_logit), rows, V)
+    _check(load().vlp_token_score(C.byref(a), stream_ptr()))
 
 
 def cider_d_workspace_bytes(G, R, T, mult):

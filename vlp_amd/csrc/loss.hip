@@ -327,6 +327,77 @@ extern "C" int vlp_token_policy_bwd(const vlp_token_policy_bwd_args* a, void* st
 }
 
 // ---------------------------------------------------------------------------------------------
+// Scoring a given token per row (include/vlp_hip.h vlp_token_score): what vlp_token_policy_fwd writes at T = 1 with entropy -- the same
+// expressions in the same order, without the products and quotients by T = 1 (exact there), so logp / lse / entropy are its bits on a
+// 16-byte aligned row -- plus the token's rank and the row's arg-max, which ride on the max pass: the token's own logit is read first, every
+// thread counts the columns that beat it (exact comparisons of fp16 values) and keeps its first maximum.  The counts are reduced as floats:
+// a count is <= V <= 2^24, so every partial sum is an exact integer.  A row with id < 0 is not read.
+// VEC = false walks a row that is not 16-byte aligned column by column (another thread <-> column assignment: another summation order).
+// ---------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(CE_THREADS) void token_score_kernel(const f16* __restrict__ logits, int64_t ld, const int64_t* __restrict__ ids,
+                                                                 float* __restrict__ logp, float* __restrict__ lse, float* __restrict__ entropy,
+                                                                 int32_t* __restrict__ rank, int64_t* __restrict__ top_id,
+                                                                 float* __restrict__ top_logit, int V) {
+    __shared__ float sh[8];
+    __shared__ float sv[CE_THREADS];
+    __shared__ int si[CE_THREADS];
+    const int row = blockIdx.x;
+    int64_t id64 = ids[row];
+    if (id64 < 0) {                                         // block-uniform: an uncounted position costs one launch slot and six stores
+        if (threadIdx.x == 0) {
+            logp[row] = 0.f; lse[row] = 0.f; entropy[row] = 0.f;
+            rank[row] = -1; top_id[row] = -1; top_logit[row] = 0.f;
+        }
+        return;
+    }
+    const int id = (int)(id64 >= V ? V - 1 : id64);
+    const f16* x = logits + (int64_t)row * ld;
+    const float lid = (float)x[id];
+    float mx = -INFINITY;
+    int bi = 0x7fffffff, cnt = 0;
+    row_visit<CE_THREADS, VEC>(x, 0, V, [&](float z, int v) {
+        bi = z > mx ? v : bi;                               // ascending columns within a thread: `>` keeps the first
+        mx = fmaxf(mx, z);
+        cnt += (z > lid || (z == lid && v < id)) ? 1 : 0;
+    });
+    const float best = mx;                                  // this thread's maximum, at column bi
+    mx = block_reduce_max<CE_THREADS>(mx, sh);
+    float s = 0.f, a = 0.f;
+    row_visit<CE_THREADS, VEC>(x, 0, V, [&](float z, int) {
+        const float d = z - mx;
+        const float e = __expf(d);
+        s += e;
+        a += d == -INFINITY ? 0.f : e * d;                  // a -inf logit: 0 log 0 = 0, never 0 * inf
+    });
+    s = block_reduce_sum<CE_THREADS>(s, sh);
+    a = block_reduce_sum<CE_THREADS>(a, sh);
+    const float above = block_reduce_sum<CE_THREADS>((float)cnt, sh);
+    argmax_block256(best, bi, sv, si);
+    if (threadIdx.x == 0) {
+        const float ls = __logf(s);
+        a = a / s;                                          // sum q_v d_v: the entropy is log S - A / S
+        lse[row] = mx + ls;
+        entropy[row] = ls - a;
+        logp[row] = lid - (mx + ls);
+        rank[row] = (int32_t)above;
+        top_id[row] = si[0] == 0x7fffffff ? 0 : si[0];      // no column above -inf (all -inf / NaN): column 0, as a first-maximum scan says
+        top_logit[row] = sv[0];
+    }
+}
+
+extern "C" int vlp_token_score(const vlp_token_score_args* a, void* stream) {
+    VLP_CHECK_ARG(a && a->logits && a->ids && a->logp && a->lse && a->entropy && a->rank && a->top_id && a->top_logit, "vlp_token_score: null operand");
+    VLP_ENTER(a->logits, "vlp_token_score");
+    VLP_CHECK_ARG(a->rows > 0 && a->V > 0 && a->V <= (1 << 24) && a->ld_logits >= a->V && (uintptr_t)a->logits % 2 == 0, "vlp_token_score: layout");
+    const bool vec = a->ld_logits % 8 == 0 && (uintptr_t)a->logits % 16 == 0;
+    hipLaunchKernelGGL(vec ? token_score_kernel<true> : token_score_kernel<false>, dim3(a->rows), dim3(CE_THREADS), 0, (hipStream_t)stream,
+                       (const f16*)a->logits, a->ld_logits, a->ids, a->logp, a->lse, a->entropy, a->rank, a->top_id, a->top_logit, a->V);
+    VLP_CHECK_LAUNCH("vlp_token_score");
+    return VLP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // BCE with logits.  loss = sum_{b,n} [max(x,0) - x*y + log(1 + exp(-|x|))] / (B*N) * N
 // ---------------------------------------------------------------------------------------------
 // Where y comes from is a template parameter (as the forbidden words of the top-k kernels are): SPARSE = false reads the dense f32 [B, ldl]

@@ -936,17 +936,62 @@ class Engine(Decoder):
         temperature, entropy = float(temperature), bool(entropy)
         if not (0.0 < temperature < float("inf")):
             raise RuntimeError("vlp_amd: score_samples needs a finite temperature > 0 (got %r)" % temperature)
+        st, sw, B, T, V = self._scoring_forward(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, sample_ids, mask_word_id,
+                                                "score_samples expects sampled ids", "SCST scoring sequence", "--max_len_b")
+        if temperature == 1.0 and not entropy:
+            K.token_logprob_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V)
+            return st, sw["logp"]
+        if entropy and "entropy" not in sw:
+            sw["entropy"] = torch.empty(B, T, device=self.device, dtype=torch.float32)
+        ent = sw["entropy"] if entropy else None
+        K.token_policy_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V, temperature=temperature, entropy=ent)
+        st.policy = (temperature, ent)
+        return (st, sw["logp"], ent) if entropy else (st, sw["logp"])
+
+    def score_captions(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, caption_ids, mask_word_id,
+                       return_logits=False, uncounted_fill=0):
+        """Inference: how probable given captions are.  Takes the decoder's inputs and caption_ids [R, T] (T = output length - input length; row r
+        is scored against image row r); a position holding -1 is not counted.  The pass is score_samples' -- vlp_scst_layout, the dense forward
+        without dropout, the LM head over the T [MASK] slots, in the ("scst", B, in_len, T) workspace -- under no_grad, and one vlp_token_score
+        launch in place of vlp_token_logprob_fwd: logp holds score_samples' bits.  An uncounted position is fed to the model as id 0 (no later
+        counted position of a causal caption attends to it) and its logits row is not read.
+        Returns (logp f32, entropy f32, rank int32, top_id int64), each [R, T] and the caller's own (copies); an uncounted position holds
+        (0, 0, -1, -1).  Test hooks: return_logits=True appends the fp16 rows that were scored, [R, T, V]; uncounted_fill is the id fed in place
+        of a -1.  Refused in train() mode with gradients enabled: nothing here is differentiable (that is score_samples)."""
+        model = self._model()
+        if model.training and torch.is_grad_enabled():
+            raise RuntimeError("vlp_amd: score_captions is an inference entry (no gradient); call it under eval() or torch.no_grad() -- "
+                               "differentiable log-probabilities come from sample_mode='sample' in train() mode")
+        with torch.no_grad():
+            cap = caption_ids.to(torch.long)
+            fed = torch.where(cap < 0, torch.full_like(cap, int(uncounted_fill)), cap)
+            st, _, B, T, V = self._scoring_forward(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, fed, mask_word_id,
+                                                   "score_captions expects caption ids", "scoring sequence", "--max_tgt_length")
+            dev = self.device
+            logp, lse, ent, top_logit = (torch.empty(B, T, device=dev, dtype=torch.float32) for _ in range(4))
+            rank = torch.empty(B, T, device=dev, dtype=torch.int32)
+            top_id = torch.empty(B, T, device=dev, dtype=torch.long)
+            K.token_score(st.ws["logits"], st.ws["Vp"], cap.contiguous().view(-1), logp, lse, ent, rank, top_id, top_logit, B * T, V)
+            out = (logp, ent, rank, top_id)
+            if return_logits:
+                out += (st.ws["logits"][:B * T, :V].reshape(B, T, V).clone(),)
+        return out
+
+    def _scoring_forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, ids, mask_word_id, expects, what, flag):
+        """The pass score_samples and score_captions share: the checks (a refused call leaves no workspace behind), the ("scst", B, in_len, T)
+        workspace, vlp_scst_layout of the ids [B, T] and the dense training forward without dropout with the LM head over the T [MASK] slots.
+        Returns (state, workspace, B, T, V); state.task_labels are the ids, state.ws["logits"] the B * T rows to score."""
         self.pack()
         model = self._model()
         V = model.config.vocab_size
         B, in_len, out_len = self._decode_check(vis_feats, vis_pe, input_ids, token_type_ids, attention_mask)
         T = out_len - in_len
-        if tuple(sample_ids.shape) != (B, T):
-            raise RuntimeError("vlp_amd: score_samples expects sampled ids [B, %d] (output length - input length), got %s" % (T, tuple(sample_ids.shape)))
+        if tuple(ids.shape) != (B, T):
+            raise RuntimeError("vlp_amd: %s [B, %d] (output length - input length), got %s" % (expects, T, tuple(ids.shape)))
         Lo = in_len + 2 * T - 1
         if Lo > 256:
-            raise RuntimeError("vlp_amd: the SCST scoring sequence has %d + 2 x %d - 1 = %d positions, more than the attention kernels' 256; "
-                               "lower --max_len_b" % (in_len, T, Lo))
+            raise RuntimeError("vlp_amd: the %s has %d + 2 x %d - 1 = %d positions, more than the attention kernels' 256; "
+                               "lower %s" % (what, in_len, T, Lo, flag))
         key = ("scst", B, in_len, T)
         sw = self._ws.get(key)
         if sw is None:
@@ -959,21 +1004,13 @@ class Engine(Decoder):
         am = attention_mask[:, :out_len, :out_len].to(torch.long).contiguous()
         tt = token_type_ids[:, :out_len].to(torch.long).contiguous()
         pid = position_ids[:, :out_len].to(torch.long).contiguous()
-        sw["labels"].copy_(sample_ids)
+        sw["labels"].copy_(ids)
         K.scst_layout(input_ids.to(torch.long).contiguous(), sw["labels"], tt, pid, am, sw["ids"], sw["seg"], sw["pos"], sw["mask"], sw["mpos"],
                       mask_word_id)
         st = self.forward(vis_feats, vis_pe, sw["ids"], sw["seg"], sw["mask"], sw["mpos"], True, True, False, position_ids=sw["pos"],
                           dropout=False, dense=True)
         st.task_labels = sw["labels"].view(-1)
-        if temperature == 1.0 and not entropy:
-            K.token_logprob_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V)
-            return st, sw["logp"]
-        if entropy and "entropy" not in sw:
-            sw["entropy"] = torch.empty(B, T, device=self.device, dtype=torch.float32)
-        ent = sw["entropy"] if entropy else None
-        K.token_policy_fwd(st.ws["logits"], st.ws["Vp"], st.task_labels, sw["logp"], st.ws["lse_ce"], B * T, V, temperature=temperature, entropy=ent)
-        st.policy = (temperature, ent)
-        return (st, sw["logp"], ent) if entropy else (st, sw["logp"])
+        return st, sw, B, T, V
 
     # ------------------------------------------------------------------------------------------
     # backward

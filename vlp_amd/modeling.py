@@ -753,6 +753,23 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         logp, ent = _LogprobFn.apply(eng._anchor, out[1], eng, out[0], out[2])
         return ids, logp, ent
 
+    def score(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, caption_ids, lengths=None):
+        """How probable given captions are under this checkpoint (not in the reference): caption r is scored against image row r, teacher
+        forced, in one pass over all positions (Engine.score_captions).  caption_ids: R token id lists, or a padded [R, W] tensor with
+        lengths [R]; vlp_amd.caption_score.counted_positions says which of the n = token_type_ids.shape[1] - input_ids.shape[1] positions
+        count (the caption's tokens and its closing [SEP], eos_id; a caption of >= n tokens is cut and has none).
+        Returns (logp f32, entropy f32, rank int32, top_id int64, counted bool), each [R, n]: the log-probability of the caption's token,
+        the entropy of the model's distribution, the token's rank in it (0: the model's first choice) and that first choice; (0, 0, -1, -1)
+        where counted is False.  Inference only: refused in train() mode with gradients enabled."""
+        from .caption_score import counted_positions
+        if not input_ids.is_cuda:
+            raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only (inputs must be on the GPU); there is no CPU path")
+        n = token_type_ids.shape[1] - input_ids.shape[1]
+        ids, counted, _ = counted_positions(caption_ids, n, self.eos_id, lengths, vocab_size=self.config.vocab_size)
+        dev = input_ids.device
+        out = self.engine.score_captions(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, ids.to(dev), self.mask_word_id)
+        return out + (counted.to(dev),)
+
     # ---- beam search: host side (what the reference also does on the host) -------------------------------
     def _ngram_blocker(self, batch_size, vocab_size):
         """Stateful callback for Engine.decode_beam: tracks the partial hypotheses (:1367-1384) and returns the uint8 [B*K, V] mask
