@@ -1,4 +1,4 @@
-"""GPU: the listed-row backward of the last encoder layer (Engine._layer_bwd_live) and the kernels under it.
+"""GPU: the listed-row backward of the last encoder layer (Engine._bwd_layer with listed=True) and the kernels under it.
 
 In a masked-LM step the gradient that enters the encoder is zero outside the masked rows, so the last layer's LayerNorm backwards, FFN /
 attention-output dgrads and their weight gradients walk a device list of the distinct masked rows (vlp_live_rows_build, vlp_gemm_nt_rows,

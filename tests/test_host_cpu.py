@@ -144,6 +144,35 @@ def test_engine_layout_and_buckets():
     assert decay[i + 1].endswith("key.weight") and decay[i + 2].endswith("value.weight")          # packed QKV
 
 
+def test_layer_handle_table_names_every_layer_parameter_once():
+    """engine.layer_param_names is the one place a layer's parameter names are written down: for a 2-layer model they are exactly the
+    bert.encoder.layer.{0,1}.* names of named_parameters(), each once, under the fields of the handle-table row; the engine's source reads
+    every field; the names behind one field lie back to back in the flat buffer (a packed view is one slice).  A parameter added to
+    the model without a handle fails here."""
+    from vlp_amd import engine as E
+    from vlp_amd import modeling as M
+    cfg = M.BertConfig(512, num_hidden_layers=2, type_vocab_size=6)
+    m = M.BertForPreTrainingLossMask(cfg, enable_butd=True, len_vis_input=100, tasks="img2txt", allow_random_fc7=True)
+    numel = {n: p.numel() for n, p in m.named_parameters()}
+    lay = m.engine.plan_layout(m)
+    import ast
+    read = {n.attr for n in ast.walk(ast.parse(open(os.path.join(ROOT, "vlp_amd", "engine.py")).read())) if isinstance(n, ast.Attribute)}
+    for i in (0, 1):
+        table = E.layer_param_names(i)
+        assert tuple(table) == E._LayerViews.__slots__ and len(table) == 12
+        listed = [n for ns in table.values() for n in ns]
+        assert sorted(listed) == sorted(n for n in numel if n.startswith("bert.encoder.layer.%d." % i))
+        assert len(set(listed)) == len(listed) == 16
+        for f, ns in table.items():
+            assert f in read, "no engine code reads the field %s" % f
+            assert all(n.endswith(".bias") == f.endswith("_b") and n.endswith(".weight") == f.endswith("_w") for n in ns), (f, ns)
+            grp = "nodecay" if E.is_no_decay(ns[0]) else "decay"
+            assert lay["names"][grp].count(ns[0]) == 1
+            for a, b in zip(ns, ns[1:]):
+                assert lay["offsets"][grp][b] - lay["offsets"][grp][a] == numel[a], (a, b)
+    assert not set(E.layer_param_names(0).values()) & set(E.layer_param_names(1).values())
+
+
 def test_entry_script_arguments_match_reference():
     from vlp_amd import run_img2txt_dist as R
     ours = {a.dest: a.default for a in R.build_parser()._actions if a.dest != "help"}

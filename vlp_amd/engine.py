@@ -37,6 +37,26 @@ def is_no_decay(name):
     return any(nd in name for nd in NO_DECAY)
 
 
+def layer_param_names(i):
+    """{field of the layer handle table: the names of encoder layer i's parameters behind it}.  The one place that writes a layer's
+    parameter names down (besides _ordered_names, whose job is their order in the flat buffers); q / k / v lie back to back there and
+    are one packed [3H, H] weight and one [3H] bias to every kernel."""
+    L = "bert.encoder.layer.%d." % i
+    qkv = [L + "attention.self." + n for n in ("query", "key", "value")]
+    one = {"o": "attention.output.dense", "ln1": "attention.output.LayerNorm", "fc1": "intermediate.dense", "fc2": "output.dense",
+           "ln2": "output.LayerNorm"}
+    names = {"qkv_w": tuple(n + ".weight" for n in qkv), "qkv_b": tuple(n + ".bias" for n in qkv)}
+    for f, n in one.items():
+        names[f + "_w"], names[f + "_b"] = (L + n + ".weight",), (L + n + ".bias",)
+    return names
+
+
+class _LayerViews(object):
+    """One encoder layer's twelve views of a flat buffer (Engine._layers): weight `*_w` and bias `*_b` of the packed QKV projection, the
+    attention-output dense (o), LayerNorm 1 (gamma = ln1_w, beta = ln1_b), the intermediate (fc1) and output (fc2) dense and LayerNorm 2."""
+    __slots__ = tuple(layer_param_names(0))
+
+
 class _State(object):
     """What one forward leaves behind for its backward."""
     __slots__ = ("gen", "B", "L", "P", "seed", "p_drop", "ws", "batch", "has_mlm", "task_labels", "pretext", "pk", "mlm_smooth", "pos_ids", "policy", "kept")
@@ -54,6 +74,53 @@ class _State(object):
         self.task_labels = None      # set by the loss of this forward (mlm_loss / vqa_loss / score_samples), read by its backward
         self.mlm_smooth = None       # label-smoothed loss: the scalar arguments of the matching backward launch
         self.policy = None           # score_samples with a temperature / entropy: (temperature, entropy rows or None) of vlp_token_policy_fwd
+
+
+class _Backward(object):
+    """What the phases of one Engine.backward share: the forward's state and shapes, the streams, and the listed-row state."""
+    __slots__ = ("eng", "st", "ws", "sh", "beta", "NL", "H", "I", "A", "V", "Nv", "M", "Mv", "ro", "rm", "p", "pa", "seed", "scale", "grouped",
+                 "kept", "main", "side", "use_side", "live", "R", "live_ready")
+
+    def __init__(self, eng, st, task):
+        model = eng._model()
+        cfg = model.config
+        self.eng, self.st, self.ws, self.sh, self.NL = eng, st, st.ws, None, cfg.num_hidden_layers       # sh: the W^T shadows (prologue)
+        self.H, self.I, self.A, self.V, self.Nv = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.vocab_size, model.len_vis_input
+        # (packed rows: every [M, *] activation of the step has M' = sum of the kept lengths rows)
+        self.ro, self.rm, self.M = st.pk if st.pk is not None else (None, None, st.B * st.L)
+        self.Mv, self.beta = st.B * self.Nv, 1 if eng.grads_dirty else 0
+        (self.p, self.pa), self.seed, self.scale = st.p_drop, st.seed, 1.0 / math.sqrt(self.H // self.A)
+        # one vlp_gemm_tn_grouped launch per layer instead of 4 split-M wgrads + 4 reduces where there are enough rows for a long contraction
+        # per workgroup; tiny batches keep split-M
+        self.grouped = self.M >= 2048
+        # the forward's map of kept rows (dense training steps only; never a score_samples forward); VLP_WGRAD_KEPT=0 read per call
+        self.kept = st.kept if (self.grouped and st.pk is None and task != "logprob" and os.environ.get("VLP_WGRAD_KEPT", "1") != "0") else None
+        self.main, self.use_side = torch.cuda.current_stream(), eng.WGRAD_SIDE_STREAM
+        self.side = eng._side_stream() if self.use_side else None
+        self.live = self.R = self.live_ready = None      # the last layer's row list, its capacity, the event behind its prologue
+
+    def on_side(self, fn):
+        """Run fn() on the side stream, ordered behind everything the main stream has issued so far (without one: here and now)."""
+        if not self.use_side:
+            fn()
+            return
+        self.side.wait_stream(self.main)
+        with torch.cuda.stream(self.side):
+            fn()
+
+    def ln_slot(self, k):
+        """The private dgamma / dbeta partials of LayerNorm k (the order of Engine._ln_table)."""
+        n = self.ws["ln_slot_bytes"]
+        return self.ws["ln_slots"][k * n:(k + 1) * n]
+
+    def wgrads_issued(self, i):
+        """Layer i's weight gradients are issued: its gradient slice is complete in this stream's order, and the event behind them guards
+        the dY set they read."""
+        self.eng._bucket_done(self.NL - i)
+        if self.use_side:
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+            self.eng._side_done[i & 1] = ev
 
 
 class Engine(Decoder):
@@ -124,6 +191,7 @@ class Engine(Decoder):
         self._shadow = None
         self._shadow_ev = None            # event behind the W^T shadows a training forward transposed on the side stream, consumed by its backward
         self._ln_tab = None               # _ln_table()
+        self._layer_tab = None            # _layers()
         self._zero1 = None                # zero_placeholder()
         self._pretext_on = False          # the latest forward ran with mask_image_regions
         self._pooler_dirty = False        # the pooler gradient buffer holds something a beta == 0 backward without the pretext branch must clear
@@ -261,12 +329,32 @@ class Engine(Decoder):
         self._shadow = None
         self._shadow_ev = None
         self._ln_tab = None
+        self._layer_tab = None
 
     def P(self, name):
         return self._params[name].data
 
     def G(self, name):
         return self._params[name].grad
+
+    def _layers(self):
+        """The layer handle table: [(parameter views, gradient views)] per encoder layer, slices of the flat buffers under the fields of
+        layer_param_names (pack() binds every .data / .grad to the same storage once; built on first use, dropped by invalidate())."""
+        if self._layer_tab is None:
+            tab = []
+            for i in range(self._model().config.num_hidden_layers):
+                w, g = _LayerViews(), _LayerViews()
+                for f, ns in layer_param_names(i).items():
+                    grp = "nodecay" if is_no_decay(ns[0]) else "decay"
+                    off, shape = self.offsets[grp], self._params[ns[0]].shape
+                    if any(off[b] - off[a] != shape.numel() for a, b in zip(ns, ns[1:])):
+                        raise RuntimeError("vlp_amd.Engine: %s do not lie back to back in the flat buffer" % (ns,))
+                    lo, hi, packed = off[ns[0]], off[ns[0]] + len(ns) * shape.numel(), (len(ns) * shape[0],) + tuple(shape[1:])
+                    setattr(w, f, self.flat[grp][lo:hi].view(packed))
+                    setattr(g, f, self.gflat[grp][lo:hi].view(packed))
+                tab.append((w, g))
+            self._layer_tab = tab
+        return self._layer_tab
 
     def unused_parameter_names(self):
         """Parameters that receive no gradient (static per task).  The pooler is used by the vis_pretext branch only:
@@ -392,7 +480,7 @@ class Engine(Decoder):
             NAp = _ru(NA, 64)
             ws.update(NAp=NAp, vq_e=h(B, H), vq_a1=h(B, 2 * H), vq_logits=h(B, NAp), vq_dlogits=h(B, NAp), vq_dz1=h(B, 2 * H), vq_de=h(B, H))
         # backward scratch (shared by all layers)
-        ws.update(dx=h(M, H), dx_alt=h(M, H), dpre=h(M, H), dpre_d=h(M, H), dz=h(M, I), dctx=h(M, H), dqkv=h(M, 3 * H),
+        ws.update(dx=h(M, H), dx_alt=h(M, H), dpre=h(M, H), dctx=h(M, H),
                   delta=f(B, A, L), d_vis_h=h(Mv, H), d_vispe_h=h(Mv, H), dz1v=h(Mv, 2048), dwpe_pad=h(H, PE_PAD), acc32=f(K.embed_bwd_workspace_floats(B, L, Nv, H)))
         # dY operands of the weight-gradient GEMMs, double-buffered by layer parity: the wgrads of layer i run on a side stream
         # while the main stream already works on layer i-1
@@ -436,12 +524,9 @@ class Engine(Decoder):
         """Device table [2 * layers + 1, 2] of (dgamma, dbeta) addresses: slot 2i = attention.output.LayerNorm of layer i, 2i + 1 =
         output.LayerNorm of layer i, last = embeddings.LayerNorm (addresses of the flat gradient buffer are stable)."""
         if self._ln_tab is None:
-            NL = self._model().config.num_hidden_layers
             rows = []
-            for i in range(NL):
-                L = "bert.encoder.layer.%d." % i
-                for n in ("attention.output.LayerNorm", "output.LayerNorm"):
-                    rows.append([self.G(L + n + ".weight").data_ptr(), self.G(L + n + ".bias").data_ptr()])
+            for _, g in self._layers():
+                rows += [[g.ln1_w.data_ptr(), g.ln1_b.data_ptr()], [g.ln2_w.data_ptr(), g.ln2_b.data_ptr()]]
             rows.append([self.G("bert.embeddings.LayerNorm.weight").data_ptr(), self.G("bert.embeddings.LayerNorm.bias").data_ptr()])
             self._ln_tab = torch.tensor(rows, dtype=torch.int64, device=self.device)
         return self._ln_tab
@@ -454,12 +539,11 @@ class Engine(Decoder):
             cfg = model.config
             H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
             items = []
-            for i, s in enumerate(sh["layers"]):
-                L = "bert.encoder.layer.%d." % i
-                items.append((self.P(L + "attention.self.query.weight"), H, s["qkvT"], 3 * H, 3 * H, H, 3 * H))   # packed [3H, H] -> [H, 3H]
-                items.append((self.P(L + "attention.output.dense.weight"), H, s["oT"], H, H, H, H))
-                items.append((self.P(L + "intermediate.dense.weight"), H, s["w1T"], I, I, H, I))
-                items.append((self.P(L + "output.dense.weight"), I, s["w2T"], H, H, I, H))
+            for s, (w, _) in zip(sh["layers"], self._layers()):
+                items.append((w.qkv_w, H, s["qkvT"], 3 * H, 3 * H, H, 3 * H))   # packed [3H, H] -> [H, 3H]
+                items.append((w.o_w, H, s["oT"], H, H, H, H))
+                items.append((w.fc1_w, H, s["w1T"], I, I, H, I))
+                items.append((w.fc2_w, I, s["w2T"], H, H, I, H))
             items.append((self.P("vis_embed.2.weight"), 2048, sh["v2T"], H, H, 2048, H))
             if model.tasks == "vqa2":
                 NA = model.num_answers
@@ -689,6 +773,112 @@ class Engine(Decoder):
             self._side_done = [None, None]
         return self._side
 
+    def _prep_mask(self, st, am, want_t):
+        """The packed attention masks of this forward (want_t: also the transposed one backward reads) and the map of a dense step's kept rows."""
+        ws, B, L, P, Nv = st.ws, st.B, st.L, st.P, self._model().len_vis_input
+        pt, mask_spec = st.pretext, isinstance(am, MaskSpec)
+        if mask_spec:                       # per-sample lengths -> packed masks on the device (seq2seq_loader.py:292-301)
+            am.check(B, L)
+            # (BLOCK_MASKED_REGION_KEYS: opt-in, the reference's own loader leaves the masked regions' key columns attendable, see above)
+            K.mask_build(am.second_st, am.second_end, am.is_s2s, ws["maskb"], B, L, ws["Lp"], out_t=want_t,
+                         region_mask=pt[0]["rmask"] if (pt is not None and self.BLOCK_MASKED_REGION_KEYS) else None, Nv=Nv)
+        else:
+            if am is None:
+                am = torch.ones(B, L, dtype=torch.long, device=st.batch[1].device)
+            if am.dim() == 2:       # modeling.py:818-819
+                am = am[:, None, :].expand(B, L, L)
+            am = am.to(torch.long).contiguous()
+            K.mask_pack(am, ws["maskb"], B, L, ws["Lp"], out_t=want_t)
+        if st.kept is not None:
+            # the rows whose gradient can be non-zero in this dense step, by the rule of _kept_lengths, on the device (no read-back: the
+            # host never learns M'): every later position is attended by no query and read by no head, so its dY is an exact zero in
+            # every weight gradient of every layer, and the grouped wgrad (backward) contracts over the mapped rows only
+            K.kept_rows_build(B, L, Nv, ws["kept_lens"], ws["kept_map"], ws["kept_n"], maskb=None if mask_spec else ws["maskb"], Lp=ws["Lp"],
+                              lens_in=am.second_end if mask_spec else None, pos=st.batch[3].to(torch.long).contiguous() if P > 0 else None)
+
+    def _fwd_inputs(self, st, attention_mask, prep_pe, with_grad):
+        """Input preparation of a forward.  With gradients and the side stream it runs underneath the forward: (1) the K-padded box / class
+        operand of the third region GEMM, (2) the packed attention masks (first read by layer 0's attention, ~190 us into the forward),
+        (3) the W^T shadows of this step's dgrad GEMMs (the weights are final once the optimizer has stepped; 78 us, first read at the head
+        of backward, behind _shadow_ev).  The main stream starts the region projections at once and waits for the events of (1) / (2),
+        returned here, where it first reads them; (None, None): everything was issued on the main stream."""
+        self._shadow_ev = None
+        want_t = st.ws["maskt"] if with_grad else None
+        if not (with_grad and self.WGRAD_SIDE_STREAM):
+            self._prep_mask(st, attention_mask, want_t)
+            prep_pe()
+            return None, None
+        side = self._side_stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            prep_pe()
+            pe_ev = torch.cuda.Event()
+            pe_ev.record(side)
+            self._prep_mask(st, attention_mask, want_t)
+            mask_ev = torch.cuda.Event()
+            mask_ev.record(side)
+            if self._params_done is not None:
+                side.wait_event(self._params_done)        # the transposes read every weight matrix
+            if self._param_works is not None:
+                # sharded optimizer step: the parameters arrive by per-bucket all-gathers that may still be in flight; the
+                # transposes read EVERY weight matrix, so this stream waits for all of them (the main stream keeps waiting per
+                # bucket where the forward first reads it -- Work.wait() may be called again there)
+                for w in self._param_works.values():
+                    if w is not None:
+                        w.wait()
+            self._refresh_shadows()
+            self._shadow_ev = torch.cuda.Event()
+            self._shadow_ev.record(side)
+        return pe_ev, mask_ev
+
+    def _fwd_layer(self, st, i, x, mask_ev):
+        """Encoder layer i on the hidden states x (modeling.py:268-372); returns its output.  mask_ev: the event behind the packed masks,
+        waited for in front of the attention (layer 0 of a forward that prepared them on the side stream)."""
+        cfg = self._model().config
+        H, I, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        a, (w, _), seed, (p, pa) = st.ws["layers"][i], self._layers()[i], st.seed, st.p_drop
+        ro, rm, M = st.pk if st.pk is not None else (None, None, st.B * st.L)
+        self._nt(x, w.qkv_w, a["qkv"], M, 3 * H, H, bias=w.qkv_b)
+        if mask_ev is not None:
+            torch.cuda.current_stream().wait_event(mask_ev)
+        K.attn_fwd(a["qkv"], st.ws["maskb"], a["ctx"], a["lse"], st.B, st.L, A, 1.0 / math.sqrt(H // A), dropout_p=pa, seed=seed,
+                   rng_stream=16 * i + 1, row_off=ro)
+        self._nt(a["ctx"], w.o_w, a["pre1"], M, H, H, bias=w.o_b, residual=x, dropout_p=p, seed=seed, rng_stream=16 * i + 2, row_map=rm)
+        K.layernorm_fwd(a["pre1"], w.ln1_w, w.ln1_b, a["x1"], M, H, a["st1"][0], a["st1"][1])
+        # a["z"] receives gelu'(z), not z: the only consumer is the FFN-down dgrad epilogue, which then multiplies by a stored
+        # number instead of re-evaluating erf + exp per element
+        self._nt(a["x1"], w.fc1_w, a["g"], M, I, H, bias=w.fc1_b, preact=a["z"], act=K.ACT_GELU_SAVE_GRAD)
+        self._nt(a["g"], w.fc2_w, a["pre2"], M, H, I, bias=w.fc2_b, residual=a["x1"], dropout_p=p, seed=seed, rng_stream=16 * i + 3, row_map=rm)
+        K.layernorm_fwd(a["pre2"], w.ln2_w, w.ln2_b, a["x2"], M, H, a["st2"][0], a["st2"][1])
+        return a["x2"]
+
+    def _fwd_heads(self, st, x, want_vqa):
+        """The heads' forward up to the logits on the last layer's output x: masked LM (P > 0), the VQA classifier, pooler + pretext loss."""
+        model = self._model()
+        H, V, Nv = model.config.hidden_size, model.config.vocab_size, model.len_vis_input
+        ws, B, L, P, pt = st.ws, st.B, st.L, st.P, st.pretext
+        ro = st.pk[0] if st.pk is not None else None
+        if P > 0:
+            C = "cls.predictions."
+            R = B * P
+            K.gather_rows(x, H, st.batch[3].contiguous(), ws["sel"], H, B, P, L, H, row_off=ro)
+            self._nt(ws["sel"], self.P(C + "transform.dense.weight"), ws["tg"], R, H, H, bias=self.P(C + "transform.dense.bias"),
+                     preact=ws["tz"], act=K.ACT_GELU)
+            K.layernorm_fwd(ws["tg"], self.P(C + "transform.LayerNorm.weight"), self.P(C + "transform.LayerNorm.bias"), ws["tln"], R, H,
+                            ws["tstat"][0], ws["tstat"][1])
+            self._nt(ws["tln"], self.P("bert.embeddings.word_embeddings.weight"), ws["logits"], R, V, H, bias=self.P(C + "bias"), ldy=ws["Vp"])
+        if want_vqa:
+            NA = model.num_answers
+            K.vqa_mul_fwd(x, ws["vq_e"], B, L, Nv, H, row_off=ro)
+            self._nt(ws["vq_e"], self.P("ans_classifier.0.weight"), ws["vq_a1"], B, 2 * H, H, bias=self.P("ans_classifier.0.bias"), act=K.ACT_RELU)
+            self._nt(ws["vq_a1"], self.P("ans_classifier.2.weight"), ws["vq_logits"], B, NA, 2 * H, bias=self.P("ans_classifier.2.bias"), ldy=ws["NAp"])
+        if pt is not None:
+            # BertPooler (modeling.py:411-417) -- only this branch reads it -- and the pretext loss (:1113-1131)
+            ptw, vmp = pt
+            K.gather_rows(x, H, ptw["pos0"], ptw["sel0"], H, B, 1, L, H, row_off=ro)
+            self._nt(ptw["sel0"], self.P("bert.pooler.dense.weight"), ptw["pooled"], B, H, H, bias=self.P("bert.pooler.dense.bias"), act=K.ACT_TANH)
+            K.pretext_fwd(ws["vis_h"], ws["vispe_h"], ptw["pooled"], vmp, ptw["probs"], ptw["sample"], ptw["loss"], B, Nv, vmp.shape[1], H)
+
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, attention_mask, masked_pos, train, want_mlm, want_vqa,
                 vis_masked_pos=None, position_ids=None, dropout=True, dense=False):
         """Runs embeddings + encoder (+ heads' forward up to the logits).  Returns the _State.  vis_masked_pos ([B, Pm] int64, values
@@ -698,10 +888,9 @@ class Engine(Decoder):
         self.pack()
         model = self._model()
         cfg = model.config
-        H, I, A, NL, Nv, V = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers, model.len_vis_input, cfg.vocab_size
+        H, NL, Nv = cfg.hidden_size, cfg.num_hidden_layers, model.len_vis_input
         B, L = input_ids.shape
         self._check_regions(vis_feats, vis_pe)
-        mask_spec = isinstance(attention_mask, MaskSpec)
         if L < Nv + 2:
             raise RuntimeError("vlp_amd: sequence length %d too short for %d regions" % (L, Nv))
         P = masked_pos.shape[1] if (want_mlm and masked_pos is not None and masked_pos.numel() > 0) else 0
@@ -722,7 +911,6 @@ class Engine(Decoder):
         self.last_packed_rows = M if ro is not None else None
 
         # ---- inputs -----------------------------------------------------------------------------
-        want_t = ws["maskt"] if train or torch.is_grad_enabled() else None
         pt = None
         if vis_masked_pos is not None and vis_masked_pos.numel() > 0:
             Pm = vis_masked_pos.shape[1]
@@ -743,58 +931,7 @@ class Engine(Decoder):
                 and os.environ.get("VLP_WGRAD_KEPT", "1") != "0"):
             st.kept = (ws["kept_map"], ws["kept_n"])
 
-        def prep_mask(am):
-            if mask_spec:                       # per-sample lengths -> packed masks on the device (seq2seq_loader.py:292-301)
-                am.check(B, L)
-                # (BLOCK_MASKED_REGION_KEYS: opt-in, the reference's own loader leaves the masked regions' key columns attendable, see above)
-                K.mask_build(am.second_st, am.second_end, am.is_s2s, ws["maskb"], B, L, ws["Lp"], out_t=want_t,
-                             region_mask=pt["rmask"] if (pt is not None and self.BLOCK_MASKED_REGION_KEYS) else None, Nv=Nv)
-            else:
-                if am is None:
-                    am = torch.ones(B, L, dtype=torch.long, device=input_ids.device)
-                if am.dim() == 2:       # modeling.py:818-819
-                    am = am[:, None, :].expand(B, L, L)
-                am = am.to(torch.long).contiguous()
-                K.mask_pack(am, ws["maskb"], B, L, ws["Lp"], out_t=want_t)
-            if st.kept is not None:
-                # the rows whose gradient can be non-zero in this dense step, by the rule of _kept_lengths, on the device (no read-back: the
-                # host never learns M'): every later position is attended by no query and read by no head, so its dY is an exact zero in
-                # every weight gradient of every layer, and the grouped wgrad (backward) contracts over the mapped rows only
-                K.kept_rows_build(B, L, Nv, ws["kept_lens"], ws["kept_map"], ws["kept_n"], maskb=None if mask_spec else ws["maskb"], Lp=ws["Lp"],
-                                  lens_in=am.second_end if mask_spec else None, pos=masked_pos.to(torch.long).contiguous() if P > 0 else None)
-
-        # ---- side stream underneath the forward (training): (1) the K-padded box / class operand of the third region GEMM, (2) the packed
-        # attention masks (first read by layer 0's attention, ~190 us into the forward), (3) the W^T shadows of this step's dgrad GEMMs (the
-        # weights are final once the optimizer has stepped; 78 us, first read at the head of backward).  The main stream starts the region
-        # projections at once and waits for (1) / (2) where it first reads them.
-        self._shadow_ev = None
-        pe_ev = mask_ev = None
-        if (train or torch.is_grad_enabled()) and self.WGRAD_SIDE_STREAM:
-            side = self._side_stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                prep_pe()
-                pe_ev = torch.cuda.Event()
-                pe_ev.record(side)
-                prep_mask(attention_mask)
-                mask_ev = torch.cuda.Event()
-                mask_ev.record(side)
-                if self._params_done is not None:
-                    side.wait_event(self._params_done)        # the transposes read every weight matrix
-                if self._param_works is not None:
-                    # sharded optimizer step: the parameters arrive by per-bucket all-gathers that may still be in flight; the
-                    # transposes read EVERY weight matrix, so this stream waits for all of them (the main stream keeps waiting per
-                    # bucket where the forward first reads it -- Work.wait() may be called again there)
-                    for w in self._param_works.values():
-                        if w is not None:
-                            w.wait()
-                self._refresh_shadows()
-                self._shadow_ev = torch.cuda.Event()
-                self._shadow_ev.record(side)
-        else:
-            prep_mask(attention_mask)
-            prep_pe()
-
+        pe_ev, mask_ev = self._fwd_inputs(st, attention_mask, prep_pe, train or torch.is_grad_enabled())
         self.wait_params("nodecay")
         self.wait_params(len(self.buckets) - 1)             # region projections
         self.wait_params(len(self.buckets) - 2)             # embedding tables
@@ -813,51 +950,13 @@ class Engine(Decoder):
                     position_ids=position_ids, region_mask=pt["rmask"] if pt is not None else None, row_map=rm, rows=M if rm is not None else 0)
         K.layernorm_fwd(ws["emb_pre"], self.P(E + "LayerNorm.weight"), self.P(E + "LayerNorm.bias"), ws["x0"], M, H, ws["stat0"][0], ws["stat0"][1],
                         dropout_p=p, seed=seed, rng_stream=1000, row_map=rm)
-        # ---- encoder (modeling.py:268-372) -----------------------------------------------------------
+        # ---- encoder, then the heads up to the logits -------------------------------------------------
         x = ws["x0"]
-        scale = 1.0 / math.sqrt(H // A)
         for i in range(NL):
-            Ln = "bert.encoder.layer.%d." % i
-            a = ws["layers"][i]
             self.wait_params(NL - i)                            # bucket of layer i
-            self._nt(x, self.P(Ln + "attention.self.query.weight"), a["qkv"], M, 3 * H, H, bias=self.P(Ln + "attention.self.query.bias"))
-            if i == 0 and mask_ev is not None:
-                torch.cuda.current_stream().wait_event(mask_ev)
-            K.attn_fwd(a["qkv"], ws["maskb"], a["ctx"], a["lse"], B, L, A, scale, dropout_p=pa, seed=seed, rng_stream=16 * i + 1, row_off=ro)
-            self._nt(a["ctx"], self.P(Ln + "attention.output.dense.weight"), a["pre1"], M, H, H, bias=self.P(Ln + "attention.output.dense.bias"),
-                     residual=x, dropout_p=p, seed=seed, rng_stream=16 * i + 2, row_map=rm)
-            K.layernorm_fwd(a["pre1"], self.P(Ln + "attention.output.LayerNorm.weight"), self.P(Ln + "attention.output.LayerNorm.bias"),
-                            a["x1"], M, H, a["st1"][0], a["st1"][1])
-            # a["z"] receives gelu'(z), not z: the only consumer is the FFN-down dgrad epilogue, which then multiplies by a stored
-            # number instead of re-evaluating erf + exp per element
-            self._nt(a["x1"], self.P(Ln + "intermediate.dense.weight"), a["g"], M, I, H, bias=self.P(Ln + "intermediate.dense.bias"),
-                     preact=a["z"], act=K.ACT_GELU_SAVE_GRAD)
-            self._nt(a["g"], self.P(Ln + "output.dense.weight"), a["pre2"], M, H, I, bias=self.P(Ln + "output.dense.bias"),
-                     residual=a["x1"], dropout_p=p, seed=seed, rng_stream=16 * i + 3, row_map=rm)
-            K.layernorm_fwd(a["pre2"], self.P(Ln + "output.LayerNorm.weight"), self.P(Ln + "output.LayerNorm.bias"), a["x2"], M, H,
-                            a["st2"][0], a["st2"][1])
-            x = a["x2"]
-        # ---- heads ------------------------------------------------------------------------------------
+            x = self._fwd_layer(st, i, x, mask_ev if i == 0 else None)
         self.wait_params(0)
-        if P > 0:
-            C = "cls.predictions."
-            R = B * P
-            K.gather_rows(x, H, masked_pos.contiguous(), ws["sel"], H, B, P, L, H, row_off=ro)
-            self._nt(ws["sel"], self.P(C + "transform.dense.weight"), ws["tg"], R, H, H, bias=self.P(C + "transform.dense.bias"),
-                     preact=ws["tz"], act=K.ACT_GELU)
-            K.layernorm_fwd(ws["tg"], self.P(C + "transform.LayerNorm.weight"), self.P(C + "transform.LayerNorm.bias"), ws["tln"], R, H,
-                            ws["tstat"][0], ws["tstat"][1])
-            self._nt(ws["tln"], self.P("bert.embeddings.word_embeddings.weight"), ws["logits"], R, V, H, bias=self.P(C + "bias"), ldy=ws["Vp"])
-        if want_vqa:
-            NA = model.num_answers
-            K.vqa_mul_fwd(x, ws["vq_e"], B, L, Nv, H, row_off=ro)
-            self._nt(ws["vq_e"], self.P("ans_classifier.0.weight"), ws["vq_a1"], B, 2 * H, H, bias=self.P("ans_classifier.0.bias"), act=K.ACT_RELU)
-            self._nt(ws["vq_a1"], self.P("ans_classifier.2.weight"), ws["vq_logits"], B, NA, 2 * H, bias=self.P("ans_classifier.2.bias"), ldy=ws["NAp"])
-        if pt is not None:
-            # BertPooler (modeling.py:411-417) -- only this branch reads it -- and the pretext loss (:1113-1131)
-            K.gather_rows(x, H, pt["pos0"], pt["sel0"], H, B, 1, L, H, row_off=ro)
-            self._nt(pt["sel0"], self.P("bert.pooler.dense.weight"), pt["pooled"], B, H, H, bias=self.P("bert.pooler.dense.bias"), act=K.ACT_TANH)
-            K.pretext_fwd(ws["vis_h"], ws["vispe_h"], pt["pooled"], st_vmp, pt["probs"], pt["sample"], pt["loss"], B, Nv, st_vmp.shape[1], H)
+        self._fwd_heads(st, x, want_vqa)
         return st
 
     def pretext_loss(self, st):
@@ -1052,134 +1151,77 @@ class Engine(Decoder):
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(idx)
 
-    def _layer_bwd_live(self, i, st, ws, sh, ds, live, R, M, rm, ro, beta, grouped, on_side, use_side, side, ln_slot, scale):
-        """Backward of encoder layer i when only the rows in `live` (device int32 [R], ascending, -1 padded) carry gradient into it: the two
-        LayerNorm backwards, the FFN and attention-output dgrads and their three weight gradients walk the list and read the saved
-        activations in place at row live[m]; the gradients between them are compact [R, *].  Attention backward and the QKV dgrad / wgrad stay
-        dense: they read dctx and the dpre1 residual, which hold exact zeros outside the listed rows."""
-        model = self._model()
-        cfg = model.config
-        H, I, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        B, L, seed = st.B, st.L, st.seed
-        p, pa = st.p_drop
-        Ln = "bert.encoder.layer.%d." % i
-        a, s = ws["layers"][i], sh["layers"][i]
-        x_in = ws["layers"][i - 1]["x2"] if i > 0 else ws["x0"]
-        dx, dctx, dpre1 = ws["dx"], ws["dctx"], ds["dpre1"]      # (dctx and dpre1 were cleared by backward's live_prologue)
-        # BertOutput: dx is read at the listed rows, everything downstream is compact
-        K.layernorm_bwd_rows(dx, a["pre2"], self.P(Ln + "output.LayerNorm.weight"), a["st2"][0], a["st2"][1], ws["lv_dpre2"],
-                             self.G(Ln + "output.LayerNorm.weight"), self.G(Ln + "output.LayerNorm.bias"), live, K.ROWS_X, R, H, ln_slot(2 * i + 1), M,
-                             beta=beta, dx_drop=ws["lv_dpre2_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 3), defer_reduce=True, row_map=rm)
-        dy2 = ws["lv_dpre2_d"] if p > 0 else ws["lv_dpre2"]
-        K.gemm_nt_rows(dy2, s["w2T"], ws["lv_dz"], live, K.ROWS_MUL, R, I, H, mul_src=a["z"], mul_mode=K.MUL_PLAIN)
-        K.gemm_nt_rows(ws["lv_dz"], s["w1T"], ws["lv_dx1"], live, 0, R, H, I, residual=ws["lv_dpre2"])
-        # BertSelfOutput: the undropped dpre1 goes to its rows of the cleared full buffer (residual of the dense QKV dgrad below)
-        K.layernorm_bwd_rows(ws["lv_dx1"], a["pre1"], self.P(Ln + "attention.output.LayerNorm.weight"), a["st1"][0], a["st1"][1], dpre1,
-                             self.G(Ln + "attention.output.LayerNorm.weight"), self.G(Ln + "attention.output.LayerNorm.bias"), live, K.ROWS_Y, R, H,
-                             ln_slot(2 * i), M, beta=beta, dx_drop=ws["lv_dpre1_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 2),
-                             defer_reduce=True, row_map=rm)
-        dy1, dy1_fl = (ws["lv_dpre1_d"], 0) if p > 0 else (dpre1, K.ROWS_X)
-        K.gemm_nt_rows(dy1, s["oT"], dctx, live, dy1_fl | K.ROWS_Y, R, H, H)
-        dqkv = ds["dqkv"]
-        K.attn_bwd(a["qkv"], ws["maskb"], ws["maskt"], a["ctx"], dctx, a["lse"], dqkv, ws["delta"], B, L, A, scale, dropout_p=pa, seed=seed,
-                   rng_stream=16 * i + 1, row_off=ro)
-
-        def last_wgrad():
-            listed = [(dy2, a["g"], self.G(Ln + "output.dense.weight"), R, H, I, beta, self.G(Ln + "output.dense.bias"), live, 0),
-                      (ws["lv_dz"], a["x1"], self.G(Ln + "intermediate.dense.weight"), R, I, H, beta, self.G(Ln + "intermediate.dense.bias"), live, 0),
-                      (dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), R, H, H, beta, self.G(Ln + "attention.output.dense.bias"), live, dy1_fl)]
-            qkv = (dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, beta, self.G(Ln + "attention.self.query.bias"))
-            if grouped:
-                K.gemm_tn_grouped_rows(listed[:2] + [qkv + (None, 0)] + listed[2:])
-            else:
-                K.gemm_tn_grouped_rows(listed)
-                self._tn(*qkv[:6], ws, beta, bias=qkv[7])
-            self._bucket_done(cfg.num_hidden_layers - i)
-            if use_side:
-                ev = torch.cuda.Event()
-                ev.record(side)
-                self._side_done[i & 1] = ev
-        on_side(last_wgrad)
-        self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre1)
-
     def backward(self, st, gscale, task, g_pretext=None, g_rows=None, h_rows=None):
         """gscale: device f32 tensor [1] = upstream gradient of the task loss (x loss scale); g_pretext: the same for the pretext loss of
         a mask_image_regions forward.  task="logprob" (a score_samples forward): g_rows = device f32 [B*T], the upstream gradient of every
         sampled token's log-probability (x loss scale) in place of the masked-LM loss; h_rows (optional, a score_samples(entropy=True)
         forward): the same for every position's entropy.  A forward scored with a temperature or an entropy runs vlp_token_policy_bwd, any
         other vlp_token_logprob_bwd.  Writes every parameter gradient into the flat gradient buffers."""
-        if st.gen != self.gen:
+        c = _Backward(self, st, task)
+        self._bwd_prologue(c)
+        self._bwd_live_rows(c, task)
+        head_wgrads = self._bwd_head(c, task, gscale, g_rows, h_rows)
+        self._bwd_pretext(c, g_pretext)
+        self._bwd_head_wgrads(c, head_wgrads)
+        self._bwd_layers(c)
+        self._bwd_embeddings(c)
+        self._bwd_regions(c)
+        self._bwd_finish(c)
+
+    def _bwd_prologue(self, c):
+        """Refusals, then what every backward starts from: final parameters, this step's W^T shadows, a cleared dx and cleared += tables."""
+        if c.st.gen != self.gen:
             raise RuntimeError("vlp_amd: the activations of this forward were overwritten by a later forward "
                                "(one in-flight forward per model; run backward before the next forward)")
-        model = self._model()
-        cfg = model.config
-        H, I, A, NL, Nv, V = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers, model.len_vis_input, cfg.vocab_size
-        B, L, P, ws, seed = st.B, st.L, st.P, st.ws, st.seed
-        p, pa = st.p_drop
-        M, Mv = B * L, B * Nv
-        ro = rm = None
-        if st.pk is not None:
-            ro, rm, M = st.pk                # packed rows: every [M, *] activation of this step has M' = sum of the kept lengths rows
-        beta = 1 if self.grads_dirty else 0
-        if beta and self.shard_plan is not None:
+        if c.beta and self.shard_plan is not None:
             raise RuntimeError("vlp_amd: VLP_DDP_MODE=sharded keeps only this rank's chunk of the reduced gradient, so gradients cannot be "
                                "accumulated over several backward passes (--gradient_accumulation_steps > 1); use allreduce or rs_ag")
-        img, input_ids, token_type_ids, masked_pos = st.batch
         self.wait_params()           # the optimizer stream has read the previous gradients and written every parameter
         if self._shadow_ev is not None:
             torch.cuda.current_stream().wait_event(self._shadow_ev)     # transposed during the forward (side stream)
             self._shadow_ev = None
         else:
             self._refresh_shadows()
-        sh = self._shadows()
-        x_last = ws["layers"][NL - 1]["x2"]
-        dx = ws["dx"]
-        dx.zero_()
-        E = "bert.embeddings."
-        if beta == 0:
+        c.sh = self._shadows()
+        c.ws["dx"].zero_()
+        if c.beta == 0:
             # tables that are only ever accumulated into (+=) start from zero
-            self.G(E + "position_embeddings.weight").zero_()
-            self.G(E + "token_type_embeddings.weight").zero_()
-
-        main = torch.cuda.current_stream()
-        use_side = self.WGRAD_SIDE_STREAM
-        side = self._side_stream() if use_side else None
-
-        def on_side(fn):
-            if not use_side:
-                fn()
-                return
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                fn()
-
-        if use_side:
+            self.G("bert.embeddings.position_embeddings.weight").zero_()
+            self.G("bert.embeddings.token_type_embeddings.weight").zero_()
+        if c.use_side:
             self._side_busy = True
-        head_wgrads = []        # weight gradients of the task head: issued on the side stream once the head's dgrad chain is on the main stream
 
-        # The gradient that enters the encoder is zero outside the masked rows, and LayerNorm backward and the dgrad GEMMs keep a zero row
-        # zero: until attention mixes rows, the last layer's backward runs over the list of masked rows only (VLP_LAST_LAYER_LIVE=0: over all
-        # rows, as every other layer).  Heads whose gradient reaches other rows (vqa2, pretext, per-token log-probabilities) keep the full path.
-        live = live_ready = None
-        if (task != "vqa2" and task != "logprob" and st.has_mlm and P > 0 and st.pretext is None
+    def _bwd_live_rows(self, c, task):
+        """The gradient that enters the encoder is zero outside the masked rows, and LayerNorm backward and the dgrad GEMMs keep a zero row
+        zero: until attention mixes rows, the last layer's backward runs over the list of masked rows only (VLP_LAST_LAYER_LIVE=0: over all
+        rows, as every other layer).  Heads whose gradient reaches other rows (vqa2, pretext, per-token log-probabilities) keep the full path."""
+        st, ws = c.st, c.ws
+        if (task != "vqa2" and task != "logprob" and st.has_mlm and st.P > 0 and st.pretext is None
                 and os.environ.get("VLP_LAST_LAYER_LIVE", "1") != "0"):
-            live, Rl = ws["lv_rows"], B * P
+            c.live, c.R = ws["lv_rows"], st.B * st.P
 
-            def live_prologue():
+            def prologue():
                 # the list and the two cleared full-size buffers the dense kernels of the last layer read (dctx: attention backward; dpre1: the
                 # residual of the QKV dgrad).  None of it depends on the head's gradient: it runs beside the head chain
-                K.live_rows_build(masked_pos.contiguous(), B, P, L, live, ws["lv_n"], row_off=ro)
-                ws["dctx"][:M].zero_()
-                ws["dyset"][(NL - 1) & 1]["dpre1"][:M].zero_()
-            on_side(live_prologue)
-            if use_side:
-                live_ready = torch.cuda.Event()
-                live_ready.record(side)
-        self._live_n = ws["lv_n"] if live is not None else None
+                K.live_rows_build(st.batch[3].contiguous(), st.B, st.P, st.L, c.live, ws["lv_n"], row_off=c.ro)
+                ws["dctx"][:c.M].zero_()
+                ws["dyset"][(c.NL - 1) & 1]["dpre1"][:c.M].zero_()
+            c.on_side(prologue)
+            if c.use_side:
+                c.live_ready = torch.cuda.Event()
+                c.live_ready.record(c.side)
+        self._live_n = ws["lv_n"] if c.live is not None else None
 
-        # ---- heads ------------------------------------------------------------------------------------
+    def _bwd_head(self, c, task, gscale, g_rows, h_rows):
+        """The task head down to dx (the gradient entering the last encoder layer).  Returns its weight gradients as callables: they are
+        issued on the side stream once the head's dgrad chain and the pretext branch are on the main stream (_bwd_head_wgrads)."""
+        st, ws, sh, beta, ro, H, V, Nv = c.st, c.ws, c.sh, c.beta, c.ro, c.H, c.V, c.Nv
+        B, L, P, masked_pos = st.B, st.L, st.P, st.batch[3]
+        x_last, dx = ws["layers"][c.NL - 1]["x2"], ws["dx"]
+        E, C = "bert.embeddings.", "cls.predictions."
+        head_wgrads = []
         if task == "vqa2":
-            NA, NAp = model.num_answers, ws["NAp"]
+            NA, NAp = self._model().num_answers, ws["NAp"]
             if isinstance(st.task_labels, SparseAnswers):
                 K.bce_sparse_loss_bwd(ws["vq_logits"], NAp, st.task_labels.idx, st.task_labels.score, B, NA, gscale, ws["vq_dlogits"], NAp)
             else:
@@ -1195,9 +1237,8 @@ class Engine(Decoder):
             if beta == 0:                                        # empty masked_pos (modeling.py:1096-1098): only the pretext loss is live
                 self.G(E + "word_embeddings.weight").zero_()
                 for n in ("bias", "transform.dense.weight", "transform.dense.bias", "transform.LayerNorm.weight", "transform.LayerNorm.bias"):
-                    self.G("cls.predictions." + n).zero_()
+                    self.G(C + n).zero_()
         else:
-            C = "cls.predictions."
             R, Vp = B * P, ws["Vp"]
             if task == "logprob":
                 if g_rows is None or g_rows.numel() != R:
@@ -1227,126 +1268,148 @@ class Engine(Decoder):
             head_wgrads.append(lambda: self._tn(ws["dtz"], ws["sel"], self.G(C + "transform.dense.weight"), R, H, H, ws, beta, bias=self.G(C + "transform.dense.bias")))
             self._nt(ws["dtz"], sh["tT"], ws["dsel"], R, H, H)
             K.scatter_add_rows(ws["dsel"], H, masked_pos.contiguous(), dx, H, B, P, L, H, row_off=ro)
-        pt = st.pretext
-        if pt is not None:
-            # vis_pretext_loss backward (modeling.py:1113-1131): masked rows of d_vis_h / d_vispe_h (embed_bwd below leaves them alone),
-            # then the pooler: tanh' is applied by the kernel, dW = d^T . h[:, 0], dh[:, 0] += d . W
-            ptw, vmp = pt
+        return head_wgrads
+
+    def _bwd_pretext(self, c, g_pretext):
+        """vis_pretext_loss backward (modeling.py:1113-1131): masked rows of d_vis_h / d_vispe_h (embed_bwd leaves them alone), then the
+        pooler: tanh' is applied by the kernel, dW = d^T . h[:, 0], dh[:, 0] += d . W.  Without the branch: the pooler's gradient buffer."""
+        st, ws, beta, H, Nv = c.st, c.ws, c.beta, c.H, c.Nv
+        if st.pretext is not None:
+            ptw, vmp = st.pretext
             if g_pretext is None:
                 g_pretext = torch.zeros(1, device=self.device, dtype=torch.float32)
             K.pretext_bwd(ws["vis_h"], ws["vispe_h"], ptw["pooled"], vmp, ptw["probs"], g_pretext, ws["d_vis_h"], ws["d_vispe_h"], ptw["dpool"],
-                          B, Nv, vmp.shape[1], H, drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002)
-            self._tn(ptw["dpool"], ptw["sel0"], self.G("bert.pooler.dense.weight"), B, H, H, ws, beta, bias=self.G("bert.pooler.dense.bias"))
+                          st.B, Nv, vmp.shape[1], H, drop_p=c.p, seed=c.seed, vis_stream=1001, vispe_stream=1002)
+            self._tn(ptw["dpool"], ptw["sel0"], self.G("bert.pooler.dense.weight"), st.B, H, H, ws, beta, bias=self.G("bert.pooler.dense.bias"))
             K.transpose(self.P("bert.pooler.dense.weight"), H, ptw["pT"], H, H, H, H)
-            self._nt(ptw["dpool"], ptw["pT"], ptw["dsel0"], B, H, H)
-            K.scatter_add_rows(ptw["dsel0"], H, ptw["pos0"], dx, H, B, 1, L, H, row_off=ro)
+            self._nt(ptw["dpool"], ptw["pT"], ptw["dsel0"], st.B, H, H)
+            K.scatter_add_rows(ptw["dsel0"], H, ptw["pos0"], ws["dx"], H, st.B, 1, st.L, H, row_off=c.ro)
             self._pooler_dirty = True
         elif beta == 0 and self._pooler_dirty:
             self.G("bert.pooler.dense.weight").zero_()           # a previous pretext step left gradients there; unused now
             self.G("bert.pooler.dense.bias").zero_()
             self._pooler_dirty = False                           # (an accumulating backward without the branch leaves buffer and flag as they are)
 
-        def head_tail():
+    def _bwd_head_wgrads(self, c, head_wgrads):
+        """The head's deferred weight gradients on the side stream, then the hand-off of the head's gradient slice."""
+        def tail():
             for fn in head_wgrads:
                 fn()
             self._bucket_done(0)
-        on_side(head_tail)          # (the side stream is ordered behind everything the main stream has issued so far)
+        c.on_side(tail)          # (the side stream is ordered behind everything the main stream has issued so far)
 
-        # ---- encoder layers, last to first ----------------------------------------------------------------
-        # The dgrad chain (LN-bwd -> dgrad GEMMs -> attention-bwd) is the critical path; the four weight-gradient GEMMs of a
-        # layer only consume its dY tensors.  They are issued on a side stream (ordered after their producers by
-        # wait_stream) so that they co-run with the next kernels of the chain; dY buffers alternate by layer parity and the
-        # main stream waits for the side stream's event before it reuses a set.
-        dctx = ws["dctx"]
-        scale = 1.0 / math.sqrt(H // A)
-        slot_bytes = ws["ln_slot_bytes"]
-
-        def ln_slot(k):
-            return ws["ln_slots"][k * slot_bytes:(k + 1) * slot_bytes]
-
-        # one vlp_gemm_tn_grouped launch per layer instead of 4 split-M wgrads + 4 reduces where there are enough rows for a long contraction
-        # per workgroup; tiny batches keep split-M
-        grouped = M >= 2048
-        # the forward's map of kept rows (dense training steps only; never a score_samples forward); VLP_WGRAD_KEPT=0 read per call
-        kept = st.kept if (grouped and st.pk is None and task != "logprob" and os.environ.get("VLP_WGRAD_KEPT", "1") != "0") else None
-        self.last_wgrad_mapped = kept is not None
-        for i in reversed(range(NL)):
-            Ln = "bert.encoder.layer.%d." % i
-            a = ws["layers"][i]
-            s = sh["layers"][i]
-            x_in = ws["layers"][i - 1]["x2"] if i > 0 else ws["x0"]
-            ds = ws["dyset"][i & 1]
-            if use_side and self._side_done[i & 1] is not None:
-                main.wait_event(self._side_done[i & 1])       # wgrads of layer i+2 have finished reading this set
-            if live is not None and i == NL - 1:
-                if live_ready is not None:
-                    main.wait_event(live_ready)
-                self._layer_bwd_live(i, st, ws, sh, ds, live, Rl, M, rm, ro, beta, grouped, on_side, use_side, side, ln_slot, scale)
-                continue
-            # BertOutput: LN(dropout(dense(g)) + x1)   (modeling.py:353-357)
-            dpre = ds["dpre2"]
-            K.layernorm_bwd(dx, a["pre2"], self.P(Ln + "output.LayerNorm.weight"), a["st2"][0], a["st2"][1], dpre,
-                            self.G(Ln + "output.LayerNorm.weight"), self.G(Ln + "output.LayerNorm.bias"), M, H, ln_slot(2 * i + 1), beta=beta,
-                            dx_drop=ds["dpre2_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 3), defer_reduce=True, row_map=rm)
-            dy2 = ds["dpre2_d"] if p > 0 else dpre
-            if not grouped:
-                on_side(lambda: self._tn(dy2, a["g"], self.G(Ln + "output.dense.weight"), M, H, I, ws, beta, bias=self.G(Ln + "output.dense.bias")))
-            self._nt(dy2, s["w2T"], ds["dz"], M, I, H, mul_src=a["z"], mul_mode=K.MUL_PLAIN)      # dG * gelu'(z) (stored by the forward)
-            # BertIntermediate (modeling.py:340-343)
-            if not grouped:
-                on_side(lambda: self._tn(ds["dz"], a["x1"], self.G(Ln + "intermediate.dense.weight"), M, I, H, ws, beta,
-                                         bias=self.G(Ln + "intermediate.dense.bias")))
-            self._nt(ds["dz"], s["w1T"], dx, M, H, I, residual=dpre)                            # + residual path of LN2's input
-            # BertSelfOutput: LN(dropout(dense(ctx)) + x)   (modeling.py:313-317)
-            dpre = ds["dpre1"]
-            K.layernorm_bwd(dx, a["pre1"], self.P(Ln + "attention.output.LayerNorm.weight"), a["st1"][0], a["st1"][1], dpre,
-                            self.G(Ln + "attention.output.LayerNorm.weight"), self.G(Ln + "attention.output.LayerNorm.bias"), M, H, ln_slot(2 * i),
-                            beta=beta, dx_drop=ds["dpre1_d"] if p > 0 else None, out_drop=(p, seed, 16 * i + 2), defer_reduce=True, row_map=rm)
-            dy1 = ds["dpre1_d"] if p > 0 else dpre
-            if not grouped:
-                on_side(lambda: self._tn(dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), M, H, H, ws, beta,
-                                         bias=self.G(Ln + "attention.output.dense.bias")))
-            self._nt(dy1, s["oT"], dctx, M, H, H)
-            # BertSelfAttention (modeling.py:268-303)
-            dqkv = ds["dqkv"]
-            K.attn_bwd(a["qkv"], ws["maskb"], ws["maskt"], a["ctx"], dctx, a["lse"], dqkv, ws["delta"], B, L, A, scale, dropout_p=pa, seed=seed,
-                       rng_stream=16 * i + 1, row_off=ro)
-
-            def last_wgrad():
-                if grouped:
-                    # the layer's four weight gradients (+ bias gradients) as ONE grid of 36 + 108 + 144 + 144 output tiles, every
-                    # workgroup walking the whole contraction: no split-M slabs, no reduce launches (csrc/gemm_tn.hip)
-                    problems = [
-                        (dy2, a["g"], self.G(Ln + "output.dense.weight"), M, H, I, beta, self.G(Ln + "output.dense.bias")),
-                        (ds["dz"], a["x1"], self.G(Ln + "intermediate.dense.weight"), M, I, H, beta, self.G(Ln + "intermediate.dense.bias")),
-                        (dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, beta, self.G(Ln + "attention.self.query.bias")),
-                        (dy1, a["ctx"], self.G(Ln + "attention.output.dense.weight"), M, H, H, beta, self.G(Ln + "attention.output.dense.bias"))]
-                    if kept is not None:
-                        # dense step: rows past a sample's kept length have dY == 0 in all four problems; the walk skips them (device map)
-                        K.gemm_tn_grouped_mapped(problems, kept[0], kept[1])
-                    else:
-                        K.gemm_tn_grouped(problems)
-                else:
-                    self._tn(dqkv, x_in, self.G(Ln + "attention.self.query.weight"), M, 3 * H, H, ws, beta,
-                             bias=self.G(Ln + "attention.self.query.bias"))     # packed [3H, H] gradient
-                self._bucket_done(NL - i)          # the layer's gradient slice is complete in this stream's order
-                if use_side:
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    self._side_done[i & 1] = ev
-            on_side(last_wgrad)
-            self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre)
-        if use_side and not grouped:
-            main.wait_stream(side)          # all layer wgrads (and their bucket hand-offs) precede the rest of backward (split-M wgrads share tn_ws)
+    def _bwd_layers(self, c):
+        """Encoder layers, last to first.  The dgrad chain (LN-bwd -> dgrad GEMMs -> attention-bwd) is the critical path; the four
+        weight-gradient GEMMs of a layer only consume its dY tensors.  They are issued on a side stream (ordered after their producers by
+        wait_stream) so that they co-run with the next kernels of the chain; dY buffers alternate by layer parity and the main stream waits
+        for the side stream's event before it reuses a set."""
+        self.last_wgrad_mapped = c.kept is not None
+        for i in reversed(range(c.NL)):
+            if c.use_side and self._side_done[i & 1] is not None:
+                c.main.wait_event(self._side_done[i & 1])       # wgrads of layer i+2 have finished reading this set
+            listed = c.live is not None and i == c.NL - 1
+            if listed and c.live_ready is not None:
+                c.main.wait_event(c.live_ready)
+            self._bwd_layer(c, i, listed)
+        if c.use_side and not c.grouped:
+            c.main.wait_stream(c.side)      # all layer wgrads (and their bucket hand-offs) precede the rest of backward (split-M wgrads share tn_ws)
             self._side_busy = False
         # (grouped wgrads: the main stream does NOT wait here -- layer 0's weight gradients (170 us, issued a moment ago) and the
-        # embedding tables run on the side stream underneath the embedding / region-projection backward below, which touches none of their
+        # embedding tables run on the side stream underneath the embedding / region-projection backward, which touches none of their
         # operands; the streams join once, at the end of backward)
-        dpre = ws["dpre"]
 
-        # ---- embeddings -------------------------------------------------------------------------------------
-        K.layernorm_bwd(dx, ws["emb_pre"], self.P(E + "LayerNorm.weight"), ws["stat0"][0], ws["stat0"][1], dpre,
-                        self.G(E + "LayerNorm.weight"), self.G(E + "LayerNorm.bias"), M, H, ln_slot(2 * NL), beta=beta, dy_drop=(p, seed, 1000),
+    def _bwd_layer(self, c, i, listed):
+        """Backward of encoder layer i (modeling.py:268-372, bottom up).  listed: only the rows in c.live (device int32 [R], ascending, -1
+        padded) carry gradient into it -- the two LayerNorm backwards, the FFN and attention-output dgrads and their three weight gradients
+        walk the list and read the saved activations in place at row live[m]; the gradients between them are compact [R, *].  Attention
+        backward and the QKV dgrad / wgrad stay dense either way: with a list they read dctx and the dpre1 residual, which hold exact zeros
+        outside the listed rows (cleared by _bwd_live_rows)."""
+        st, ws, beta, M, p, H, I = c.st, c.ws, c.beta, c.M, c.p, c.H, c.I
+        a, s, (w, g), ds = ws["layers"][i], c.sh["layers"][i], self._layers()[i], ws["dyset"][i & 1]
+        x_in = ws["layers"][i - 1]["x2"] if i > 0 else ws["x0"]
+        dx, dctx, dpre1, dqkv = ws["dx"], ws["dctx"], ds["dpre1"], ds["dqkv"]
+        # the gradients between the kernels: compact [R, *] beside the list, else the dY set's [M, *] (dx1, the gradient of x1: dx itself)
+        if listed:
+            live, R = c.live, c.R
+            dpre2, dpre2_d, dz, dx1, dpre1_d = ws["lv_dpre2"], ws["lv_dpre2_d"], ws["lv_dz"], ws["lv_dx1"], ws["lv_dpre1_d"]
+        else:
+            live, R = None, M
+            dpre2, dpre2_d, dz, dx1, dpre1_d = ds["dpre2"], ds["dpre2_d"], ds["dz"], dx, ds["dpre1_d"]
+        dy2 = dpre2_d if p > 0 else dpre2
+        # (dy1 of a list without dropout is the undropped dpre1 at its rows of the cleared full buffer: addressed through the list)
+        dy1, dy1_fl = (dpre1_d, 0) if p > 0 else (dpre1, K.ROWS_X)
+        # the layer's four weight gradients (dY, X, dW, rows, N, K, beta, dbias); the packed [3H, H] QKV gradient is always dense
+        wg = [(dy2, a["g"], g.fc2_w, R, H, I, beta, g.fc2_b),
+              (dz, a["x1"], g.fc1_w, R, I, H, beta, g.fc1_b),
+              (dqkv, x_in, g.qkv_w, M, 3 * H, H, beta, g.qkv_b),
+              (dy1, a["ctx"], g.o_w, R, H, H, beta, g.o_b)]
+        split = not c.grouped and not listed       # split-M launches, each right behind the kernel that wrote its dY
+
+        def tn(t):
+            self._tn(*t[:6], ws, t[6], bias=t[7])
+        # BertOutput: LN(dropout(dense(g)) + x1) (modeling.py:353-357); dG * gelu'(z) (stored by the forward); BertIntermediate (:340-343)
+        # + the residual path of LN2's input; BertSelfOutput: LN(dropout(dense(ctx)) + x) (:313-317)
+        ln2 = dict(dx_drop=dpre2_d if p > 0 else None, out_drop=(p, c.seed, 16 * i + 3), beta=beta, defer_reduce=True, row_map=c.rm)
+        ln1 = dict(dx_drop=dpre1_d if p > 0 else None, out_drop=(p, c.seed, 16 * i + 2), beta=beta, defer_reduce=True, row_map=c.rm)
+        if listed:
+            K.layernorm_bwd_rows(dx, a["pre2"], w.ln2_w, *a["st2"], dpre2, g.ln2_w, g.ln2_b, live, K.ROWS_X, R, H, c.ln_slot(2 * i + 1), M, **ln2)
+            K.gemm_nt_rows(dy2, s["w2T"], dz, live, K.ROWS_MUL, R, I, H, mul_src=a["z"], mul_mode=K.MUL_PLAIN)
+            K.gemm_nt_rows(dz, s["w1T"], dx1, live, 0, R, H, I, residual=dpre2)
+            K.layernorm_bwd_rows(dx1, a["pre1"], w.ln1_w, *a["st1"], dpre1, g.ln1_w, g.ln1_b, live, K.ROWS_Y, R, H, c.ln_slot(2 * i), M, **ln1)
+            K.gemm_nt_rows(dy1, s["oT"], dctx, live, dy1_fl | K.ROWS_Y, R, H, H)
+        else:
+            K.layernorm_bwd(dx, a["pre2"], w.ln2_w, *a["st2"], dpre2, g.ln2_w, g.ln2_b, M, H, c.ln_slot(2 * i + 1), **ln2)
+            if split:
+                c.on_side(lambda: tn(wg[0]))
+            self._nt(dy2, s["w2T"], dz, M, I, H, mul_src=a["z"], mul_mode=K.MUL_PLAIN)
+            if split:
+                c.on_side(lambda: tn(wg[1]))
+            self._nt(dz, s["w1T"], dx1, M, H, I, residual=dpre2)
+            K.layernorm_bwd(dx1, a["pre1"], w.ln1_w, *a["st1"], dpre1, g.ln1_w, g.ln1_b, M, H, c.ln_slot(2 * i), **ln1)
+            if split:
+                c.on_side(lambda: tn(wg[3]))
+            self._nt(dy1, s["oT"], dctx, M, H, H)
+        # BertSelfAttention (modeling.py:268-303)
+        K.attn_bwd(a["qkv"], ws["maskb"], ws["maskt"], a["ctx"], dctx, a["lse"], dqkv, ws["delta"], st.B, st.L, c.A, c.scale, dropout_p=c.pa,
+                   seed=c.seed, rng_stream=16 * i + 1, row_off=c.ro)
+
+        def wgrads():           # what is left of the layer's weight gradients, behind its attention backward
+            if listed:
+                # three walks of the list and the dense QKV problem (in one launch with enough rows, QKV third as in every grouped launch)
+                rows = [wg[0] + (live, 0), wg[1] + (live, 0), wg[3] + (live, dy1_fl)]
+                K.gemm_tn_grouped_rows(rows[:2] + [wg[2] + (None, 0)] + rows[2:] if c.grouped else rows)
+            elif c.kept is not None:
+                # dense step: rows past a sample's kept length have dY == 0 in all four problems; the walk skips them (device map)
+                K.gemm_tn_grouped_mapped(wg, c.kept[0], c.kept[1])
+            elif c.grouped:
+                # ONE grid of 36 + 108 + 144 + 144 output tiles, every workgroup walking the whole contraction: no split-M slabs, no
+                # reduce launches (csrc/gemm_tn.hip)
+                K.gemm_tn_grouped(wg)
+            if not c.grouped:
+                tn(wg[2])       # split-M (the other three: in the listed launch above, or issued beside the dgrads)
+            c.wgrads_issued(i)
+        c.on_side(wgrads)
+        self._nt(dqkv, s["qkvT"], dx, M, H, 3 * H, residual=dpre1)
+
+    def _embed_bwd(self, c, dpre, parts):
+        """parts = 1: the region rows (d_vis_h / d_vispe_h; they do not depend on position ids), 2: the three embedding tables."""
+        st, ws, E = c.st, c.ws, "bert.embeddings."
+        pt, (_, input_ids, token_type_ids, _) = st.pretext, st.batch
+        args = (ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"), self.G(E + "position_embeddings.weight"),
+                self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"], ws["acc32"], st.B, st.L, c.Nv,
+                c.H, c.V, self._model().config.type_vocab_size)
+        kw = dict(drop_p=c.p, seed=c.seed, vis_stream=1001, vispe_stream=1002, region_mask=pt[0]["rmask"] if pt is not None else None, parts=parts)
+        if parts == 2 and st.pos_ids is not None:       # explicit position ids (score_samples): the position table follows them
+            K.embed_bwd_pos(dpre, input_ids, token_type_ids, st.pos_ids, *args, **kw)
+        else:
+            K.embed_bwd(dpre, input_ids, token_type_ids, *args, **kw)
+
+    def _bwd_embeddings(self, c):
+        """Embedding LayerNorm and the region rows on the main stream; the tables and every LayerNorm's parameter sums on the side stream."""
+        ws, beta, M, rm, NL, H, E = c.ws, c.beta, c.M, c.rm, c.NL, c.H, "bert.embeddings."
+        dpre = ws["dpre"]
+        K.layernorm_bwd(ws["dx"], ws["emb_pre"], self.P(E + "LayerNorm.weight"), ws["stat0"][0], ws["stat0"][1], dpre,
+                        self.G(E + "LayerNorm.weight"), self.G(E + "LayerNorm.bias"), M, H, c.ln_slot(2 * NL), beta=beta, dy_drop=(c.p, c.seed, 1000),
                         defer_reduce=True, row_map=rm)
         if rm is not None:
             # the embedding backward sums over (batch, position) in the dense [B, L] geometry (position table: a column of the batch;
@@ -1356,55 +1419,50 @@ class Engine(Decoder):
             K.rows_unpack(dpre, rm, M, dense, H)
             dpre = dense
 
-        def embed_bwd(parts):
-            """parts = 1: the region rows (d_vis_h / d_vispe_h; they do not depend on position ids), 2: the three embedding tables."""
-            args = (ws["vis_h"], ws["vispe_h"], self.G(E + "word_embeddings.weight"), self.G(E + "position_embeddings.weight"),
-                    self.G(E + "token_type_embeddings.weight"), ws["d_vis_h"], ws["d_vispe_h"], ws["acc32"], B, L, Nv, H, V, cfg.type_vocab_size)
-            kw = dict(drop_p=p, seed=seed, vis_stream=1001, vispe_stream=1002, region_mask=pt[0]["rmask"] if pt is not None else None, parts=parts)
-            if parts == 2 and st.pos_ids is not None:       # explicit position ids (score_samples): the position table follows them
-                K.embed_bwd_pos(dpre, input_ids, token_type_ids, st.pos_ids, *args, **kw)
-            else:
-                K.embed_bwd(dpre, input_ids, token_type_ids, *args, **kw)
-
         def tables_and_ln_params():
             # the tail of backward that nothing on the main stream waits for: dgamma / dbeta of the 2 * layers + 1 LayerNorms (one launch,
             # slot order = table order) and the three embedding tables (five launches); their gradient slice is announced from here
             K.layernorm_bwd_reduce_batched(ws["ln_slots"], self._ln_table(), 2 * NL + 1, M, H, beta=beta)
-            embed_bwd(2)
+            self._embed_bwd(c, dpre, 2)
             self._bucket_done(NL + 1)           # position / type / word embedding tables (tied decoder wgrad + embedding backward) are final
 
-        # region rows first (the region-projection dgrad / wgrads below wait for d_vis_h / d_vispe_h only); the tables and the LayerNorm
+        # region rows first (the region-projection dgrad / wgrads wait for d_vis_h / d_vispe_h only); the tables and the LayerNorm
         # parameter sums run on the side stream underneath them (round 5: six small launches, ~140 us, off the critical path)
-        embed_bwd(1)
-        if use_side:
+        self._embed_bwd(c, dpre, 1)
+        if c.use_side:
             self._side_busy = True
-        on_side(tables_and_ln_params)
-        # vis_pe_embed: Linear(1607, H) -- wgrad into the padded shadow, then crop-accumulate
-        # vis_embed: Linear(2048,2048)+ReLU -> Linear(2048,H)+ReLU+Dropout
-        self._nt(ws["d_vis_h"], sh["v2T"], ws["dz1v"], Mv, 2048, H, mul_src=ws["h1"], mul_mode=K.MUL_RELU_MASK)
-        if grouped and Mv >= 2048:
+        c.on_side(tables_and_ln_params)
+
+    def _bwd_regions(self, c):
+        """Region projections.  vis_pe_embed: Linear(1607, H) -- wgrad into the padded shadow, then crop-accumulate; vis_embed:
+        Linear(2048,2048)+ReLU -> Linear(2048,H)+ReLU+Dropout."""
+        ws, beta, Mv, H, img = c.ws, c.beta, c.Mv, c.H, c.st.batch[0]
+        self._nt(ws["d_vis_h"], c.sh["v2T"], ws["dz1v"], Mv, 2048, H, mul_src=ws["h1"], mul_mode=K.MUL_RELU_MASK)
+        if c.grouped and Mv >= 2048:
             # the three region-projection wgrads (78 + 96 + 256 output tiles, contraction over B x 100 region rows) as one grouped launch
             K.gemm_tn_grouped([
                 (ws["dz1v"], img, self.G("vis_embed.0.weight"), Mv, 2048, 2048, beta, self.G("vis_embed.0.bias")),
                 (ws["d_vis_h"], ws["h1"], self.G("vis_embed.2.weight"), Mv, H, 2048, beta, self.G("vis_embed.2.bias")),
                 (ws["d_vispe_h"], ws["vpe_in"], ws["dwpe_pad"], Mv, H, PE_PAD, 0, None)])
         else:
-            if use_side and self._side_busy:
+            if c.use_side and self._side_busy:
                 # these split-M launches use ws["tn_ws"] on the MAIN stream; the head wgrads deferred to the side stream use the same scratch and
                 # with <= 2 layers no per-layer wait orders the two (ADVICE r5): join first (small batches only -- Mv < 2048)
-                main.wait_stream(side)
+                c.main.wait_stream(c.side)
             self._tn(ws["d_vispe_h"], ws["vpe_in"], ws["dwpe_pad"], Mv, H, PE_PAD, ws, 0)
             self._tn(ws["d_vis_h"], ws["h1"], self.G("vis_embed.2.weight"), Mv, H, 2048, ws, beta, bias=self.G("vis_embed.2.bias"))
             self._tn(ws["dz1v"], img, self.G("vis_embed.0.weight"), Mv, 2048, 2048, ws, beta, bias=self.G("vis_embed.0.bias"))
         K.copy2d(ws["dwpe_pad"], PE_PAD, False, self.G("vis_pe_embed.0.weight"), PE_DIM, H, PE_DIM, PE_DIM, beta=beta)
         K.colsum(ws["d_vispe_h"], self.G("vis_pe_embed.0.bias"), Mv, H, beta=beta, workspace=ws["cs_ws"])
-        if use_side and self._side_busy:
+
+    def _bwd_finish(self, c):
+        """Join the streams, hand off the last gradient slice, mark the gradients as written."""
+        if c.use_side and self._side_busy:
             # the streams join HERE, in front of the last hand-off: a reducer may coalesce the embedding tables (written on the side stream)
             # with the region projections into one bucket, and that bucket's collective is ordered behind the stream that announces it
-            main.wait_stream(side)
+            c.main.wait_stream(c.side)
             self._side_busy = False
-        self._bucket_done(NL + 2)
+        self._bucket_done(c.NL + 2)
         self.grads_dirty = True
         if self.post_backward_hook is not None:
             self.post_backward_hook()
-
