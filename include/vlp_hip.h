@@ -49,6 +49,8 @@ extern "C" {
  * they take the existing argument structs plus the row list as separate arguments, so no struct grew: purely additive as well. */
 /* + vlp_beam_select_groups (diverse beam search: the selection step with the beams in groups): it takes vlp_beam_select_args as it is plus two
  * scalars; purely additive as well. */
+/* + vlp_logsoftmax_topk_want, vlp_beam_select_constrained (constrained beam search): the existing arguments plus separate ones, no struct grew;
+ * purely additive as well. */
 /* + vlp_kept_rows_build, vlp_gemm_tn_grouped_mapped (the dense step's grouped wgrad over a device map of the kept rows): they take
  * vlp_gemm_tn_args as it is plus the map and its device count; purely additive as well. */
 /* + vlp_token_score (log-probability, entropy, rank and arg-max of a given token per logits row: scoring given captions) and its argument
@@ -619,6 +621,33 @@ int vlp_beam_select(const vlp_beam_select_args* a, void* stream);
  * bit-equal outputs.  VLP_ERR_BAD_ARG before any launch: a null operand, B <= 0, K outside 1..64, groups < 1, K % groups != 0, a penalty that
  * is NaN, negative or infinite, first == 0 without last_total / last_eos. */
 int vlp_beam_select_groups(const vlp_beam_select_args* a, int32_t groups, float penalty, void* stream);
+/* Constrained beam search (Anderson et al. 2017, Post & Vilar 2018; not in the reference): captions that must mention given phrases.
+ *   vlp_logsoftmax_topk_want: vlp_logsoftmax_topk (forbid, or neither) / vlp_logsoftmax_topk_list (cand_ids, cand_ld, cand_cnt) -- the two
+ *       forms exclude each other -- on the same kernel bodies, dispatch and lse, so out_scores / out_ids are theirs bit for bit; in addition
+ *       want_val[r, c] (f32 [rows, C]) = the value that kernel body computes for word want_ids[r, c] (int32 [rows, C], 1 <= C <= 8):
+ *       (float)x[w] - lse, + -10000 when forbidden by mask or list, -10000 when it is the blocked eos; -inf for an id of -1 (or outside
+ *       [0, V)).  A wanted word that is in the row's list carries the list's bits.  A few gathers behind the lse, no second walk.
+ *   vlp_beam_select_constrained: the selection step.  cons_ids int32 [B, C, Lc] / cons_len int32 [B, C] (0: unused) are the phrases of every
+ *       sample; a beam's state is one int32 (bits 0-7 met mask, 8-11 phrase in progress + 1, 16-23 tokens of it matched); prev_state
+ *       [B, K] (NULL in the first step).  Row r of a sample offers K + C candidates, index i = r*(K+C) + j: its top-K list (j < K) and its
+ *       wanted words want_ids / want_val [rows, C] (absent: -1, a list id of the row, an earlier wanted id of the row).  v0 is
+ *       vlp_beam_select's value; an eos of a live parent that leaves a phrase unmet gets + -10000 and is dead, as every candidate of an
+ *       ended parent is; with `last` != 0 (the search's last step, which ends every hypothesis) every candidate of a live parent that leaves
+ *       a phrase unmet is treated so, whatever its word.  K picks walk the banks (bank = matched tokens, met phrases included) from
+ *       Tb = sum of cons_len downwards, wrapping, skipping banks without a live candidate, each the best (v0 descending, i ascending, NaN as -inf) live candidate of its bank; dead
+ *       candidates follow when no live one is left.  The six outputs of vlp_beam_select keep their meaning; out_state int32 [B, K] and
+ *       want_next int32 [B*K, C] (the next step's want_ids: per phrase its next token, -1 when met / unused / the beam has ended) are
+ *       added.  With every cons_len == 0 the picks are vlp_beam_select's whenever live candidates outrank dead ones (any search).  The rule
+ *       in full, as a numpy specification: vlp_amd/constrained.py.
+ *       One launch (one wave per sample, <= 64 * 72 candidates in LDS), no synchronisation, capturable; equal inputs give equal bits.
+ *       VLP_ERR_BAD_ARG before any launch: a null operand, B <= 0, K outside 1..64, C outside 1..8, Lc outside 1..8, first == 0 without
+ *       last_total / last_eos / prev_state. */
+int vlp_logsoftmax_topk_want(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t K, const uint8_t* forbid, const int32_t* cand_ids,
+                             int64_t cand_ld, const int32_t* cand_cnt, int32_t eos_id, int32_t block_eos, const int32_t* want_ids, int32_t C,
+                             float* out_scores, int64_t* out_ids, float* want_val, void* stream);
+int vlp_beam_select_constrained(const vlp_beam_select_args* a, const int32_t* want_ids, const float* want_val, const int32_t* prev_state,
+                                const int32_t* cons_ids, const int32_t* cons_len, int32_t C, int32_t Lc, int32_t last, int32_t* out_state,
+                                int32_t* want_next, void* stream);
 /* Duplicate n-gram blocking on the device (get_dup_ngram_candidates, modeling.py:1391-1406), for a search that never leaves the GPU:
  *   vlp_ngram_candidates: wids / ptrs are the frames [frames, B, K] that vlp_beam_select writes (int64, contiguous).  Row r = b*K + k:
  *       the hypothesis that ends in beam k of frame s is rebuilt by following ptrs back from frame s (length s + 1 <= 256); the words that

@@ -245,6 +245,8 @@ SYMBOLS = {
     "vlp_logsoftmax_topk": (C.c_int, [vp, i64, i32, i32, i32, vp, i32, i32, vp, vp, vp]),
     "vlp_beam_select": (C.c_int, [C.POINTER(BeamSelectArgs), vp]),
     "vlp_beam_select_groups": (C.c_int, [C.POINTER(BeamSelectArgs), i32, C.c_float, vp]),
+    "vlp_beam_select_constrained": (C.c_int, [C.POINTER(BeamSelectArgs), vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "vlp_logsoftmax_topk_want": (C.c_int, [vp, i64, i32, i32, i32, vp, vp, i64, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "vlp_ngram_candidates": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i64, vp, vp]),
     "vlp_logsoftmax_topk_list": (C.c_int, [vp, i64, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     "vlp_kv_gather": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]),
@@ -651,6 +653,38 @@ def beam_select_groups(kk_scores, kk_ids, last_total, last_eos, out_scores, out_
     a = BeamSelectArgs(ptr(kk_scores), ptr(kk_ids), ptr(last_total), ptr(last_eos), ptr(out_scores), ptr(out_ids), ptr(out_ptrs), ptr(out_eos),
                        ptr(src_rows), ptr(next_ids), next_ids.stride(0) if next_ids is not None else 0, B, K, 1 if first else 0, eos_id)
     _check(load().vlp_beam_select_groups(C.byref(a), int(groups), float(penalty), stream_ptr()))
+
+
+def logsoftmax_topk_want(logits, ld, rows, V, K, out_scores, out_ids, want_ids, want_val, forbid=None, cand_ids=None, cand_cnt=None, eos_id=0,
+                         block_eos=False):
+    """logsoftmax_topk (dense `forbid` or none) or logsoftmax_topk_list (`cand_ids` / `cand_cnt`) -- same kernels, same top-K bits -- that also
+    writes want_val[r, c] f32 = row r's value of word want_ids[r, c] (int32 [rows, C], C <= 8; -1 gives -inf)."""
+    _req_cuda(logits, out_scores, out_ids, want_ids, want_val, forbid, cand_ids, cand_cnt)
+    assert want_ids.dtype == torch.int32 and want_val.dtype == torch.float32 and want_ids.is_contiguous() and want_val.is_contiguous()
+    assert want_ids.dim() == 2 and want_ids.shape[0] >= rows and tuple(want_val.shape) == tuple(want_ids.shape)
+    cand_ld = 0
+    if cand_ids is not None:
+        assert cand_ids.dtype == torch.int32 and cand_cnt.dtype == torch.int32 and cand_ids.stride(1) == 1 and cand_cnt.is_contiguous()
+        assert cand_ids.shape[0] >= rows and cand_cnt.numel() >= rows
+        cand_ld = cand_ids.stride(0)
+    _check(load().vlp_logsoftmax_topk_want(ptr(logits), ld, rows, V, K, ptr(forbid), ptr(cand_ids), cand_ld, ptr(cand_cnt), eos_id,
+                                           1 if block_eos else 0, ptr(want_ids), want_ids.shape[1], ptr(out_scores), ptr(out_ids), ptr(want_val),
+                                           stream_ptr()))
+
+
+def beam_select_constrained(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, out_ptrs, out_eos, src_rows, next_ids, B, K, first, eos_id,
+                            want_ids, want_val, prev_state, cons_ids, cons_len, C_, Lc, out_state, want_next, last=False):
+    """beam_select under lexical constraints (vlp_amd.constrained is the rule): int32 want_ids / f32 want_val [rows, C], prev_state [B, K] (None
+    on the first frame), cons_ids [B, C, Lc], cons_len [B, C], out_state [B, K], want_next [B*K, C]; all contiguous.  last: the search's last frame."""
+    _req_cuda(kk_scores, kk_ids, last_total, last_eos, out_scores, out_ids, out_ptrs, out_eos, src_rows, next_ids, want_ids, want_val, prev_state,
+              cons_ids, cons_len, out_state, want_next)
+    for t in (want_ids, prev_state, cons_ids, cons_len, out_state, want_next):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous())
+    assert want_val is None or (want_val.dtype == torch.float32 and want_val.is_contiguous())
+    a = BeamSelectArgs(ptr(kk_scores), ptr(kk_ids), ptr(last_total), ptr(last_eos), ptr(out_scores), ptr(out_ids), ptr(out_ptrs), ptr(out_eos),
+                       ptr(src_rows), ptr(next_ids), next_ids.stride(0) if next_ids is not None else 0, B, K, 1 if first else 0, eos_id)
+    _check(load().vlp_beam_select_constrained(C.byref(a), ptr(want_ids), ptr(want_val), ptr(prev_state), ptr(cons_ids), ptr(cons_len), int(C_), int(Lc),
+                                              1 if last else 0, ptr(out_state), ptr(want_next), stream_ptr()))
 
 
 def kv_gather(src, src_rows, dst, dst_rows, idx, R, lo, hi, row_elems):

@@ -879,12 +879,35 @@ DEVFN bool topk_list_has(const int* lst, int n, int v) {
     for (int j = 0; j < n; ++j) hit |= lst[j] == v;
     return hit;
 }
+// WANT (vlp_logsoftmax_topk_want, constrained beam search): besides the K best, the row's value of up to 8 given words, want_val[row, c] for
+// word want_ids[row, c]: the expression a list entry goes through, on the kernel's own lse (the two kernels sum in different orders), so a
+// wanted word that is also in the list carries the list's bits.  -1 (or an id outside [0, V)) gives -inf.  A few gathers behind the lse,
+// no second walk over the row.  The kernels take it as a trailing parameter pack W: empty for the existing entry points, whose kernels keep
+// their bodies and their argument lists, and one TopkWant for vlp_logsoftmax_topk_want.
+struct TopkWant { const int32_t* ids; float* val; int C; };
+template <bool LIST>
+DEVFN void topk_want_store(const TopkWant& tw, int row, int tid, const f16* x, int V, float lse, const uint8_t* fb, const int* lst, int ncand,
+                           int eos_id, int block_eos) {
+    if (tid >= tw.C) return;
+    const int w = tw.ids[(int64_t)row * tw.C + tid];
+    float val = -INFINITY;
+    if (w >= 0 && w < V) {
+        val = (float)x[w] - lse;
+        if (fb && fb[w]) val += -10000.0f;
+        const bool is_eos = block_eos && w == eos_id;
+        if (is_eos) val = -10000.0f;
+        if constexpr (LIST) {
+            if (!is_eos && topk_list_has(lst, ncand, w)) val += -10000.0f;
+        }
+    }
+    tw.val[(int64_t)row * tw.C + tid] = val;
+}
 // (This kernel keeps its hand-written passes and LDS trees: on row_visit / block_reduce_max / argmax_block256 its loops compile to the same
 // instructions, yet a launch at 64 rows, K = 17 measured 486 us against 470 us -- and 467 us with the reduction words moved in LDS: a
 // code-placement effect that is not understood.  profiles/vocab_row_refactor_ab.txt)
-template <bool LIST>
+template <bool LIST, class... W>
 __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl, int eos_id,
-                                                              int block_eos, float* out_scores, int64_t* out_ids) {
+                                                              int block_eos, float* out_scores, int64_t* out_ids, W... tw) {
     __shared__ float sv[256];
     __shared__ int si[256];
     __shared__ int lst[LIST ? TOPK_LIST_MAX : 1];
@@ -913,6 +936,7 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits,
     }
     const float lse = mx + __logf(sv[0]);
     __syncthreads();
+    if constexpr (sizeof...(W) > 0) topk_want_store<LIST>(tw..., row, tid, x, V, lse, fb, lst, ncand, eos_id, block_eos);
     float pv = INFINITY;
     int pi = -1;
     for (int k = 0; k < K; ++k) {
@@ -954,9 +978,9 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const f16* logits,
 // 256-candidate block arg-max over the threads' heads.  Same results as the K+2-pass kernel above (value descending, index ascending).
 // Round 6: 1024 threads per row and 16-byte loads (the 256-thread form walked the row three times with 2-byte loads at a 512-byte stride: 113
 // dependent iterations per pass, 73 us per launch at 192 rows -- 5 % of a beam-3 token step); block reductions by wave shuffles + 16 LDS words.
-template <int KMAX, bool LIST>
+template <int KMAX, bool LIST, class... W>
 __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* logits, int64_t ld, int V, int K, const uint8_t* forbid, TopkList tl,
-                                                                     int eos_id, int block_eos, float* out_scores, int64_t* out_ids) {
+                                                                     int eos_id, int block_eos, float* out_scores, int64_t* out_ids, W... tw) {
     __shared__ float red[16], sv[16];
     __shared__ int si[16];
     __shared__ int lst[LIST ? TOPK_LIST_MAX : 1];
@@ -972,6 +996,7 @@ __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* 
     float sum = 0.f;
     row_visit<1024, true>(x, 0, V, [&](float f, int) { sum += __expf(f - mx); });
     const float lse = mx + __logf(block_reduce_sum<1024>(sum, red));
+    if constexpr (sizeof...(W) > 0) topk_want_store<LIST>(tw..., row, tid, x, V, lse, fb, lst, ncand, eos_id, block_eos);
     float lv[KMAX];
     int lidx[KMAX];
 #pragma unroll
@@ -1016,26 +1041,27 @@ __global__ __launch_bounds__(1024) void logsoftmax_topk_small_kernel(const f16* 
         __syncthreads();
     }
 }
+template <class... W>
 static int topk_launch(const char* who, const void* logits, int64_t ld, int rows, int V, int K, const uint8_t* forbid, const TopkList* tl, int eos_id,
-                       int block_eos, float* out_scores, int64_t* out_ids, hipStream_t s) {
+                       int block_eos, float* out_scores, int64_t* out_ids, hipStream_t s, W... tw) {
     const bool vec_ok = ld % 8 == 0 && (uintptr_t)logits % 16 == 0;      // 16-byte row loads; anything else takes the scalar K+2-pass kernel
     const TopkList none = {nullptr, 0, nullptr};
 #define LAUNCH_TOPK(KM)                                                                                                                          \
     do {                                                                                                                                         \
-        if (tl) hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, true>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, nullptr, *tl, \
-                                   eos_id, block_eos, out_scores, out_ids);                                                                       \
-        else hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, false>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, forbid, none,  \
-                                eos_id, block_eos, out_scores, out_ids);                                                                          \
+        if (tl) hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, true, W...>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, nullptr, \
+                                   *tl, eos_id, block_eos, out_scores, out_ids, tw...);                                                              \
+        else hipLaunchKernelGGL((logsoftmax_topk_small_kernel<KM, false, W...>), dim3(rows), dim3(1024), 0, s, (const f16*)logits, ld, V, K, forbid,  \
+                                none, eos_id, block_eos, out_scores, out_ids, tw...);                                                                \
     } while (0)
     if (vec_ok && K <= 4) LAUNCH_TOPK(4);
     else if (vec_ok && K <= 8) LAUNCH_TOPK(8);
     else if (vec_ok && K <= 16) LAUNCH_TOPK(16);
     else if (tl)
-        hipLaunchKernelGGL(logsoftmax_topk_kernel<true>, dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, nullptr, *tl, eos_id, block_eos,
-                           out_scores, out_ids);
+        hipLaunchKernelGGL((logsoftmax_topk_kernel<true, W...>), dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, nullptr, *tl, eos_id, block_eos,
+                           out_scores, out_ids, tw...);
     else
-        hipLaunchKernelGGL(logsoftmax_topk_kernel<false>, dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, forbid, none, eos_id, block_eos,
-                           out_scores, out_ids);
+        hipLaunchKernelGGL((logsoftmax_topk_kernel<false, W...>), dim3(rows), dim3(256), 0, s, (const f16*)logits, ld, V, K, forbid, none, eos_id, block_eos,
+                           out_scores, out_ids, tw...);
 #undef LAUNCH_TOPK
     VLP_CHECK_LAUNCH(who);
     return VLP_OK;
@@ -1054,6 +1080,20 @@ extern "C" int vlp_logsoftmax_topk_list(const void* logits, int64_t ld, int32_t 
     VLP_ENTER(logits, "vlp_logsoftmax_topk_list");
     const TopkList tl = {cand_ids, cand_ld, cand_cnt};
     return topk_launch("vlp_logsoftmax_topk_list", logits, ld, rows, V, K, nullptr, &tl, eos_id, block_eos, out_scores, out_ids, (hipStream_t)stream);
+}
+extern "C" int vlp_logsoftmax_topk_want(const void* logits, int64_t ld, int32_t rows, int32_t V, int32_t K, const uint8_t* forbid, const int32_t* cand_ids,
+                                        int64_t cand_ld, const int32_t* cand_cnt, int32_t eos_id, int32_t block_eos, const int32_t* want_ids, int32_t C,
+                                        float* out_scores, int64_t* out_ids, float* want_val, void* stream) {
+    VLP_CHECK_ARG(logits && out_scores && out_ids && rows > 0 && V > 0 && K > 0 && K <= V && ld >= V, "vlp_logsoftmax_topk_want: bad args");
+    VLP_CHECK_ARG(want_ids && want_val && C >= 1 && C <= 8, "vlp_logsoftmax_topk_want: needs want_ids / want_val with 1 <= C <= 8 (got C=%d)", C);
+    VLP_CHECK_ARG(!(forbid && (cand_ids || cand_cnt)), "vlp_logsoftmax_topk_want: takes the dense forbid mask or the forbid list, not both");
+    VLP_CHECK_ARG((cand_ids == nullptr) == (cand_cnt == nullptr) && (!cand_ids || (cand_ld >= 1 && cand_ld <= TOPK_LIST_MAX)),
+                  "vlp_logsoftmax_topk_want: a forbid list needs cand_ids and cand_cnt with 1 <= cand_ld <= %d", TOPK_LIST_MAX);
+    VLP_ENTER(logits, "vlp_logsoftmax_topk_want");
+    const TopkList tl = {cand_ids, cand_ld, cand_cnt};
+    const TopkWant tw = {want_ids, want_val, C};
+    return topk_launch("vlp_logsoftmax_topk_want", logits, ld, rows, V, K, forbid, cand_ids ? &tl : nullptr, eos_id, block_eos, out_scores, out_ids,
+                             (hipStream_t)stream, tw);
 }
 
 // One wave per hypothesis row r = b*K + k: the words that would complete a repeated n-gram (get_dup_ngram_candidates, modeling.py:1391-1406).
@@ -1257,6 +1297,166 @@ extern "C" int vlp_beam_select_groups(const vlp_beam_select_args* a, int32_t gro
     VLP_ENTER(a->kk_scores, "vlp_beam_select_groups");
     hipLaunchKernelGGL(beam_select_groups_kernel, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a, groups, penalty);
     VLP_CHECK_LAUNCH("vlp_beam_select_groups");
+    return VLP_OK;
+}
+
+// Constrained beam search: beam_select_kernel's step when every sample carries up to 8 phrases of up to 8 word pieces that its caption must
+// mention (the rule, with the state / advance / wanted / bank definitions: vlp_amd/constrained.py).  One wave per sample.  A parent row offers
+// K + C candidates: its top-K list and its C wanted words (vlp_logsoftmax_topk_want), a wanted slot absent when its id is -1 or repeats a list
+// id or an earlier wanted id of the row.  Value, new state and a byte (the bank, 0x80 = dead, 0xFF = absent or taken) of every candidate go to
+// LDS once: 64 * 72 entries of 9 bytes.  A pick orders the candidates by (d ascending, value descending, index ascending) with d = the
+// cursor's distance down to the candidate's bank, wrapping from 0 to Tb, and d = Tb + 1 for a dead candidate: the minimum IS the best
+// candidate of the first bank at or below the cursor that has a live one, and a dead candidate only when no live one is left -- one strided
+// scan and one wave reduction per pick, as beam_select_groups_kernel picks.  The top-K slots are never absent, so every pick finds one.
+// In the search's last frame (`last`) every candidate that leaves a phrase unmet is forbidden as an unmet eos is: the frame ends the
+// hypothesis (an addition to the rule the feature was specified with; last = 0 is that rule).  The eos flag's product is rounded before the
+// sums (pinned in a register, see beam_group_key): the host's two roundings for any flag value.
+DEVFN int cons_advance(int st, int64_t w, const int* cid, const int* cln, int C, int Lc) {
+    int met = st & 0xFF, cur = ((st >> 8) & 0xF) - 1, off = (st >> 16) & 0xFF;
+    if (cur >= 0 && (cur >= C || off >= cln[cur])) { cur = -1; off = 0; }
+    if (cur >= 0) {
+        if (w == (int64_t)cid[cur * Lc + off]) {
+            ++off;
+            if (off == cln[cur]) { met |= 1 << cur; cur = -1; off = 0; }
+            return met | ((cur + 1) << 8) | (off << 16);
+        }
+        cur = -1;
+        off = 0;
+    }
+    for (int c = 0; c < C; ++c) {
+        if (cln[c] > 0 && !((met >> c) & 1) && (int64_t)cid[c * Lc] == w) {
+            if (cln[c] == 1) met |= 1 << c;
+            else { cur = c; off = 1; }
+            break;
+        }
+    }
+    return met | ((cur + 1) << 8) | (off << 16);
+}
+DEVFN int cons_bank(int st, const int* cln, int C) {
+    const int met = st & 0xFF, cur = ((st >> 8) & 0xF) - 1;
+    int t = cur >= 0 ? (st >> 16) & 0xFF : 0;
+    for (int c = 0; c < C; ++c) t += ((met >> c) & 1) ? cln[c] : 0;
+    return t < 64 ? t : 64;
+}
+__global__ __launch_bounds__(64) void beam_select_constrained_kernel(vlp_beam_select_args a, const int32_t* want_ids, const float* want_val,
+                                                                     const int32_t* prev_state, const int32_t* cons_ids, const int32_t* cons_len, int C,
+                                                                     int Lc, int last, int32_t* out_state, int32_t* want_next) {
+    __shared__ float val[64 * 72];
+    __shared__ int nst[64 * 72];
+    __shared__ unsigned char flag[64 * 72];
+    __shared__ int cid[64];
+    __shared__ int cln[8];
+    const int b = blockIdx.x, lane = threadIdx.x, K = a.K, S = K + C, R = a.first ? 1 : K, ncand = R * S;
+    if (lane < C * Lc) cid[lane] = cons_ids[(int64_t)b * C * Lc + lane];
+    if (lane < C) {
+        const int n = cons_len[(int64_t)b * C + lane];
+        cln[lane] = n < 0 ? 0 : (n > Lc ? Lc : n);
+    }
+    __syncthreads();
+    int Tb = 0, full = 0;
+    for (int c = 0; c < C; ++c) {
+        Tb += cln[c];
+        full |= cln[c] > 0 ? 1 << c : 0;
+    }
+    for (int i = lane; i < ncand; i += 64) {
+        const int r = i / S, j = i - r * S;
+        const int64_t row = (int64_t)b * R + r;
+        int64_t w;
+        float v0;
+        bool absent = false;
+        if (j < K) {
+            w = a.kk_ids[row * K + j];
+            v0 = a.kk_scores[row * K + j];
+        } else {
+            const int c = j - K;
+            const int32_t wi = want_ids[row * C + c];
+            w = wi;
+            v0 = want_val[row * C + c];
+            absent = wi == -1;
+            for (int q = 0; q < K; ++q) absent |= a.kk_ids[row * K + q] == w;
+            for (int q = 0; q < c; ++q) absent |= want_ids[row * C + q] == wi;
+        }
+        bool ended = false;
+        int ps = 0;
+        if (!a.first) {
+            const float le = a.last_eos[row];
+            float pen = le * -10000.0f;
+            asm volatile("" : "+v"(pen));
+            v0 = (v0 + pen) + a.last_total[row];
+            ended = le != 0.0f;
+            ps = prev_state[row];
+        }
+        const int ns = ended ? ps : cons_advance(ps, w, cid, cln, C, Lc);
+        const bool unmet = (w == a.eos_id || last) && !ended && (ns & 0xFF) != full;      // an unmet end: eos, or the search's last frame
+        if (unmet) v0 += -10000.0f;
+        val[i] = v0 != v0 ? __int_as_float(0x7fc00000) : v0;          // one NaN (the host's inf - inf has the sign bit set, the device's has not)
+        nst[i] = ns;
+        flag[i] = absent ? 0xFF : (unsigned char)(cons_bank(ns, cln, C) | ((ended || unmet) ? 0x80 : 0));
+    }
+    __syncthreads();
+    int cursor = Tb, my_i = 0;
+    for (int n = 0; n < K; ++n) {
+        int bd = 0x7fffffff, bi = 0x7fffffff;
+        float bv = -INFINITY;
+        for (int i = lane; i < ncand; i += 64) {
+            const int f = flag[i];
+            if (f == 0xFF) continue;
+            const int bk = f & 0x7F;
+            const int d = (f & 0x80) ? Tb + 1 : (cursor >= bk ? cursor - bk : cursor - bk + Tb + 1);
+            float v = val[i];
+            v = v != v ? -INFINITY : v;
+            if (d < bd || (d == bd && (v > bv || (v == bv && i < bi)))) { bd = d; bv = v; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int od = __shfl_xor(bd, o, 64), oi = __shfl_xor(bi, o, 64);
+            const float ov = __shfl_xor(bv, o, 64);
+            if (od < bd || (od == bd && (ov > bv || (ov == bv && oi < bi)))) { bd = od; bv = ov; bi = oi; }
+        }
+        if (bi >= ncand) bi = 0;                       // (cannot happen: R * K >= K slots are never absent)
+        if (bd <= Tb) {
+            const int bk = flag[bi] & 0x7F;
+            cursor = bk > 0 ? bk - 1 : Tb;
+        }
+        if (lane == n) my_i = bi;
+        __syncthreads();
+        if (lane == 0) flag[bi] = 0xFF;
+        __syncthreads();
+    }
+    if (lane < K) {
+        const int i = my_i, r = i / S, j = i - r * S;
+        const int64_t row = (int64_t)b * R + r, o = (int64_t)b * K + lane;
+        const int64_t id = j < K ? a.kk_ids[row * K + j] : (int64_t)want_ids[row * C + (j - K)];
+        const int ns = nst[i];
+        a.out_scores[o] = val[i];
+        a.out_ids[o] = id;
+        a.out_ptrs[o] = r;
+        a.out_eos[o] = id == a.eos_id ? 1.0f : 0.0f;
+        a.src_rows[o] = a.first ? (int64_t)b : (int64_t)b * K + r;
+        a.next_ids[o * a.next_ids_stride] = id;
+        out_state[o] = ns;
+        const int met = ns & 0xFF, cur = ((ns >> 8) & 0xF) - 1, off = (ns >> 16) & 0xFF;
+        for (int c = 0; c < C; ++c) {
+            int wn = -1;
+            if (id != a.eos_id && cln[c] > 0 && !((met >> c) & 1)) wn = (c == cur && off < cln[c]) ? cid[c * Lc + off] : cid[c * Lc];
+            want_next[o * C + c] = wn;
+        }
+    }
+}
+extern "C" int vlp_beam_select_constrained(const vlp_beam_select_args* a, const int32_t* want_ids, const float* want_val, const int32_t* prev_state,
+                                           const int32_t* cons_ids, const int32_t* cons_len, int32_t C, int32_t Lc, int32_t last, int32_t* out_state,
+                                           int32_t* want_next, void* stream) {
+    VLP_CHECK_ARG(a && a->kk_scores && a->kk_ids && a->out_scores && a->out_ids && a->out_ptrs && a->out_eos && a->src_rows && a->next_ids &&
+                      want_ids && want_val && cons_ids && cons_len && out_state && want_next,
+                  "vlp_beam_select_constrained: null operand");
+    VLP_CHECK_ARG(a->B > 0 && a->K >= 1 && a->K <= 64 && C >= 1 && C <= 8 && Lc >= 1 && Lc <= 8,
+                  "vlp_beam_select_constrained: needs B > 0, 1 <= K <= 64, 1 <= C <= 8 and 1 <= Lc <= 8 (got B=%d K=%d C=%d Lc=%d)", a->B, a->K, C, Lc);
+    VLP_CHECK_ARG(a->first || (a->last_total && a->last_eos && prev_state),
+                  "vlp_beam_select_constrained: a later step needs last_total, last_eos and prev_state");
+    VLP_ENTER(a->kk_scores, "vlp_beam_select_constrained");
+    hipLaunchKernelGGL(beam_select_constrained_kernel, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a, want_ids, want_val, prev_state, cons_ids,
+                       cons_len, C, Lc, last ? 1 : 0, out_state, want_next);
+    VLP_CHECK_LAUNCH("vlp_beam_select_constrained");
     return VLP_OK;
 }
 

@@ -28,6 +28,13 @@ A short last batch is filled up with its last image (and the extra rows dropped)
       diverse beam search (vlp_amd.diverse; vlp_beam_select_groups on the device): the beams in G groups, a word penalised by L for every
       earlier group that chose it in the same step.  logprob / value stay unpenalised, so --n_best, --nbest_file and --select work on the
       diverse beam unchanged -- and have hypotheses that differ to choose from.
+  --constraints_file PATH (default: none, the tool as above, byte for byte) runs a constrained beam search (vlp_amd.constrained;
+      vlp_logsoftmax_topk_want and vlp_beam_select_constrained on the device): PATH is a json object {image id: [phrase, ...]}, a phrase a
+      list of word-piece ids or a string whose words are looked up in the vocabulary (--do_lower_case is honoured; a missing word is split
+      by the greedy longest-match-first WordPiece rule with ## continuations).  At most 8 phrases of at most 8 pieces per image; a phrase
+      that needs [UNK] or names a special token is an error, as are --beam_groups > 1 and --beam_size < 2.  Images without an entry are
+      searched unconstrained.  Every record of --output_file (and of --nbest_file) gains "constraints" (the image's phrases as id lists) and
+      "met" (one boolean per phrase); python -m vlp_amd.eval_captions reads the file as it stands.
 """
 import argparse
 import glob
@@ -89,8 +96,22 @@ def parse_args(argv=None):
                    help="diverse beam search: split the --beam_size beams into G groups, 1..--beam_size and dividing it (default 1: the plain search)")
     p.add_argument("--diversity_penalty", type=float, default=0.0, metavar="L",
                    help="with --beam_groups >= 2: subtract L from a word's score for every earlier group that chose it in the same step (default 0)")
+    p.add_argument("--constraints_file", default=None, metavar="PATH",
+                   help="constrained beam search: a json object {image id: [phrase, ...]} of phrases the caption must mention; a phrase is a list "
+                        "of word-piece ids or a string (needs a vocabulary); at most 8 phrases of at most 8 pieces per image")
     add_selection_flags(p)
     a = p.parse_args(argv)
+    a.constraints = None
+    if a.constraints_file:
+        if a.beam_size < 2:
+            p.error("--constraints_file steers a beam search: it needs --beam_size >= 2 (got %d)" % a.beam_size)
+        if a.beam_groups > 1:
+            p.error("--constraints_file and --beam_groups %d (diverse beam search) exclude each other" % a.beam_groups)
+        try:
+            path = vocab_path(a)
+            a.constraints = load_constraints(a.constraints_file, Vocab(path) if path else None, a.do_lower_case)
+        except (OSError, ValueError) as e:
+            p.error("--constraints_file %s: %s" % (a.constraints_file, e))
     if not (1 <= a.beam_groups <= max(a.beam_size, 1)):
         p.error("--beam_groups must be in 1..--beam_size = 1..%d (got %d)" % (max(a.beam_size, 1), a.beam_groups))
     if a.beam_size % a.beam_groups != 0:
@@ -156,6 +177,86 @@ class Vocab(object):
         if missing:
             raise KeyError("not in the vocabulary: %s" % ", ".join(missing))
         return [self.ids[t] for t in tokens]
+
+
+def vocab_path(args):
+    """--vocab_file, else <bert_model>/vocab.txt when --bert_model is a directory that has one, else None."""
+    if args.vocab_file is None and os.path.isdir(args.bert_model) and os.path.exists(os.path.join(args.bert_model, "vocab.txt")):
+        return os.path.join(args.bert_model, "vocab.txt")
+    return args.vocab_file
+
+
+def word_pieces(word, vocab):
+    """The greedy longest-match-first WordPiece split of one word (continuations carry ##) as ids, or None when it cannot be built."""
+    out, start = [], 0
+    while start < len(word):
+        end = len(word)
+        while end > start:
+            piece = ("##" if start else "") + word[start:end]
+            if piece in vocab.ids:
+                break
+            end -= 1
+        if end == start:
+            return None
+        out.append(vocab.ids[piece])
+        start = end
+    return out
+
+
+def phrase_ids(phrase, vocab, do_lower_case=False):
+    """One phrase of a constraints file as word-piece ids: a list of ids as it is, a string word by word (a word of the vocabulary is its id,
+    any other is split by word_pieces).  ValueError for a phrase that is empty, needs [UNK] or contains a special token."""
+    special = special_ids(vocab)
+    if isinstance(phrase, str):
+        if vocab is None:
+            raise ValueError("the phrase %r is text: it needs a vocabulary (--vocab_file, or a --bert_model directory with vocab.txt)" % (phrase,))
+        ids = []
+        for word in (phrase.lower() if do_lower_case else phrase).split():
+            if word.upper() in ("[CLS]", "[UNK]", "[SEP]", "[MASK]", "[PAD]"):
+                raise ValueError("the phrase %r contains the special token %s" % (phrase, word.upper()))
+            pieces = [vocab.ids[word]] if word in vocab.ids else word_pieces(word, vocab)
+            if pieces is None:
+                raise ValueError("the phrase %r cannot be built from the vocabulary without [UNK] (word %r)" % (phrase, word))
+            ids.extend(pieces)
+    elif isinstance(phrase, list) and all(isinstance(t, int) and not isinstance(t, bool) for t in phrase):
+        ids = list(phrase)
+        if any(t < 0 or (vocab is not None and t >= len(vocab)) for t in ids):
+            raise ValueError("the phrase %r holds an id outside the vocabulary" % (phrase,))
+    else:
+        raise ValueError("a phrase is a string or a list of word-piece ids (got %r)" % (phrase,))
+    if not ids:
+        raise ValueError("the phrase %r is empty" % (phrase,))
+    if any(t in special for t in ids):
+        raise ValueError("the phrase %r contains a special token ([CLS], [UNK], [SEP], [MASK] or [PAD])" % (phrase,))
+    return ids
+
+
+def load_constraints(path, vocab, do_lower_case=False):
+    """A constraints file -> {image id as a string: [id list, ...]}; ValueError names what is wrong with it."""
+    from .constrained import MAX_CONS, MAX_LEN
+    with open(path, "r", encoding="utf-8") as f:
+        raw = json.load(f)
+    if not isinstance(raw, dict) or not all(isinstance(v, list) for v in raw.values()):
+        raise ValueError("expected a json object that maps an image id to a list of phrases")
+    out = {}
+    for imgid, phrases in raw.items():
+        ids = [phrase_ids(ph, vocab, do_lower_case) for ph in phrases]
+        if len(ids) > MAX_CONS:
+            raise ValueError("image %s has %d phrases, at most %d are searched for" % (imgid, len(ids), MAX_CONS))
+        for ph, t in zip(phrases, ids):
+            if len(t) > MAX_LEN:
+                raise ValueError("the phrase %r of image %s is %d word pieces long, at most %d" % (ph, imgid, len(t), MAX_LEN))
+        out[str(imgid)] = ids
+    return out
+
+
+def constraint_shape(constraints):
+    """(C, Lc) of a whole run: one shape for every batch, so that the token steps are captured once."""
+    return (max([len(p) for p in constraints.values()] + [1]), max([len(t) for p in constraints.values() for t in p] + [1]))
+
+
+def met_list(mask, phrases):
+    return [bool((int(mask) >> c) & 1) for c in range(len(phrases))]
 
 
 def special_ids(vocab):
@@ -254,8 +355,9 @@ def build_decoder(args, vocab, state, device):
     return model.eval()
 
 
-def decode_images(model, store, keys, args, vocab, device):
-    """Captions of the store rows `keys`, in order."""
+def decode_images(model, store, keys, args, vocab, device, constraints=None):
+    """Captions of the store rows `keys`, in order.  constraints: per key the image's phrases as id lists (an empty list: none); the
+    result is then a list of (caption, met mask)."""
     cls_id, unk_id, sep_id, mask_id, pad_id = special_ids(vocab)
     Nv, bs = args.len_vis_input, args.batch_size
     if store.nv != Nv:
@@ -274,18 +376,41 @@ def decode_images(model, store, keys, args, vocab, device):
             store.gather(chunk, feat.numpy(), cls.numpy(), bbox.numpy())
             img = feat.to(device, non_blocking=True)
             regions = RawRegions(bbox.to(device, non_blocking=True), cls.to(device, non_blocking=True))
-            out = model(img, regions, input_ids, seg, pos, mask, task_idx=None)
+            out = model(img, regions, input_ids, seg, pos, mask, task_idx=None, **_batch_constraints(constraints, i, n, bs))
             ids = (out["pred_seq"] if args.beam_size > 1 else out[0]).tolist()       # synchronises: the pinned buffers are free again
-            captions.extend(caption_of(w, vocab, sep_id, pad_id) for w in ids[:n])
+            if constraints is None:
+                captions.extend(caption_of(w, vocab, sep_id, pad_id) for w in ids[:n])
+            else:
+                captions.extend(zip((caption_of(w, vocab, sep_id, pad_id) for w in ids[:n]), out["pred_met"].tolist()[:n]))
     return captions
 
 
-def decode_images_nbest(model, store, keys, args, vocab, device, df=None):
+_shape_of_run = {}
+
+
+def _run_shape(constraints):
+    """constraint_shape of a run's per-image list, computed once per list."""
+    if _shape_of_run.get("id") != id(constraints):
+        _shape_of_run.update(id=id(constraints), shape=constraint_shape({k: p for k, p in enumerate(constraints)}))
+    return _shape_of_run["shape"]
+
+
+def _batch_constraints(constraints, i, n, bs):
+    """The model's constraints= keyword for the batch of images i .. i+n-1 (filled up to bs with its last image), at the run's one (C, Lc)."""
+    if constraints is None:
+        return {}
+    from .constrained import pack_constraints
+    C, Lc = _run_shape(constraints)
+    part = constraints[i:i + n]
+    return {"constraints": pack_constraints(part + [part[-1]] * (bs - n), bs, C, Lc)}
+
+
+def decode_images_nbest(model, store, keys, args, vocab, device, df=None, constraints=None):
     """--n_best N >= 2: per store row of `keys`, in order, (hypotheses, pick).  hypotheses: N dicts {rank, caption, logprob, value, ok[,
     utility]} from the ranked list of the image's beam search (vlp_beam_nbest; nothing but the final read goes to the host); pick: the rank
     --select keeps -- none: 0; logprob: the ok hypothesis with the largest logprob; consensus (df: the table): the hypothesis with the
     largest CIDEr-D against the image's other hypotheses, scored on the device, the rows of rank > 0 that are not ok emptied first.
-    Ties go to the lowest rank."""
+    Ties go to the lowest rank.  constraints: as decode_images takes them; every hypothesis then also carries its met mask, "met"."""
     from . import consensus as CS
     from .scst import clean_captions
     cls_id, unk_id, sep_id, mask_id, pad_id = special_ids(vocab)
@@ -306,7 +431,7 @@ def decode_images_nbest(model, store, keys, args, vocab, device, df=None):
             store.gather(chunk, feat.numpy(), cls.numpy(), bbox.numpy())
             img = feat.to(device, non_blocking=True)
             regions = RawRegions(bbox.to(device, non_blocking=True), cls.to(device, non_blocking=True))
-            tr = model(img, regions, input_ids, seg, pos, mask, task_idx=None)
+            tr = model(img, regions, input_ids, seg, pos, mask, task_idx=None, **_batch_constraints(constraints, i, n, bs))
             if args.select == "consensus":                          # launched before the read below: no synchronisation of its own
                 ok_nb = tr["nbest_ok"].transpose(0, 1).reshape(N * bs).bool()          # sample-major again: rank k of image b = row k*bs + b
                 ok_nb[:bs] = True                                   # rank 0 stays as it is
@@ -318,6 +443,9 @@ def decode_images_nbest(model, store, keys, args, vocab, device, df=None):
             for b in range(n):                                      # (the rows that pad a short last batch are dropped, their picks too)
                 hyps = [{"rank": k, "caption": caption_of(ids[b][k], vocab, sep_id, pad_id), "logprob": logp[b][k], "value": val[b][k],
                          "ok": bool(ok[b][k])} for k in range(N)]
+                if constraints is not None:
+                    for k, m in enumerate(tr["nbest_met"][b].tolist()):
+                        hyps[k]["met"] = m
                 k_sel = 0
                 if args.select == "consensus":
                     k_sel = pick[b]
@@ -359,9 +487,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
 
-    vocab_file = args.vocab_file
-    if vocab_file is None and os.path.isdir(args.bert_model) and os.path.exists(os.path.join(args.bert_model, "vocab.txt")):
-        vocab_file = os.path.join(args.bert_model, "vocab.txt")
+    vocab_file = vocab_path(args)
     vocab = Vocab(vocab_file) if vocab_file else None
 
     with open(args.src_file, "r", encoding="utf-8") as f:
@@ -378,6 +504,15 @@ def main(argv=None):
         df = consensus_doc_freq(args.consensus_df, args.max_tgt_length, special_ids(vocab)[2])
         logger.info("--consensus_df %s: %d n-grams over %d images", args.consensus_df, len(df), df.n_docs)
 
+    cons = None          # --constraints_file: per image, in order, its phrases as id lists (none for an image without an entry)
+    if args.constraints is not None:
+        cons = [args.constraints.get(str(imgid), []) for imgid, _ in images]
+
+    def with_met(records, masks):
+        if cons is None:
+            return records
+        return [dict(r, constraints=ph, met=met_list(m, ph)) for r, ph, m in zip(records, cons, masks)]
+
     ckpts = sorted(glob.glob(args.model_recover_path.strip()))
     if not ckpts:
         raise FileNotFoundError("--model_recover_path %r matches no file" % (args.model_recover_path,))
@@ -386,20 +521,25 @@ def main(argv=None):
         logger.info("***** Recover model: %s *****", ckpt)
         model = build_decoder(args, vocab, torch.load(ckpt, map_location="cpu"), device)
         if args.n_best > 1:
-            ranked = decode_images_nbest(model, store, [key for _, key in images], args, vocab, device, df=df)
+            ranked = decode_images_nbest(model, store, [key for _, key in images], args, vocab, device, df=df, constraints=cons)
             if args.nbest_file:          # every hypothesis that is one: rank 0 always, the others when ok
                 with open(nbest_path(args, ckpt, len(ckpts)), "w") as f:
                     json.dump([dict({"image_id": imgid, "rank": h["rank"], "caption": h["caption"], "logprob": _finite(h["logprob"]),
-                                     "value": _finite(h["value"])}, **({"utility": h["utility"]} if "utility" in h else {}))
-                               for (imgid, _), (hyps, _) in zip(images, ranked) for h in hyps if h["ok"] or h["rank"] == 0], f)
+                                     "value": _finite(h["value"])}, **dict(({"utility": h["utility"]} if "utility" in h else {}),
+                                                                           **({"constraints": cons[n], "met": met_list(h["met"], cons[n])}
+                                                                              if cons is not None else {})))
+                               for n, ((imgid, _), (hyps, _)) in enumerate(zip(images, ranked)) for h in hyps if h["ok"] or h["rank"] == 0], f)
             if args.select == "none":
                 predictions = [{"image_id": imgid, "caption": hyps[0]["caption"]} for (imgid, _), (hyps, _) in zip(images, ranked)]
             else:
                 predictions = [{"image_id": imgid, "caption": hyps[k]["caption"], "rank": k, "logprob": _finite(hyps[k]["logprob"]),
                                 "utility": hyps[k].get("utility")} for (imgid, _), (hyps, k) in zip(images, ranked)]
+            predictions = with_met(predictions, [hyps[k].get("met", 0) if args.select != "none" else hyps[0].get("met", 0) for hyps, k in ranked])
         else:
-            captions = decode_images(model, store, [key for _, key in images], args, vocab, device)
-            predictions = [{"image_id": imgid, "caption": cap} for (imgid, _), cap in zip(images, captions)]
+            captions = decode_images(model, store, [key for _, key in images], args, vocab, device, constraints=cons)
+            if cons is not None:
+                captions, masks = [c for c, _ in captions], [m for _, m in captions]
+            predictions = with_met([{"image_id": imgid, "caption": cap} for (imgid, _), cap in zip(images, captions)], masks if cons is not None else None)
         out = output_path(args, ckpt, len(ckpts))
         with open(out, "w") as f:
             json.dump(predictions, f)

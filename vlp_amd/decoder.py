@@ -9,6 +9,7 @@ import collections
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as K
@@ -404,7 +405,8 @@ class Decoder(object):
     NGRAM_MAX_FRAMES = 256       # csrc/elementwise.hip: NGRAM_MAX_FRAMES frames per hypothesis (and <= TOPK_LIST_MAX = 1024 ids per list)
 
     def decode_beam(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, mask_word_id, beam_size, eos_id,
-                    min_len=0, forbid_fn=None, ngram=None, groups=1, diversity=0.0, group_select="device"):
+                    min_len=0, forbid_fn=None, ngram=None, groups=1, diversity=0.0, group_select="device", constraints=None,
+                    constrained_select="device"):
         """Beam search frames (modeling.py:1255-1430) on the K/V-cache decoder.  The first step runs B sequences; its cache rows are
         replicated to the B*K beams (first_expand), afterwards every step decodes B*K sequences and the caches follow the back
         pointers (select_beam_items) -- only the generated positions; the prefix is identical for all beams of a sample and is kept,
@@ -420,6 +422,15 @@ class Decoder(object):
         the search as it is and refuses a diversity.
         `group_select="host"` is the A/B and fallback path of G > 1: every frame copies the top-K lists and the last frame's totals / eos flags
         to the host, runs diverse.beam_select_groups_host and uploads the frame.
+        `constraints=(cons_ids [B, C, Lc], cons_len [B, C])` is a constrained beam search (vlp_amd.constrained is the rule; not in the
+        reference): up to 8 phrases of up to 8 word pieces per image that its caption must mention.  The pair is checked on the host and
+        copied into buffers of the workspace, with the first frame's wanted words, before anything is launched: the captured steps point at
+        those buffers, never at the caller's tensors.  A step then launches vlp_logsoftmax_topk_want for the top-K call and
+        vlp_beam_select_constrained for vlp_beam_select (the last frame with its `last` flag: a hypothesis cut off by the target length
+        unmet is forbidden as an unmet eos is) -- one for one, captured / replayed, ("constrained", C, Lc) in the plan key; ngram=,
+        forbid_fn= and min_len work as before, groups > 1 is refused.  `constrained_select="host"` runs
+        constrained.beam_select_constrained_host per frame instead (A/B and fallback, not planned).  The call returns a fourth tensor, the
+        state frames int32 [frames, B, K].  Without constraints nothing changes, launch for launch.
         Returns (total_scores, step_ids, back_ptrs) as [frames, B, K] tensors on the device."""
         Kb, eos_id = int(beam_size), int(eos_id)
         G, lam = int(groups), float(diversity)
@@ -433,6 +444,17 @@ class Decoder(object):
             check_groups(Kb, G, lam)
         if Kb < 2 or Kb > 64:
             raise RuntimeError("vlp_amd: beam size must be in [2, 64]")
+        if constrained_select not in ("device", "host"):
+            raise ValueError("constrained_select must be 'device' or 'host', got %r" % (constrained_select,))
+        cons = None
+        if constraints is not None:
+            from . import constrained as CB
+            if G > 1:
+                raise ValueError("vlp_amd: constraints and groups > 1 (diverse beam search) exclude each other")
+            cons = CB.check_constraints(constraints[0], constraints[1], self._model().config.vocab_size, eos_id)
+            if cons[0].shape[0] != input_ids.shape[0]:
+                raise ValueError("vlp_amd: constraints for %d images, batch of %d" % (cons[0].shape[0], input_ids.shape[0]))
+            CB.check_limits(Kb, cons[0].shape[1], cons[0].shape[2])
         if ngram is not None:
             if forbid_fn is not None:
                 raise RuntimeError("vlp_amd: decode_beam takes forbid_fn (host blocking) or ngram (device blocking), not both")
@@ -448,7 +470,7 @@ class Decoder(object):
         tot, wids, ptrs, eos = ws["tot"], ws["wids"], ws["ptrs"], ws["eos"]
         bufs = (ws["kvA"], ws["kvB"])
         host = {"forbid": None}          # forbid_fn's mask for the next frame
-        on_host = G > 1 and group_select == "host"
+        on_host = (G > 1 and group_select == "host") or (cons is not None and constrained_select == "host")
         # what the selection bakes into a captured step beyond (s, eos_id, block_eos): the blocking's size and ignore list, and (G, lambda)
         plan_tag = ()
         if ngram is not None:
@@ -460,9 +482,34 @@ class Decoder(object):
             plan_tag = ("ngram", ng_n, ign)
         if G > 1:
             plan_tag += ("groups", G, lam)
+        if cons is not None:
+            Cc, Lc = cons[0].shape[1], cons[0].shape[2]
+            cw = ws.setdefault("constrained", {}).get((Cc, Lc))
+            if cw is None:       # owned by the workspace, one set per (C, Lc): what the captured launches of that plan key point at
+                i32 = dict(device=self.device, dtype=torch.int32)
+                cw = ws["constrained"][(Cc, Lc)] = dict(
+                    ids=torch.empty(B, Cc, Lc, **i32), len=torch.empty(B, Cc, **i32), want=torch.empty(2, c.R, Cc, **i32),
+                    want_val=torch.empty(c.R, Cc, device=self.device, dtype=torch.float32), state=torch.empty(c.out_len, B, Kb, **i32))
+            cw["ids"].copy_(torch.from_numpy(cons[0]))
+            cw["len"].copy_(torch.from_numpy(cons[1]))
+            # frame 0's wanted words: the first piece of every phrase, -1 for an unused slot (wanted(0))
+            # (two want buffers: frame s reads want[s & 1] and writes the next frame's words to the other one)
+            cw["want"][0, :B].copy_(torch.from_numpy(np.where(cons[1] > 0, cons[0][:, :, 0], -1).astype(np.int32)))
+            cstate = cw["state"]
+            plan_tag += ("constrained", Cc, Lc)
 
         def block_eos(s):
             return bool(min_len) and (s + 1 <= min_len)
+
+        def select_constrained_on_host(s, first):
+            kk_s, kk_i = (ws["kk_s"][:B], ws["kk_i"][:B]) if first else (ws["kk_s"].view(B, Kb, Kb), ws["kk_i"].view(B, Kb, Kb))
+            rows = B if first else c.R
+            out = CB.beam_select_constrained_host(kk_s, kk_i, cw["want"][s & 1, :rows], cw["want_val"][:rows], None if first else tot[s - 1],
+                                                  None if first else eos[s - 1], None if first else cstate[s - 1], cons[0], cons[1], first, eos_id,
+                                                  last=s + 1 == n_steps)
+            for dst, src in ((tot[s], out[0]), (wids[s], out[1]), (ptrs[s], out[2]), (eos[s], out[3]), (ws["src_rows"], out[4]),
+                             (ws["xids"][:, 0], out[1].reshape(-1)), (cstate[s], out[6]), (cw["want"][(s + 1) & 1], out[7])):
+                dst.copy_(torch.from_numpy(src))
 
         def select_on_host(s, first):
             from .diverse import beam_select_groups_host
@@ -477,13 +524,26 @@ class Decoder(object):
             # step 0: B sequences.  first_expand (:1325-1332) is implicit: the prefix K|V of a sample stays in its per-sample cache and is
             # shared by its beams inside the attention kernel; the per-beam caches only ever hold generated positions
             rows, prev_tot, prev_eos = (B, None, None) if first else (c.R, tot[s - 1], eos[s - 1])
-            if ngram is not None and not first:
+            if cons is not None:
+                listed = ngram is not None and not first
+                K.logsoftmax_topk_want(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], cw["want"][s & 1], cw["want_val"],
+                                       forbid=None if listed else host["forbid"], cand_ids=ws["cand_ids"] if listed else None,
+                                       cand_cnt=ws["cand_cnt"] if listed else None, eos_id=eos_id, block_eos=block_eos(s))
+            elif ngram is not None and not first:
                 K.logsoftmax_topk_list(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], ws["cand_ids"], ws["cand_cnt"], eos_id=eos_id,
                                        block_eos=block_eos(s))
             else:
                 K.logsoftmax_topk(ws["logits"], ws["Vp"], rows, V, Kb, ws["kk_s"], ws["kk_i"], forbid=host["forbid"], eos_id=eos_id,
                                   block_eos=block_eos(s))
-            if G == 1:
+            if cons is not None:
+                if on_host:
+                    select_constrained_on_host(s, first)
+                else:
+                    K.beam_select_constrained(ws["kk_s"], ws["kk_i"], prev_tot, prev_eos, tot[s], wids[s], ptrs[s], eos[s], ws["src_rows"],
+                                              ws["xids"][:, 0], B, Kb, first, eos_id, cw["want"][s & 1], cw["want_val"],
+                                              None if first else cstate[s - 1], cw["ids"], cw["len"], Cc, Lc, cstate[s], cw["want"][(s + 1) & 1],
+                                              last=s + 1 == n_steps)
+            elif G == 1:
                 K.beam_select(ws["kk_s"], ws["kk_i"], prev_tot, prev_eos, tot[s], wids[s], ptrs[s], eos[s], ws["src_rows"], ws["xids"][:, 0],
                               B, Kb, first, eos_id)
             elif on_host:
@@ -509,6 +569,8 @@ class Decoder(object):
 
         self._decode_steps(c, select, lambda s: bufs[(s - 1) & 1], (ws["kv"], c.in_len, Kb), plan_key,
                            between=ask_forbid_fn if forbid_fn is not None else None)
+        if cons is not None:
+            return tot[:n_steps].clone(), wids[:n_steps].clone(), ptrs[:n_steps].clone(), cstate[:n_steps].clone()
         return tot[:n_steps].clone(), wids[:n_steps].clone(), ptrs[:n_steps].clone()
 
     def beam_nbest(self, tot, wids, ptrs, n_best, eos_id, length_penalty, out_len):

@@ -622,6 +622,9 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
     # beam_groups > 1 (diverse beam search): "device" = vlp_beam_select_groups in every frame, steps captured / replayed; "host" =
     # vlp_amd.diverse.beam_select_groups_host with a round trip per frame (A/B and fallback).  Same results.
     group_select = "device"
+    # constraints= (constrained beam search): "device" = vlp_logsoftmax_topk_want + vlp_beam_select_constrained in every frame, steps captured /
+    # replayed; "host" = vlp_amd.constrained.beam_select_constrained_host with a round trip per frame (A/B and fallback).  Same results.
+    constrained_select = "device"
 
     def __init__(self, config, mask_word_id=0, num_labels=2, search_beam_size=1, length_penalty=1.0, eos_id=0,
                  forbid_duplicate_ngrams=False, forbid_ignore_set=None, ngram_size=3, min_len=0, enable_butd=False, len_vis_input=49,
@@ -659,7 +662,7 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
                              "1..search_beam_size and dividing it, and a finite diversity_penalty >= 0 that is 0 unless beam_groups >= 2" % (G, lam, K))
 
     def forward(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, sample_mode="greedy",
-                n_samples=1, temperature=1.0, top_k=0, top_p=1.0, return_entropy=False):
+                n_samples=1, temperature=1.0, top_k=0, top_p=1.0, return_entropy=False, constraints=None):
         """Returns (output_ids [B, n], output_probs [B, n]) with n = token_type_ids.shape[1] - input_ids.shape[1], as :1253.
         output_probs are the maximal prediction scores (logits), exactly what the reference returns in greedy mode (:1228).
         n_samples = K > 1 with sample_mode='sample' (not in the reference): K draws per image, returned sample-major as [K*B, n] ids and
@@ -673,7 +676,10 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         log-probabilities are softmax(logits / temperature)'s, differentiable through the tempered scoring pass (vlp_token_policy_fwd /
         _bwd); top_k / top_p stay refused there.
         return_entropy=True (train() mode with gradients and sample_mode='sample' only): returns (ids, logp, entropy), all [rows, n]; entropy
-        is the sampled policy's entropy at every position, a second differentiable output of the same scoring pass."""
+        is the sampled policy's entropy at every position, a second differentiable output of the same scoring pass.
+        constraints (beam search only, see beam_search): phrases every image's caption must mention; per-call data, hence a keyword here."""
+        if constraints is not None and (self.search_beam_size < 2 or sample_mode != "greedy" or n_samples != 1 or return_entropy):
+            raise ValueError("constraints steer a beam search: they need search_beam_size >= 2 and take no sampling arguments")
         if not input_ids.is_cuda:
             raise RuntimeError("vlp_amd: the decoder runs on the HIP engine only (inputs must be on the GPU); there is no CPU path")
         n_samples = int(n_samples)
@@ -721,7 +727,8 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
                                                        self.mask_word_id, n_samples)
         if self.search_beam_size > 1:
             with torch.no_grad():
-                return self.beam_search(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=task_idx)
+                return self.beam_search(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=task_idx,
+                                        constraints=constraints)
         if sample_mode not in ("greedy", "sample"):
             raise NotImplementedError("sample_mode=%r (the reference knows 'greedy' and 'sample', modeling.py:1227-1237)" % (sample_mode,))
         if sample_mode == "sample" and self.training and torch.is_grad_enabled():
@@ -811,7 +818,7 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             return mask
         return step
 
-    def beam_search(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None):
+    def beam_search(self, vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, task_idx=None, constraints=None):
         """Returns the reference's traces dict (:1436-1494): 'pred_seq' [B, L] (0 padded), 'scores' f32 / 'wids' / 'ptrs' [B, L, K]
         (frames padded with zeros to the output length L), on the input device.
         With n_best = N > 1 or backtrack = "device" the hypotheses come from vlp_beam_nbest (Engine.beam_nbest; the rule is
@@ -819,9 +826,27 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
         the ranked list of every image: 'nbest_seq' [B, N, L], 'nbest_score' f32 (cumulative log-probability) / 'nbest_value' f64 (score +
         length_penalty * length) / 'nbest_len' int32 / 'nbest_ok' uint8 [B, N] (0: a hypothesis that went on after its eos, or an empty one).
         With beam_groups = G > 1 the frames are those of a diverse beam search (vlp_amd.diverse: G groups of K / G beams, diversity_penalty per
-        earlier pick of the same word in a frame); the scores stay unpenalised log-probabilities, so everything above keeps its meaning."""
+        earlier pick of the same word in a frame); the scores stay unpenalised log-probabilities, so everything above keeps its meaning.
+        constraints (not in the reference; vlp_amd.constrained is the rule): phrases the caption of every image must mention, as a
+        (cons_ids [B, C, Lc], cons_len [B, C]) pair or a list, one entry per image, of lists of word-piece id lists (<= 8 phrases of <= 8
+        pieces).  The frames are then those of a constrained beam search and the dict also carries 'cons_state' int32 [B, L, K] (every beam's
+        constraint state, zero padded like the frames), 'pred_met' int32 [B] (the met mask of pred_seq; bit c: phrase c is mentioned) and,
+        with n_best > 1, 'nbest_met' int32 [B, N]: constrained.constraints_met of the returned sequences, computed on the host.
+        beam_groups > 1 is refused.  constraints=None is the search as it is."""
         B, out_len = input_ids.shape[0], token_type_ids.shape[1]
         K = self.search_beam_size
+        cons = None
+        if constraints is not None:
+            from . import constrained as CB
+            if self.constrained_select not in ("device", "host"):
+                raise ValueError("constrained_select must be 'device' or 'host', got %r" % (self.constrained_select,))
+            if self.beam_groups > 1:
+                raise ValueError("constraints and beam_groups=%d (diverse beam search) exclude each other" % self.beam_groups)
+            if isinstance(constraints, (tuple, list)) and len(constraints) == 2 and all(hasattr(t, "shape") for t in constraints):
+                cons = constraints
+            else:
+                cons = CB.pack_constraints(constraints, B)
+            cons = CB.check_constraints(cons[0], cons[1], self.config.vocab_size, self.eos_id)
         if self.backtrack not in ("device", "host"):
             raise ValueError("backtrack must be 'device' or 'host', got %r" % (self.backtrack,))
         if not 1 <= self.n_best <= K:
@@ -837,12 +862,31 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
                 ngram = (self.ngram_size, self.forbid_ignore_set)
             else:                    # ngram_size == 1 (the reference's seq[-0:] quirk) stays on the host
                 forbid_fn = self._ngram_blocker(B, self.config.vocab_size)
-        tot, wids, ptrs = self.engine.decode_beam(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
-                                                  K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn, ngram=ngram,
-                                                  **(dict(groups=self.beam_groups, diversity=self.diversity_penalty, group_select=self.group_select)
-                                                     if self.beam_groups > 1 else {}))
+        kw = dict(groups=self.beam_groups, diversity=self.diversity_penalty, group_select=self.group_select) if self.beam_groups > 1 else {}
+        if cons is not None:
+            kw = dict(constraints=cons, constrained_select=self.constrained_select)
+        res = self.engine.decode_beam(vis_feats, vis_pe, input_ids, token_type_ids, position_ids, attention_mask, self.mask_word_id,
+                                      K, self.eos_id, min_len=self.min_len, forbid_fn=forbid_fn, ngram=ngram, **kw)
+        tot, wids, ptrs = res[:3]
         frames = tot.shape[0]
         dev = input_ids.device
+
+        def with_constraints(out):
+            """The constrained search's extra entries: the state frames, and the met masks of the returned sequences (host)."""
+            if cons is None:
+                return out
+            st = torch.zeros(B, out_len, K, dtype=torch.int32, device=dev)
+            st[:, :frames] = res[3].permute(1, 0, 2)
+            out["cons_state"] = st
+
+            def met(seqs):                   # [B, n, L] -> int32 [B, n]
+                a = seqs.cpu().numpy()
+                return torch.tensor([[CB.constraints_met(a[b, n], cons[0][b], cons[1][b], eos_id=self.eos_id) for n in range(a.shape[1])]
+                                     for b in range(B)], dtype=torch.int32, device=dev)
+            out["pred_met"] = met(out["pred_seq"][:, None])[:, 0]
+            if "nbest_seq" in out and self.n_best > 1:
+                out["nbest_met"] = met(out["nbest_seq"])
+            return out
         # frames stay on the device: [frames, B, K] -> [B, out_len, K], zero padded (three small launches; no per-sample host loop)
         scores = torch.zeros(B, out_len, K, dtype=torch.float32, device=dev)
         wid_o = torch.zeros(B, out_len, K, dtype=torch.long, device=dev)
@@ -857,10 +901,10 @@ class BertForSeq2SeqDecoder(PreTrainedBertModel):
             out = {"pred_seq": seq[:B].clone(), "scores": scores, "wids": wid_o, "ptrs": ptr_o}     # (copies: the workspace keeps the kernel's rows)
             for name, t in (("nbest_seq", seq), ("nbest_score", score), ("nbest_value", value), ("nbest_len", length), ("nbest_ok", ok)):
                 out[name] = by_image(t, N).clone(memory_format=torch.contiguous_format)
-            return out
+            return with_constraints(out)
         # best hypothesis of every sample (:1446-1474), vectorised over the batch on the host: ONE device -> host copy of the three frame tensors
         pred = self._backtrack_batch(tot.cpu().numpy(), wids.cpu().numpy(), ptrs.cpu().numpy(), out_len)
-        return {"pred_seq": torch.from_numpy(pred).to(dev), "scores": scores, "wids": wid_o, "ptrs": ptr_o}
+        return with_constraints({"pred_seq": torch.from_numpy(pred).to(dev), "scores": scores, "wids": wid_o, "ptrs": ptr_o})
 
     def _backtrack_batch(self, scores, words, back, out_len):
         """The best hypothesis (:1446-1474) of all samples at once (numpy; arrays [frames, B, K]) -> int64 [B, out_len], 0 padded: candidates are the
